@@ -23,6 +23,9 @@ Prints ONE JSON line on rank 0, including
   roofline     : the dominant kernel vs the dense fp16/bf16 MFMA peak
   parity       : measured in this run - the HIP kernels vs the committed reference goldens (tests/golden)
   cpu_baseline : the oracle (CPU restatement of the reference, pinned by the goldens) timed on this box's host cores
+
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (see write_outputs).  The inputs are seeded: two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -94,7 +97,48 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--cpu-rays", type=int, default=512)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, float64 "
+                         "kept; at most 64 MB in all, larger outputs as a fixed seeded sample of their rows): render - the render() dict; "
+                         "train - the step's [loss, edge_loss] and the parameters after it")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20     # bytes, all files of --dump-outputs together
+
+
+def snapshot_outputs(ret, modules=()):
+    """Host copies of what one step returned (a tensor, or a dict of them) plus the parameters of `modules` ((prefix, module) pairs)."""
+    if isinstance(ret, torch.Tensor):
+        ret = {"loss": ret}
+    out = {}
+    for k, v in (ret or {}).items():
+        if isinstance(v, torch.Tensor):
+            out[k] = v.detach().as_subclass(torch.Tensor).to("cpu", copy=True)
+    for prefix, m in modules:
+        for k, p in m.named_parameters():
+            out[f"{prefix}.{k}"] = p.detach().to("cpu", copy=True)
+    return out
+
+
+def write_outputs(d, tensors):
+    """DIR/<name>.npy for every tensor: float64 stays float64, everything else becomes float32.  Over DUMP_BUDGET, every array with more
+    than one row keeps the same fraction of its rows, drawn by a generator seeded with the row count: the same rows of every array of
+    one length (the same rays), and the same rows from run to run."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: v.numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32) for k, v in tensors.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_BUDGET:
+        fixed = sum(a.nbytes for a in arrs.values() if a.ndim == 0 or a.shape[0] <= 1)
+        frac = (DUMP_BUDGET - fixed) / (total - fixed)
+        for k, a in arrs.items():
+            if a.ndim and a.shape[0] > 1:
+                n = a.shape[0]
+                rows = np.sort(np.random.default_rng(n).choice(n, max(1, int(n * frac)), replace=False))
+                arrs[k] = a[rows]
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return {"dir": d, "files": len(arrs), "bytes": sum(a.nbytes for a in arrs.values()), "sampled": bool(total > DUMP_BUDGET)}
 
 
 def relaunch_under_launcher(n, backend="nccl"):
@@ -357,10 +401,11 @@ class _RunnerLoop:
 
 
 def train_dropin_key(dev, precision, rays, steps=40, warmup=10, n_samples=64, n_importance=64, up_sample_steps=4, fused_adam=False,
-                     patched=False):
+                     patched=False, outputs=None):
     """See _RunnerLoop.  `patched`: ``emap_amd.dropin.train_wrapper`` around the SAME ``train_udf`` (what ``dropin.patch_runner(train=True)``
     does to ``Runner_UDF``): host-mirrored variance / beta / gamma, gradients installed by RenderFn, FusedAdam swapped in, deferred
-    tensorboard scalars.  Host reads of device values per step are counted (writer) + known (.item() / format / bool of the loop body)."""
+    tensorboard scalars.  Host reads of device values per step are counted (writer) + known (.item() / format / bool of the loop body).
+    `outputs` (a dict): receives the parameters after the last timed step (the runner's step returns nothing else)."""
     from emap_amd import dropin
     loop = _RunnerLoop(dev, precision, rays, fused_adam, n_samples, n_importance, up_sample_steps)
     S = loop.renderer.samples_per_ray
@@ -371,6 +416,9 @@ def train_dropin_key(dev, precision, rays, steps=40, warmup=10, n_samples=64, n_
         train = dropin.train_wrapper(train, sys.modules[__name__], single_thread_autograd=os.environ.get("EMAP_DROPIN_MT", "0") != "1")
     dt, med = train(loop, run)
     loop.renderer.check_errors()
+    if outputs is not None:
+        outputs.update(snapshot_outputs(None, [("udf_network", loop.udf_network), ("deviation_network", loop.variance_network_fine),
+                                               ("beta_network", loop.beta_network)]))
     n_steps = steps + warmup
     writer_reads = SummaryWriter.device_reads / n_steps
     # loop body: unpatched - beta.item(), bool(variance.mean() < ...), format(psnr), loss.item(), beta.item() for the writer = 5 reads of
@@ -632,8 +680,9 @@ def main():
         # the reference runner's own optimizer step on the drop-in classes (one GPU: EMAP itself is single-GPU)
         if world != 1:
             raise SystemExit("bench.py --path dropin runs on one GPU (the reference's loop has no data parallelism)")
+        dumped = {} if a.dump_outputs else None
         res = train_dropin_key(dev, a.precision, rays, steps=a.steps, warmup=a.warmup + a.settle_steps // 10, fused_adam=(a.path == "dropin-fused"),
-                               patched=(a.path == "dropin-patched"))
+                               patched=(a.path == "dropin-patched"), outputs=dumped)
         line = {"metric": res["metric"], "value": res["value"], "unit": "ray-samples/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
                 "ms_per_step": res["ms_per_step"], "ms_per_step_median": res["ms_per_step_median"], "higher_is_better": True, "scaling": "weak",
                 "vs_baseline": None, "dtype": MODE_DTYPE[a.precision], "data": "synthetic",
@@ -642,6 +691,8 @@ def main():
                            "mode": "train", "path": a.path, "precision": a.precision, "host_syncs_per_step": res["host_syncs_per_step"],
                            "host_waits_for_the_forward_per_step": res["host_waits_for_the_forward_per_step"]},
                 "whole_step_frac_of_mfma_peak": res["value"] * A_TRAIN / 1e12 / MFMA_PEAK_TFLOPS, "last_progress_text": res["last_progress_text"]}
+        if dumped is not None:
+            line["dump_outputs"] = write_outputs(a.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
         return
 
@@ -744,15 +795,21 @@ def main():
     gc.collect()
     gc.disable()
     barrier()
+    last = None
     t0 = time.perf_counter()
     for s_ev, e_ev in evs:
         s_ev.record()
-        step()
+        last = step()
         e_ev.record()
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
     r.check_errors()
+    # the last timed step's results, copied off the device before the profiling loop below runs (and, in train mode, steps) again
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = snapshot_outputs(last, [("udf_network", r.udf_network), ("deviation_network", r.deviation_network),
+                                         ("beta_network", r.beta_network)] if a.mode == "train" else [])
     per_step = sorted(s_ev.elapsed_time(e_ev) for s_ev, e_ev in evs)
     med_ms = per_step[len(per_step) // 2]
     if dist is not None:
@@ -943,6 +1000,8 @@ def main():
                 line["cpu_baseline"] = cpu_baseline(state, kw, a.cpu_rays, a.mode)
             except Exception as e:  # the baseline must never take the GPU line down
                 line["cpu_baseline"] = {"error": repr(e)}
+        if dumped is not None:
+            line["dump_outputs"] = write_outputs(a.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     if trainer is not None:
         trainer.close()                 # a launch that gave up on a peer must fail the bench, not report a number

@@ -45,7 +45,7 @@ def _oracle_render_fn(kw, net, dev, bet, rays, car=1.0, fs=0.9):
     return fn
 
 
-def _oracle_trainer(kw, net, dev, bet, eikonal_sync):
+def _oracle_trainer(kw, net, dev, bet, eikonal_sync, group=None):
     """emap_amd.parallel.Trainer with its two HIP stages replaced by the oracle and the backward mirror."""
     import emap_amd
     from emap_amd.parallel import Trainer
@@ -93,8 +93,8 @@ def _oracle_trainer(kw, net, dev, bet, eikonal_sync):
             for p, val in ((dev.variance, dis * 10 * inv_s), (bet.beta, dbt * 10 * beta), (bet.gamma, dgm * 10 * gamma)):
                 flat_grad[lay.offsets[id(p)]] = float(val)
 
-    return OracleTrainer(r, lr_geo=1e-3, lr=5e-3, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.05, eikonal_sync=eikonal_sync,
-                         fused_adam=False)
+    return OracleTrainer(r, lr_geo=1e-3, lr=5e-3, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.05, group=group,
+                         eikonal_sync=eikonal_sync, fused_adam=False)
 
 
 def _run_step(rank, world, port, n_global, mode, out_q):
@@ -168,7 +168,15 @@ def test_native_and_autograd_steps_agree_and_local_sync_is_close():
     nat = _launch(1, 16, "exact")[0]
     assert nat[1] == pytest.approx(auto[1], rel=2e-5)
     assert np.abs(nat[4] - auto[4]).max() <= 2e-4 * np.abs(auto[4]).max() + 1e-9
-    assert np.abs(nat[3] - auto[3]).max() <= 1e-5
+    # Adam's first step moves every element with |g| >> eps by ~lr, however small |g| is.  An element whose gradient sits at the float32
+    # rounding floor of the sums that produce it (~1e-8 of max |g|) moves by +-lr with whatever sign rounding gave it, and the summation
+    # order of the host's float32 kernels differs from CPU to CPU (one such element came out 2 x lr apart on another host).  So: the
+    # elements on which the two gradients disagree in sign are few and at that floor, and every other parameter agrees to 1e-5.
+    ga, gn = auto[4], nat[4]
+    flipped = np.sign(ga) != np.sign(gn)
+    floor = 1e-7 * np.abs(ga).max()
+    assert flipped.sum() <= 8 and np.all(np.maximum(np.abs(ga), np.abs(gn))[flipped] <= floor), (np.flatnonzero(flipped), ga[flipped], gn[flipped])
+    assert np.abs(nat[3] - auto[3])[~flipped].max() <= 1e-5
     loc = _launch(2, 16, "local")
     assert np.array_equal(loc[0][3], loc[1][3])
     cos = float((loc[0][4] * nat[4]).sum() / (np.linalg.norm(loc[0][4]) * np.linalg.norm(nat[4])))
@@ -192,12 +200,7 @@ def test_shard_and_flat_params_single_process():
 
 
 # ---------------------------------------------------------------------------------------- exact_lagged's per-rank slots at world 8
-def _run_lagged_slots(rank, world, port, out_q):
-    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-    torch.set_num_threads(1)
-    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-    kw, net, dev, bet = _make()
-    tr = _oracle_trainer(kw, net, dev, bet, "exact_lagged")
+def _run_lagged_slots(rank, world, tr, pg):
     assert tr.collectives_per_step == 2 and tr._maxima_tail().numel() == 2 * tr.MAX_RANKS
     n = tr.flat.numel
     # own range maxima of rank r at step s: a smooth history, then a 100x jump on rank 5 (step 3) and a 1000x collapse everywhere (step 4)
@@ -214,16 +217,53 @@ def _run_lagged_slots(rank, world, port, out_q):
         tr.flat.grad.zero_()
         tr._lag_publish(cur, rank)                                  # slots <- own maxima; cur <- the scale this step's sweep would use
         if not tr._lag_valid:                                       # first step: Trainer._collectives() runs the MAX all-reduce instead
-            dist.all_reduce(cur, op=dist.ReduceOp.MAX)
+            dist.all_reduce(cur, op=dist.ReduceOp.MAX, group=pg)
             tr._lag.copy_(cur)
         used.append(cur.clone())
         tr.flat.grad[:n] = float(rank + 1) * (s + 1)                # "the gradients": the bucket's SUM must leave the slots intact
-        dist.all_reduce(tr.flat.grad, op=dist.ReduceOp.SUM)         # ONE collective: gradients + statistics + every rank's two maxima
+        dist.all_reduce(tr.flat.grad, op=dist.ReduceOp.SUM, group=pg)   # ONE collective: gradients + statistics + every rank's two maxima
         sums.append(float(tr.flat.grad[0]))
         tr._lag_collect()
         hist.append(tr._lag.clone())
-    out_q.put((rank, torch.stack(used).numpy(), torch.stack(hist).numpy(), sums))
-    dist.barrier()
+    dist.barrier(group=pg)
+    return rank, torch.stack(used).numpy(), torch.stack(hist).numpy(), sums
+
+
+def _lagged_slots_ranks(world, out_q):
+    """`world` gloo ranks as threads of ONE process (the ranks of a test must stay few processes): each rank its own ProcessGroupGloo
+    over one in-process store, and its own Trainer on that group.  The default group (world 1) only makes torch.distributed report
+    itself initialised, which Trainer's world size needs."""
+    import datetime
+    import threading
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    torch.set_num_threads(1)
+    store = dist.HashStore()
+    dist.init_process_group("gloo", store=dist.PrefixStore("default/", store), rank=0, world_size=1)
+    pgs, res, errs = {}, {}, []
+
+    def on_threads(fn):
+        def guarded(r):
+            try:
+                fn(r)
+            except BaseException as e:          # reported to the parent: a rank that raised fails the test
+                errs.append(f"rank {r}: {e!r}")
+        ths = [threading.Thread(target=guarded, args=(r,), daemon=True) for r in range(world)]
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join(timeout=300)
+        if any(t.is_alive() for t in ths):
+            errs.append("a rank thread did not finish")
+
+    # the groups connect to each other while they are constructed: all at once, one thread per rank
+    on_threads(lambda r: pgs.__setitem__(r, dist.ProcessGroupGloo(dist.PrefixStore("ranks/", store), r, world, datetime.timedelta(seconds=120))))
+    if not errs:
+        trainers = {}
+        for r in range(world):
+            kw, net, dev, bet = _make()
+            trainers[r] = _oracle_trainer(kw, net, dev, bet, "exact_lagged", group=pgs[r])
+        on_threads(lambda r: res.__setitem__(r, _run_lagged_slots(r, world, trainers[r], pgs[r])))
+    out_q.put((errs, [res[r] for r in sorted(res)]))
     dist.destroy_process_group()
 
 
@@ -232,18 +272,17 @@ def test_exact_lagged_rank_slots_with_eight_ranks():
     """the per-rank maxima slots in the gradient bucket's tail (Trainer._lag_publish / _lag_collect, the
     eikonal_sync='exact_lagged' mode) had only ever run with 2 ranks.  8 gloo ranks, 5 steps with a 100x jump on one rank and a 1000x
     collapse on all: every rank derives the same global history from the ONE bucket all-reduce, the scale it uses is
-    clamp(4 x previous global maxima, own, 16 x own), and the gradient part of the bucket is the plain sum."""
+    clamp(4 x previous global maxima, own, 16 x own), and the gradient part of the bucket is the plain sum.  The 8 ranks are threads of
+    one child process (_lagged_slots_ranks)."""
     world = 8
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_run_lagged_slots, args=(r, world, port, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = sorted((q.get(timeout=600) for _ in range(world)), key=lambda r: r[0])
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    p = ctx.Process(target=_lagged_slots_ranks, args=(world, q))
+    p.start()
+    errs, res = q.get(timeout=600)
+    p.join(timeout=120)
+    assert p.exitcode == 0
+    assert not errs and len(res) == world, errs
 
     def own(r, s):
         base = np.array([1.0 + 0.25 * r, 0.5 + 0.125 * ((r * 3) % world)], np.float32) * np.float32(1.0 + 0.1 * s)
