@@ -110,7 +110,7 @@ static VjpPlan plan_vjp(const NetLayout& L, int64_t P, size_t avail = 0) {
     VjpPlan pl;
     build_vjp_layout(L, &pl.V);
     const int cus = device_cus();
-    pl.sweep_grid = (L.H == 256 && VJP_NW_256 == 8) ? cus : 2 * cus;          // 8 waves: one workgroup per CU; 4 waves: two
+    pl.sweep_grid = L.H == 256 ? cus : 2 * cus;          // d_hidden 256: 8 waves, one workgroup per CU; 128: two
     const int64_t tiles = (P + VJP_PT - 1) / VJP_PT;
     pl.chunk_tiles = (int)std::min<int64_t>(std::max<int64_t>(tiles, 1), VJP_CHUNK_TILES);
     const size_t pfl = plan_wgrad(L, pl.V, cus, pl.jobs, &pl.n_jobs, pl.job_h, pl.job_pe, &pl.wgrad_wg);
@@ -208,9 +208,6 @@ static int fused_composite_from_env() {
     return (e && e[0] == '0') ? 0 : 1;
 }
 static std::atomic<int> g_fused_composite{fused_composite_from_env()};
-#ifndef EMAP_FUSED_REDUCE
-#define EMAP_FUSED_REDUCE 1     // the fused tail also runs the cross-ray reduction (CompositeFuse::done_cnt); 0: composite_reduce_kernel as a launch of its own (A/B)
-#endif
 
 static Workspace plan_workspace(const EmapRenderParams& p, const NetLayout* L = nullptr) {
     const size_t N = (size_t)std::max(p.n_rays, 0);
@@ -464,15 +461,15 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
                                  partials, &cf.c);
         if (rc) return rc;
         cf.ray_cnt = ray_cnt;
-        cf.done_cnt = EMAP_FUSED_REDUCE ? ray_cnt + N : nullptr;
+        cf.done_cnt = ray_cnt + N;   // the fused tail also runs the cross-ray reduction
     }
     {
         ProfScope ps(0, st);
         rc = launch_mlp(L, packed, prec, fin, (int64_t)N * S, udf, grad3, st, err_flags, ws + w.rev, fuse_comp ? &cf : nullptr);
     }
     if (rc) return rc;
-    // 3 launches per render: value pass, importance_sample, value + grad_x + compositing + cross-ray reduction (-DEMAP_FUSED_REDUCE=0: the reduction as a fourth)
-    if (fuse_comp) return (cf.done_cnt && cf.c.out.scalars) ? EMAP_OK : launch_composite_reduce(cf.c, err_flags, st);
+    // 3 launches per render: value pass, importance_sample, value + grad_x + compositing + cross-ray reduction
+    if (fuse_comp) return cf.c.out.scalars ? EMAP_OK : launch_composite_reduce(cf.c, err_flags, st);
     return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, p->inv_s, p->beta, p->gamma,
                             p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
                             p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,

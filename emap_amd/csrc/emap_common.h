@@ -87,13 +87,7 @@ constexpr int SWM_UNIT_BYTES = 6656;
 
 // The transposed 32x32 section in the MIXED layout of the MX-fp6 reverse sweep (udf_mlp.hip:pack32_t_body, udf_mlp_rev32.inc):
 // split-fp16 at d_hidden = 256 (a sweep wave owns two row tiles = one 32-value MX block per lane)
-#ifndef EMAP_SWEEP_MX
-#define EMAP_SWEEP_MX 1     // 1: the training sweep's cross terms as MX-fp6 MFMAs (udf_mlp_vjp.inc, round 5); 0: three f16 passes as in rounds 1-4 (A/B builds: all units)
-#endif
-#ifndef EMAP_REV_MX6
-#define EMAP_REV_MX6 1      // 0: f16 cross terms in the backward GEMMs too (A/B builds: compile udf_mlp AND udf_mlp_f16x3 with the flag)
-#endif
-__host__ __device__ inline bool r32_t_mixed(const NetLayout& L) { return EMAP_REV_MX6 && L.mx_bwd && L.is_f16 && L.nparts == 2 && L.H == 256; }
+__host__ __device__ inline bool r32_t_mixed(const NetLayout& L) { return L.mx_bwd && L.is_f16 && L.nparts == 2 && L.H == 256; }
 // The same for the FORWARD sweep of that kernel (udf_mlp.hip:pack32_body writes the mixed layout too): precision mode EMAP_PREC_F16X3M.
 __host__ __device__ inline bool r32_mixed(const NetLayout& L) { return L.mx_fwd && r32_t_mixed(L); }
 // fixed MX scales of the positional-encoding block (|sin|, |cos| <= 1, raw coordinates up to 1.875 exactly): 2^-2 for the hi parts,
@@ -217,10 +211,10 @@ constexpr int VJP_PT = 32;
 #endif
 constexpr int VJP_CHUNK_TILES = EMAP_VJP_CHUNK_TILES;   // tiles per sweep launch of the preferred plan (bounds the stash: 16 384 x ~0.54 MiB = 8.8 GB, one chunk for 4096 rays x 128 samples;
                                                           // 12.85 vs 13.7 ms per training step there with chunks of 2048); a caller with a smaller workspace gets smaller chunks
-#ifndef EMAP_VJP_NW256
-#define EMAP_VJP_NW256 8
-#endif
-constexpr int VJP_NW_256 = EMAP_VJP_NW256;   // waves per workgroup of the sweep at d_hidden = 256: 8 (one workgroup per CU; measured 876-880 us) or 4 (two tile pairs per wave, two workgroups per CU: 939-958 us, 22 % more cycles)
+// 1 KiB planes per hidden layer and tile pair in a sweep workgroup's slab (udf_mlp_vjp.inc, written and read by the kernel, sized by
+// build_vjp_layout): a' (hi part) and sigma' (unorm16) in 4; the f16 sweep of the split-fp16 modes (no MX-fp6 cross terms) adds 2 with the
+// lo parts of a' (SLABLO)
+constexpr __host__ __device__ int vjp_slab_planes(bool split_f16, bool sweep_mx) { return split_f16 && !sweep_mx ? 6 : 4; }
 constexpr int WGRAD_MAX_JOBS = 2 * EMAP_MAX_LIN;
 struct VjpLayout {
     int32_t a_rt[EMAP_MAX_LIN + 1], a_off[EMAP_MAX_LIN + 1];   // row tiles / KiB offset inside a tile's A block

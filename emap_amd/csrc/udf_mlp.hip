@@ -477,7 +477,7 @@ int build_layout(const EmapNetConfig* cfg, int prec, NetLayout* L) {
     if (cfg->multires < 0 || cfg->multires > 10) { set_error("multires must be in 0..10 (got %d)", cfg->multires); return EMAP_E_INVALID; }   // 0: raw coordinates only (udf_model.py:26-29)
     if (cfg->d_out != 1) { set_error("d_out must be 1 (got %d): feature outputs are not on the hot path", cfg->d_out); return EMAP_E_INVALID; }
     if (prec < EMAP_PREC_BF16 || prec > EMAP_PREC_F16X3E) { set_error("unknown precision mode %d", prec); return EMAP_E_INVALID; }
-    if (prec == EMAP_PREC_F16X3M && (cfg->d_hidden != 256 || !EMAP_REV_MX6)) {
+    if (prec == EMAP_PREC_F16X3M && cfg->d_hidden != 256) {
         set_error("precision f16x3m (MX fp6 cross terms in the forward sweep) needs d_hidden = 256 (got %d)", cfg->d_hidden);
         return EMAP_E_INVALID;
     }
@@ -528,7 +528,7 @@ int build_layout(const EmapNetConfig* cfg, int prec, NetLayout* L) {
     // precise weight gradients: hi + lo parts of both operands of dW = sum Z A^T (wgrad.hip: three passes over twice the stash).  The mode without
     // MX fp6 anywhere (f16x3e) is the one that asks for margin; there the sweep is the f16 one, whose lo fragments are f16 as well.
     L->wgrad_lo = (prec == EMAP_PREC_F16X3E && L->is_f16 && L->nparts == 2) ? 1 : 0;
-    L->sweep_mx = (EMAP_SWEEP_MX && L->is_f16 && L->nparts == 2 && H == 256 && prec != EMAP_PREC_F16X3E && L->has_rev) ? 1 : 0;
+    L->sweep_mx = (L->is_f16 && L->nparts == 2 && H == 256 && prec != EMAP_PREC_F16X3E && L->has_rev) ? 1 : 0;
     L->swm_units = 0;
     L->swm_off_bytes = (int32_t)(((size_t)L->r32_t_frag_off_bytes + (size_t)tf * FRAG_BYTES + 255) & ~(size_t)255);
     for (int l = 0; l < cfg->n_lin; ++l) { L->swm_unit[l] = -1; L->swm_t_unit[l] = -1; }
@@ -554,23 +554,18 @@ void build_vjp_layout(const NetLayout& L, VjpLayout* V) {
     }
     V->a_tile_kb = a; V->z_tile_kb = z;
     (void)s;
-    // per workgroup: [hidden layer][tile pair][4 x 64 lanes x 16 B] lane-linear (a' as f16 / bf16 hi part, sigma' as unorm16); the f16 sweep of the
-    // split-fp16 modes adds two planes with the lo parts of a' (udf_mlp_vjp.inc, SLABLO)
-    const bool slablo = !L.sweep_mx && L.is_f16 && L.nparts == 2;
-    V->s_slab_kb = (L.n_lin - 1) * (L.H / 32) * (slablo ? 6 : 4);
+    // per workgroup: [hidden layer][tile pair][planes x 64 lanes x 16 B] lane-linear (vjp_slab_planes)
+    V->s_slab_kb = (L.n_lin - 1) * (L.H / 32) * vjp_slab_planes(L.is_f16 && L.nparts == 2, L.sweep_mx);
 }
 
 __global__ __launch_bounds__(256) void pack_all_kernel(const PackArgs a, unsigned nb0, unsigned nb1, unsigned nb2) {
     const unsigned b = blockIdx.x;
-#ifndef EMAP_PACK_SECTIONS
-#define EMAP_PACK_SECTIONS 63      // timing builds: bit per section (scripts/r5/pack_time.py)
-#endif
-    if (b < nb0) { if (EMAP_PACK_SECTIONS & 1) pack_body(a, b); }
-    else if (b < nb0 + nb1) { if (EMAP_PACK_SECTIONS & 2) pack_t_body(a, b - nb0); }
-    else if (b < 2 * nb0 + nb1) { if (EMAP_PACK_SECTIONS & 4) pack32_body(a, b - nb0 - nb1); }
-    else if (b < 2 * (nb0 + nb1)) { if (EMAP_PACK_SECTIONS & 8) pack32_t_body(a, b - 2 * nb0 - nb1); }
-    else if (b < 2 * (nb0 + nb1) + nb2) { if (EMAP_PACK_SECTIONS & 16) pack_wlast_body(a, b - 2 * (nb0 + nb1)); }
-    else { if (EMAP_PACK_SECTIONS & 32) pack_swm_body(a, b - 2 * (nb0 + nb1) - nb2); }
+    if (b < nb0) pack_body(a, b);
+    else if (b < nb0 + nb1) pack_t_body(a, b - nb0);
+    else if (b < 2 * nb0 + nb1) pack32_body(a, b - nb0 - nb1);
+    else if (b < 2 * (nb0 + nb1)) pack32_t_body(a, b - 2 * nb0 - nb1);
+    else if (b < 2 * (nb0 + nb1) + nb2) pack_wlast_body(a, b - 2 * (nb0 + nb1));
+    else pack_swm_body(a, b - 2 * (nb0 + nb1) - nb2);
 }
 
 int launch_pack(const NetLayout& L, const float* const* g, const float* const* v, const float* const* b,

@@ -44,16 +44,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "sampler_dev.inc"      // per-ray device code of sampler.hip: the fused importance-sampling instantiations (IS) run it between their MLP passes
 #include "composite_dev.inc"    // render_core's tail for one ray: the fused tail of the value + grad_x kernel (udf_mlp_rev32.inc, COMP)
 
-#ifndef EMAP_FS2_ASM_SPLIT
-#define EMAP_FS2_ASM_SPLIT 0     // 1: value passes of the split-fp16 modes split their activations with split_f16_pair (2.5 instead of 5 instructions per value) - measured round 6: step 0.5206 / 0.5211 vs 0.5193 / 0.5175 ms (no gain), not adopted; 0: the RNE cast form
-#endif
 #ifndef EMAP_IS_RING
 #define EMAP_IS_RING 0     // 1: fused importance sampling, 8-wave geometries: K-steps 2, 3 of every pair's next GEMM are fetched into an LDS side ring under the
                            // epilogue (RING below).  Built, bit-identical, measured in round 6 and NOT adopted: render 0.5376 / 0.5391 ms against 0.5332 / 0.5308
                            // without it (profiles/r06_is_side_ring.txt)
-#endif
-#ifndef EMAP_FS2_PINGPONG
-#define EMAP_FS2_PINGPONG 1
 #endif
 #ifndef EMAP_FS2_FUSE_LAST
 #define EMAP_FS2_FUSE_LAST 0   // 1: the output layer's row is applied in the epilogues of the last hidden layer (LASTH in udf_mlp_fs2_kernel) - built, parity-green (248 GPU tests,
@@ -242,19 +236,8 @@ __device__ __forceinline__ void softplus_sig_fast(float z, float& a, float& s) {
     s = __builtin_amdgcn_rcpf(u);
 }
 
-// The same for TWO values in packed fp32 registers (gfx950: v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 process a register pair per issue slot at full
-// rate): the multiply, the add and the fma of softplus_sig_fast - and the lo-accumulator fold of the callers - take one instruction per pair
-// instead of one per value; exp / log / rcp / min / max have no packed form.  Same IEEE operations on the same operands: bit-identical results.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void softplus_sig_fast2(f32x2 z, f32x2& a, f32x2& s) {
-    const f32x2 t = z * (f32x2){-144.26950408889634f, -144.26950408889634f};
-    const f32x2 e = {__builtin_amdgcn_exp2f(fminf(t[0], 126.0f)), __builtin_amdgcn_exp2f(fminf(t[1], 126.0f))};
-    const f32x2 u = e + (f32x2){1.0f, 1.0f};
-    const f32x2 l = {__builtin_amdgcn_logf(u[0]), __builtin_amdgcn_logf(u[1])};
-    const f32x2 q = __builtin_elementwise_fma(l, (f32x2){6.9314718055994531e-3f, 6.9314718055994531e-3f}, z);
-    a = (f32x2){vmax0(q[0]), vmax0(q[1])};
-    s = (f32x2){__builtin_amdgcn_rcpf(u[0]), __builtin_amdgcn_rcpf(u[1])};
-}
+// (round 6: a packed-fp32 form of softplus_sig_fast for the rev32 forward epilogue - 47 fewer instructions per row tile, kernel +2 %,
+// profiles/r06_ab_packed_epilogue.txt - was retired; it is in git history)
 
 // hi / lo split of two fp32 values into packed f16 pairs (split-fp16, lo parts x2^11):
 //   hi = RTZ(x) (v_cvt_pkrtz_f16_f32: both values in one instruction),  lo = RNE((x - hi) * 2^11)
@@ -383,7 +366,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
     // [NKS][NCT][NPART] 1 KiB fragments: the current layer's input.  One workgroup per CU (8 waves, narrow tiles): TWO buffers - a layer reads
     // one and writes the other, a wave stores its outputs as soon as it has them and one barrier per layer remains (as in udf_mlp_vjp.inc);
     // otherwise (two / three workgroups per CU share the LDS) one buffer overwritten by the layer's output between two barriers.
-    constexpr bool PP = (NW == 8) && EMAP_FS2_PINGPONG;
+    constexpr bool PP = (NW == 8);
     char* const xb0 = smem;
     char* const xb1 = smem + (PP ? XB : 0);
     char* pebuf = smem + (PP ? 2 : 1) * XB;       // [PE_KS][NCT][NPART]
@@ -749,24 +732,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                         }
                     } else {
                     if (!last) {
+                        // (round 6: split_f16_pair here, 2.5 instead of 5 instructions per value, brought no gain - step 0.5206 / 0.5211 against
+                        // 0.5193 / 0.5175 ms - and was retired; it is in git history)
                         auto put2 = [&](int ct, int e0, float x0, float x1) __attribute__((always_inline)) {
-                            if constexpr (EMAP_FS2_ASM_SPLIT && SCALED && !GRAD) {
-                                // the value + grad_x kernel's split (v_cvt_pkrtz + v_fma_mix: 2.5 instructions per value instead of 5; hi = RTZ, the lo part
-                                // absorbs the extra bit): the epilogue is VALU-bound - both waves of a SIMD run theirs at the same time (round-6 timeline)
-                                uint32_t hi, lo;
-                                split_f16_pair(x0, x1, hi, lo);
-                                typedef uint32_t u32x4_ __attribute__((ext_vector_type(4)));
-                                u32x4_ vh = __builtin_bit_cast(u32x4_, o[pi][ct][0]), vl = __builtin_bit_cast(u32x4_, o[pi][ct][1]);
-                                vh[e0 >> 1] = hi; vl[e0 >> 1] = lo;
-                                o[pi][ct][0] = __builtin_bit_cast(V8, vh); o[pi][ct][1] = __builtin_bit_cast(V8, vl);
-                            } else {
                             const T h0 = (T)x0, h1 = (T)x1;
                             o[pi][ct][0][e0] = h0;
                             o[pi][ct][0][e0 + 1] = h1;
                             if constexpr (NPART == 2) {
                                 o[pi][ct][1][e0] = (T)((x0 - (float)h0) * LO_SCALE);
                                 o[pi][ct][1][e0 + 1] = (T)((x1 - (float)h1) * LO_SCALE);
-                            }
                             }
                         };
                         static_for<4>([&](auto q_c) __attribute__((always_inline)) {
@@ -904,7 +878,7 @@ static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointS
     a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
     for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
     a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
-    const size_t lds = (size_t)(((NW == 8 && EMAP_FS2_PINGPONG) ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES;   // <= 80 KiB: two workgroups per CU (8 waves: one, two exchange buffers)
+    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES;   // <= 80 KiB: two workgroups per CU (8 waves: one, two exchange buffers)
     static uint64_t attr_mask = 0;   // per device: the LDS-size attribute is a property of (function, device)
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, GRAD, NW>;
     if (attr_needed(attr_mask)) {
@@ -925,13 +899,8 @@ static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointS
 #ifndef EMAP_FS2_T32_MIN
 #define EMAP_FS2_T32_MIN 257
 #endif
-// A/B builds (-DEMAP_COARSE_NW8): 64-point tiles as ONE 8-wave workgroup per CU with two exchange buffers (512 .. 1023 tiles only); measured in
-// round 5 at the coarse pass of the 512-ray render: +15 us against two 4-wave workgroups per CU (217 VGPRs, no spill) - not used
-#ifdef EMAP_COARSE_NW8
-#define EMAP_COARSE_FORM(HH) if constexpr (HH == 256) { if (tiles(64) < 1024) return launch_mlp_fs2_t<HH, MODE, 4, false, 8>(L, packed, src, P, udf, grad3, st, err); }
-#else
-#define EMAP_COARSE_FORM(HH)
-#endif
+// (round 5: 64-point tiles as ONE 8-wave workgroup per CU at 512 .. 1023 tiles measured +15 us at the coarse pass of the 512-ray render against two
+// 4-wave workgroups per CU; that form was retired and is in git history)
 template <int MODE>
 int launch_mlp_val32_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, hipStream_t st, int32_t* err);   // udf_mlp_rev32.inc
 template <int MODE>
@@ -939,24 +908,7 @@ int launch_mlp_fs2_mode(const NetLayout& L, const void* packed, const PointSourc
                         hipStream_t st, int32_t* err) {
     const bool grad = grad3 != nullptr;
     auto tiles = [&](int pts) { return (P + pts - 1) / pts; };
-#ifdef EMAP_FS2_GEOM_ENV      // probe builds only (scripts/r6/gpu_value_geometry_sweep.py): EMAP_FS2_GEOM = 10 NCT + NW forces the geometry of every value launch at d_hidden = 256
-    if (!grad && L.H == 256) {
-        static const int forced = getenv("EMAP_FS2_GEOM") ? atoi(getenv("EMAP_FS2_GEOM")) : 0;
-        switch (forced) {
-            case 18: return launch_mlp_fs2_t<256, MODE, 1, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            case 28: return launch_mlp_fs2_t<256, MODE, 2, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            case 48: return launch_mlp_fs2_t<256, MODE, 4, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            case 38: return launch_mlp_fs2_t<256, MODE, 3, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            case 58: return launch_mlp_fs2_t<256, MODE, 5, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            case 34: return launch_mlp_fs2_t<256, MODE, 3, false, 4>(L, packed, src, P, udf, grad3, st, err);
-            case 14: return launch_mlp_fs2_t<256, MODE, 1, false, 4>(L, packed, src, P, udf, grad3, st, err);
-            case 24: return launch_mlp_fs2_t<256, MODE, 2, false, 4>(L, packed, src, P, udf, grad3, st, err);
-            case 44: return launch_mlp_fs2_t<256, MODE, 4, false, 4>(L, packed, src, P, udf, grad3, st, err);
-            default: break;
-        }
-    }
-#endif
-    // Value launches of the split modes at d_hidden = 256: the geometry by a MEASURED table (round 6, scripts/r6/gpu_value_geometry_sweep.py, every geometry at every size,
+    // Value launches of the split modes at d_hidden = 256: the geometry by a MEASURED table (round 6, every geometry at every size with a probe build since retired,
     // two rounds, profiles/r06_value_geometry.txt; us per launch, rounds 1-5's rule in brackets where it differed).  Every geometry sums in the same K order: the choice
     // never changes a result (tests: test_mlp_all_tile_geometries_agree, test_value_launches_...).
     //   <= 4 096 points   1 x 8 (16-point tiles, one 8-wave workgroup per CU)           28 ... 30
@@ -998,7 +950,7 @@ int launch_mlp_fs2_mode(const NetLayout& L, const void* packed, const PointSourc
 #define EMAP_FS2(HH)                                                                                              \
     if (L.H == HH) {                                                                                              \
         if (grad) return launch_mlp_fs2_t<HH, MODE, 4, true>(L, packed, src, P, udf, grad3, st, err);              \
-        if (tiles(64) >= 512) { EMAP_COARSE_FORM(HH) return launch_mlp_fs2_t<HH, MODE, 4, false>(L, packed, src, P, udf, grad3, st, err); } \
+        if (tiles(64) >= 512) return launch_mlp_fs2_t<HH, MODE, 4, false>(L, packed, src, P, udf, grad3, st, err); \
         if (tiles(32) >= EMAP_FS2_T32_MIN) return launch_mlp_fs2_t<HH, MODE, 2, false>(L, packed, src, P, udf, grad3, st, err); \
         if constexpr (HH == 256) {   /* few points: one 8-wave workgroup per CU halves the weight bytes through each L1 */ \
             if (tiles(32) >= 192) return launch_mlp_fs2_t<HH, MODE, 2, false, 8>(L, packed, src, P, udf, grad3, st, err); \
@@ -1032,7 +984,7 @@ static int launch_is_t(const NetLayout& L, const void* packed, const IsLaunch& q
     a.is_udf_coarse = q.udf_coarse; a.is_z_final = q.z_final; a.is_n_rays = q.N; a.is_sc = q.Sc; a.is_m = q.m; a.is_steps = q.steps;
     a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
     // + the side ring of the 8-wave geometries (RING in the kernel: 8 KiB per wave behind the rays' lists)
-    const size_t lds = (size_t)(((NW == 8 && EMAP_FS2_PINGPONG) ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15) +
+    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15) +
                        ((NW == 8 && NPART == 2 && H == 256 && EMAP_IS_RING) ? (size_t)NW * 2 * 2 * NPART * FRAG_BYTES : 0);
     static uint64_t attr_mask = 0;
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, false, NW, true>;
@@ -1065,12 +1017,6 @@ int launch_is_mode(const NetLayout& L, const void* packed, const IsLaunch& q, hi
     // => fused iff N <= 512.  emap_set_fused_sampling(2) forces the fused kernel, (0) the chain.
     if (L.H == 256 && Prec<MODE>::NPART == 2 && fused_sampling_mode() != 2 && q.N > EMAP_IS_FUSED_MAX_RAYS) return IS_NOT_FUSED;
     if (L.H == 256) {
-#ifdef EMAP_IS_GEOM     // A/B builds: force a workgroup geometry (14 = 1 ray x 4 waves, 24 = 2 x 4, 28 = 2 x 8, 18 = 1 x 8)
-        if (EMAP_IS_GEOM == 14) return launch_is_t<256, MODE, 1, 4>(L, packed, q, st, err);
-        if (EMAP_IS_GEOM == 24) return launch_is_t<256, MODE, 2, 4>(L, packed, q, st, err);
-        if (EMAP_IS_GEOM == 18) return launch_is_t<256, MODE, 1, 8>(L, packed, q, st, err);
-        if (EMAP_IS_GEOM == 28) return launch_is_t<256, MODE, 2, 8>(L, packed, q, st, err);
-#endif
         if (tiles(32) >= EMAP_FS2_T32_MIN) return launch_is_t<256, MODE, 2, 4>(L, packed, q, st, err);
         // one ray per 8-wave workgroup only while that is ONE round (<= 256 rays): rounds 1-5 kept it up to 383 rays - two rounds of 16-column tiles where one round of
         // 32-column tiles does (the value launches' tables above: 5 120 points 52.3 -> 32.8 us per pass in the split modes, 26.4 -> 23.1 in the single-pass ones)

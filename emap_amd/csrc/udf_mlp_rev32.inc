@@ -32,19 +32,8 @@ typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
 
-#ifndef EMAP_PK_EPILOGUE
-#define EMAP_PK_EPILOGUE 0      // 1: packed-fp32 softplus / sigmoid in the forward epilogue (softplus_sig_fast2) - measured round 6: 47 fewer instructions per row tile, +7 % cycles, +3.5 % clock, kernel +2 % (profiles/r06_ab_packed_epilogue.txt); 0: the scalar form
-#endif
 #ifndef EMAP_REV_MX_SAFE
 #define EMAP_REV_MX_SAFE 0  // debug: 1 = every wait of the MX K-loop drains all loads (vmcnt(0)) instead of its counted value
-#endif
-#ifndef EMAP_REV_FUSE_LAST
-#define EMAP_REV_FUSE_LAST 1   // 1: the last hidden layer's epilogue takes the output's K-slice and the first delta_z of the reverse sweep itself (LASTH below); 0: rounds 3-6a (A/B)
-#endif
-#ifndef EMAP_REV_XHEAD
-#define EMAP_REV_XHEAD 0       // 1: MX reverse sweep - the K-loop head of a layer's FIRST row tile is requested at the end of the previous layer (XHEAD below).  Built, bit-identical,
-                               // measured in round 6 and NOT adopted: 325.4 us against 325.5 (4 interleaved rounds, profiles/r06_ab_rev32_xhead.txt) - the other workgroup of the CU already
-                               // fills the ~1.35 k cycles a wave waits for its head; and the linear ISA lint cannot follow loads in flight across a back-edge.  0: in place
 #endif
 #ifndef EMAP_REV_MXS
 #define EMAP_REV_MXS 2      // K64-steps of weight fragments (8 loads each) in flight ahead of the consuming phase in the MX K-loop
@@ -132,7 +121,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
     // terms; the forward sweep keeps f16 cross terms (softplus(beta = 100) amplifies its errors: no margin).  The MX block of a
     // lane = the 32 values it holds of its wave's two row tiles (one K64-step of the next GEMM), scale = power of two from the
     // block's largest magnitude.  Layout of the transposed fragments: udf_mlp.hip:pack32_t_body (r32_t_mixed).
-    constexpr bool MX6 = EMAP_REV_MX6 && BWD6 && MODE == EMAP_PREC_F16X3 && H == 256 && PPW == 2 && NC == 2 && KQ == 2;   // BWD6 = false: precision mode EMAP_PREC_F16X3E
+    constexpr bool MX6 = BWD6 && MODE == EMAP_PREC_F16X3 && H == 256 && PPW == 2 && NC == 2 && KQ == 2;   // BWD6 = false: precision mode EMAP_PREC_F16X3E
     // MX6F: the FORWARD GEMMs likewise (the activations are published exactly as the reverse sweep publishes its deltas: f16 hi parts + the
     // fp6 forms of hi and lo; the weights in the mixed layout of udf_mlp.hip:pack32_body).  Emulation (scripts/probes/mx6_emulation.py,
     // fwd = bwd = "k6:rne"): udf 1.5e-5, grad_x 7.0e-5 of the gate's 1e-4 (3.3e-5 with f16 cross terms in the forward sweep).
@@ -783,7 +772,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
 
         // LASTH applies when the last hidden layer is an ordinary one (hidden input only) and the output layer reads no PE block (wave-uniform)
         bool fuse_last = false;
-        if constexpr (EMAP_REV_FUSE_LAST && !VAL) {
+        if constexpr (!VAL) {
             if (n_hidden >= 1) {
                 const LayerDesc Lh = a.layer[n_hidden - 1];
                 fuse_last = (Lh.h_ks != 0) && !Lh.pe_ks && (a.tpe_off[a.n_lin - 1] < 0);
@@ -836,19 +825,8 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
                         static_for<8>([&](auto rp_c) __attribute__((always_inline)) {
                             constexpr int r = 2 * decltype(rp_c)::value;
                             float a0, s0, a1, s1;
-#if EMAP_PK_EPILOGUE
-                            {   // packed fp32: the lo-accumulator fold and softplus / sigmoid of the register pair (r, r + 1)
-                                f32x2 zz = {acc[c][r], acc[c][r + 1]};
-                                if constexpr (SPLIT && !MX6F)
-                                    zz = __builtin_elementwise_fma((f32x2){accx[c][r], accx[c][r + 1]}, (f32x2){1.0f / LO_SCALE, 1.0f / LO_SCALE}, zz);
-                                f32x2 aa, ss;
-                                softplus_sig_fast2(zz, aa, ss);
-                                a0 = aa[0]; a1 = aa[1]; s0 = ss[0]; s1 = ss[1];
-                            }
-#else
                             softplus_sig_fast(zval(c, r), a0, s0);
                             softplus_sig_fast(zval(c, r + 1), a1, s1);
-#endif
                             put2(pi_c, c_c, std::integral_constant<int, r>{}, a0, a1);
                             if constexpr (SG24) {
                                 // t = round(sigma' * (2^24 - 1)): bytes 2, 1 of the pair -> the unorm16 plane, byte 0 -> the low-byte plane
@@ -928,7 +906,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             }
         };
         for (int l = 0; l < n_loop; ++l) fwd_layer(l, no_t{});
-        if constexpr (EMAP_REV_FUSE_LAST && !VAL) {
+        if constexpr (!VAL) {
             if (fuse_last) fwd_layer(n_hidden - 1, yes_t{});
         }
 
@@ -995,32 +973,19 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             });
             publish_bwd();
         }
-        // XHEAD (round 6, MX reverse sweep): the head of a layer's FIRST row tile - the scale words and the first MXD fragment loads of its K-loop, one L2
-        // round trip, ~1.35 k cycles when it is waited for in place (timeline: K-loop 0 3.9 k cycles against 2.5 k for K-loop 1) - is requested at the END of the
-        // previous layer, behind its last epilogue, and lands under mx_finish and the two barriers of the publishing step.  hipcc keeps an in-flight asm load's
-        // registers in place across a loop's back-edge only while NOTHING else branches between the load and its wait (tried: a wave-uniform flag choosing between
-        // the prefetched and the in-place form of the K-loop, or around the request - register copies of in-flight loads, which the ISA lint rejects, and 150-330
-        // spilled VGPRs; the PE rows of the skip layer moved behind the epilogues to keep the body branch-free - 170-190 spilled VGPRs beside the block vectors).
-        // So the layer body exists twice: form A - PE rows if the layer has them, head in place (what every layer ran before) - for the first layer and for a
-        // layer that reads the PE block; form B - prefetched head, no PE rows - for the runs of ordinary layers behind them.  Both request the next layer's head
-        // at their end, unconditionally; the one request per run that nobody consumes is retired behind the run (it was issued before the publishing step: landed).
-        constexpr bool XH = (EMAP_REV_XHEAD != 0) && MX6;
-        auto xhead = [&](int bn) __attribute__((always_inline)) {
-            const int t0 = a.t_off[bn < 1 ? 1 : bn];
-            mx_head(std::integral_constant<int, NKS / 2>{}, no_t{}, tbase + (size_t)((t0 < 0 ? 0 : t0) + p0 * NKS * NFR) * FRAG_BYTES, nullptr);
-        };
-        auto rev_layer = [&](const int b, auto pre_c) __attribute__((always_inline)) {
-            constexpr bool PRE = decltype(pre_c)::value;
+        // (round 6: an MX form that requested a layer's first K-loop head at the end of the previous layer measured 325.4 against 325.5 us and
+        // was retired; it is in git history - profiles/r06_ab_rev32_xhead.txt)
+        auto rev_layer = [&](const int b) __attribute__((always_inline)) {
             // PE rows of the skip layer: delta_PE += W_b[:, PE]^T delta_z[b], K split across the waves (first: the accumulators are
             // free and no output fragment is waiting to be published)
-            if constexpr (!PRE) { if (a.tpe_off[b] >= 0) pe_rows(a.tpe_off[b]); }
+            if (a.tpe_off[b] >= 0) pe_rows(a.tpe_off[b]);
             static_for<PPW>([&](auto pi_c) __attribute__((always_inline)) {
                 constexpr int pi = decltype(pi_c)::value;
                 const int p = p0 + pi;
                 sg_src = uniform_ptr(slab + (size_t)((b - 1) * NPAIR + p) * SGB);   // sigma' of layer b-1, rows of tile p
                 const char* wb = tbase + (size_t)(a.t_off[b] + p * NKS * NFR) * FRAG_BYTES;
                 if constexpr (MX6) {
-                    k_run6_p(std::integral_constant<int, NKS / 2>{}, std::integral_constant<int, 0>{}, no_t{}, yes_t{}, std::integral_constant<bool, (PRE || pi > 0)>{}, wb, 0, nullptr);
+                    k_run6_p(std::integral_constant<int, NKS / 2>{}, std::integral_constant<int, 0>{}, no_t{}, yes_t{}, std::integral_constant<bool, (pi > 0)>{}, wb, 0, nullptr);
                     if constexpr (pi + 1 < PPW) mx_head(std::integral_constant<int, NKS / 2>{}, no_t{}, wb + (size_t)NKS * NFR * FRAG_BYTES, nullptr);
                 } else {
                     k_run_p(std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{}, no_t{}, yes_t{}, std::integral_constant<bool, (pi > 0)>{},
@@ -1030,22 +995,9 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
                 }
                 bwd_epilogue(pi_c);
             });
-            if constexpr (XH) xhead(b - 1);
             publish_bwd();
         };
-        if constexpr (XH) {
-            int b = a.n_lin - 2;
-            while (b >= 1) {
-                rev_layer(b, no_t{});                                                   // form A
-                --b;
-                for (; b >= 1 && a.tpe_off[b] < 0; --b) rev_layer(b, yes_t{});          // form B: the run of ordinary layers behind it
-                static_assert(!XH || (MXD == 16 && 4 * NKS >= 16), "XHEAD: the unconsumed head is the ring's first 16 loads (MXS = 2)");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(asc), "+v"(arh[0]), "+v"(arh[1]), "+v"(arh[2]), "+v"(arh[3]), "+v"(arh[4 % RH]), "+v"(arh[5 % RH]), "+v"(arh[6 % RH]),
-                             "+v"(arh[7 % RH]), "+v"(arq[0]), "+v"(arq[1]), "+v"(arq[2 % RQ]), "+v"(arq[3 % RQ]), "+v"(ar2[0]), "+v"(ar2[1]), "+v"(ar2[2 % RQ]), "+v"(ar2[3 % RQ]) :: "memory");
-            }
-        } else {
-            for (int b = a.n_lin - 2; b >= 1; --b) rev_layer(b, no_t{});
-        }
+        for (int b = a.n_lin - 2; b >= 1; --b) rev_layer(b);
         // layer 0: only PE rows
         pe_rows(a.tpe_off[0]);
         }   // !VAL

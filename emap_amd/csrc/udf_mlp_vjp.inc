@@ -44,9 +44,6 @@
 // taken from the launch's max|du|, max|dg| (absmax_kernel), so that fp16 neither overflows nor flushes; wgrad_reduce
 // divides by K.
 #pragma once
-#ifndef EMAP_VJP_ROLL
-#define EMAP_VJP_ROLL 1
-#endif
 
 __device__ __forceinline__ void asm_gload4(uint32_t& dst, int voff, const char* sbase) {   // as asm_gload16: 4 B per lane
     asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");
@@ -109,11 +106,14 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     constexpr int NPAIR = H / 32;
     constexpr int NFR = 2 * NPART;
     constexpr int PD = 2;
-    constexpr int PPW = NPAIR / NW;                      // output tile pairs per wave (8 waves: 1, one workgroup per CU; 4 waves: 2, two per CU)
+    // one output tile pair per wave (a 4-wave form at d_hidden = 256 with two pairs per wave and two workgroups per CU measured 939-958 us
+    // against 876-880 us; it was retired and is in git history)
+    constexpr int PPW = NPAIR / NW;
     constexpr int KQ = NKS / NW;                         // K-steps per wave of the K-split last layer
-    static_assert(PPW * NW == NPAIR && KQ * NW == NKS && NW >= 4, "waves per workgroup");
-    constexpr bool SMX = SMX_ && EMAP_SWEEP_MX && MODE == EMAP_PREC_F16X3 && H == 256 && NW == 8;
-    constexpr bool SLABLO = !SMX && MODE == EMAP_PREC_F16X3;      // host side: build_vjp_layout (s_slab_kb)
+    static_assert(PPW == 1 && PPW * NW == NPAIR && KQ * NW == NKS && NW >= 4, "waves per workgroup");
+    constexpr bool SMX = SMX_ && MODE == EMAP_PREC_F16X3 && H == 256;
+    constexpr int NSLAB = vjp_slab_planes(MODE == EMAP_PREC_F16X3, SMX);   // host side: build_vjp_layout (s_slab_kb)
+    constexpr bool SLABLO = NSLAB > 4;
     typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -159,12 +159,11 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     const float Kscale = vjp_scale_from(va.absmax);
 
     clock_stamp(a.clk, 2);
-    // ROLLV (one tile pair per wave): the first PD K-steps of a wave's NEXT GEMM (next layer it owns a pair of, K-split last layer, next reverse
+    // Rolled heads: the first PD K-steps of a wave's NEXT GEMM (next layer it owns a pair of, K-split last layer, next reverse
     // step, next tile's first layer) are requested right after the K-loop of the current one, so the L2 round trip that opened every layer
     // step (both waves of a SIMD waited for it at the same time, ~1 k of 12.8 k cycles) lies under the epilogue, the stash and the barrier.
     // PLAIN loads into `hd`: the values cross branch joins and loop back-edges, where hipcc may copy registers - it may, it knows these
     // loads and waits before it touches them (inline-asm loads in flight there are what scripts/isa_lint.py rejects).
-    constexpr bool ROLLV = (PPW == 1) && (EMAP_VJP_ROLL != 0);
     V8 hd[PD][NFR];
     auto load_head = [&](const char* wb) __attribute__((always_inline)) {
 #pragma unroll
@@ -223,7 +222,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
         }
         else if (tile + (int)gridDim.x < a.n_tiles) head_after_fwd(-1);
     };
-    if constexpr (ROLLV) { if ((int)blockIdx.x < a.n_tiles) head_after_fwd(-1); }
+    if ((int)blockIdx.x < a.n_tiles) head_after_fwd(-1);
     // K-steps of an exchange buffer that no wave writes (the tile pairs a short layer does not have) are read against zero weights:
     // they must hold finite numbers, not whatever the LDS held before the launch
     for (int i = tid * 16; i < (PP ? 2 : 1) * XB; i += NW * 64 * 16) *reinterpret_cast<f32x4*>(smem + i) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -527,7 +526,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
             });
         };
 
-        using roll_t = std::integral_constant<bool, ROLLV>;
         auto k_run = [&](auto ns_c, auto npe_c, auto init_c, const char* wb, int xs0, int pes0, const float* bp) __attribute__((always_inline)) {
             k_run_p(ns_c, npe_c, init_c, std::false_type{}, wb, xs0, pes0, bp);
         };
@@ -604,7 +602,6 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
         // gradients, which the hi + lo weight-gradient passes (NetLayout::wgrad_lo) cannot remove.  The two planes are fetched AFTER the K-loop
         // (plain loads, one exposed L2 round trip per tile pair and layer): 8 more registers live across the K-loop spilled (scratch 80 B -
         // and a spilled register of an asm load in flight is garbage).
-        constexpr int NSLAB = SLABLO ? 6 : 4;
         u32x4 sgv[4];
         auto load_slab = [&](const char* src) __attribute__((always_inline)) {
             const char* sb = uniform_ptr(src);
@@ -630,17 +627,17 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                 const char* wb = wbase + (size_t)(L.frag_off + p * ns * NFR) * FRAG_BYTES;
                 if constexpr (SMX) {
                     const char* wm = va.swm + (size_t)(va.swm_unit[l] + p * (NKS / 4)) * SWM_UNIT_BYTES;
-                    if (kind == KIND_NORMAL) k_run_mx(std::integral_constant<int, 1>{}, std::integral_constant<int, NKS / 4>{}, roll_t{}, 0, wb, wm, bp);
+                    if (kind == KIND_NORMAL) k_run_mx(std::integral_constant<int, 1>{}, std::integral_constant<int, NKS / 4>{}, yes_t{}, 0, wb, wm, bp);
                     else if (kind == KIND_SKIP) {   // PE K-steps in three f16 passes (bias seed), then the hidden K-steps continue on the same accumulators
-                        k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, roll_t{}, wb, 0, 0, bp);
+                        k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, yes_t{}, wb, 0, 0, bp);
                         k_run_mx(std::integral_constant<int, 2>{}, std::integral_constant<int, NKS / 4>{}, no_t{}, 0, wb + (size_t)PE_KS * NFR * FRAG_BYTES, wm, bp);
-                    } else k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, roll_t{}, wb, 0, 0, bp);
+                    } else k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, yes_t{}, wb, 0, 0, bp);
                 } else {
-                if (kind == KIND_NORMAL) k_run_p(std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{}, yes_t{}, roll_t{}, wb, 0, 0, bp);
-                else if (kind == KIND_SKIP) k_run_p(std::integral_constant<int, PE_KS + NKS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, roll_t{}, wb, 0, 0, bp);
-                else k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, roll_t{}, wb, 0, 0, bp);
+                if (kind == KIND_NORMAL) k_run_p(std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{}, yes_t{}, yes_t{}, wb, 0, 0, bp);
+                else if (kind == KIND_SKIP) k_run_p(std::integral_constant<int, PE_KS + NKS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, yes_t{}, wb, 0, 0, bp);
+                else k_run_p(std::integral_constant<int, PE_KS>{}, std::integral_constant<int, PE_KS>{}, yes_t{}, yes_t{}, wb, 0, 0, bp);
                 }
-                if constexpr (ROLLV) head_after_fwd(l);
+                head_after_fwd(l);
                 uint32_t bk[SLABLO ? 24 : 16];     // [q][0] = (a'0, a'1) as T pair, [q][1] = (sigma'0, sigma'1) as unorm16 pair; SLABLO: [16 + q] = the lo parts of (a'0, a'1)
                 static_for<8>([&](auto q_c) __attribute__((always_inline)) {
                     constexpr int q = decltype(q_c)::value, t = q >> 2, r = q & 3;
@@ -692,7 +689,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     for (int ct = 0; ct < NCT; ++ct) hpart[ct] = zval(0, ct, 0);
                 }
             } else {
-            k_run_p(std::integral_constant<int, KQ>{}, std::integral_constant<int, 0>{}, no_t{}, roll_t{}, wb, KQ * wave, 0, nullptr);
+            k_run_p(std::integral_constant<int, KQ>{}, std::integral_constant<int, 0>{}, no_t{}, yes_t{}, wb, KQ * wave, 0, nullptr);
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) hpart[ct] = zval(0, ct, 0);
             }
@@ -702,7 +699,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) hpart[ct] += zval(0, ct, 0);
             }
-            if constexpr (ROLLV) head_after_bwd(a.n_lin - 1, tile);
+            head_after_bwd(a.n_lin - 1, tile);
             if constexpr (!PP) __syncthreads();   // every wave has finished reading the exchange buffer: its head becomes `red`
             if (g == 0) {
 #pragma unroll
@@ -794,9 +791,9 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     }
                 } else {
                     const char* wb = tbase + (size_t)(a.t_off[b] + p * NKS * NFR) * FRAG_BYTES;
-                    if constexpr (SMX) k_run_mx(std::integral_constant<int, 0>{}, std::integral_constant<int, NKS / 4>{}, roll_t{}, 0, wb,
+                    if constexpr (SMX) k_run_mx(std::integral_constant<int, 0>{}, std::integral_constant<int, NKS / 4>{}, yes_t{}, 0, wb,
                                                 va.swm + (size_t)(va.swm_t_unit[b] + p * (NKS / 4)) * SWM_UNIT_BYTES, nullptr);
-                    else k_run_p(std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{}, no_t{}, roll_t{}, wb, 0, 0, nullptr);
+                    else k_run_p(std::integral_constant<int, NKS>{}, std::integral_constant<int, 0>{}, no_t{}, yes_t{}, wb, 0, 0, nullptr);
                 }
                 wait_slab();
                 u32x4 aplo[2];
@@ -807,7 +804,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     asm_gload16_sc1<1024>(aplo[1], wvoff, lp);
                     asm volatile("s_waitcnt vmcnt(0)" : "+v"(aplo[0]), "+v"(aplo[1]) : : "memory");
                 }
-                if constexpr (ROLLV) { if (b != a.n_lin - 1) head_after_bwd(b, tile); }   // behind the slab's vmcnt(0): the request must not be waited for here
+                if (b != a.n_lin - 1) head_after_bwd(b, tile);   // behind the slab's vmcnt(0): the request must not be waited for here
                 static_for<8>([&](auto q_c) __attribute__((always_inline)) {
                     constexpr int q = decltype(q_c)::value, t = q >> 2, r = q & 3;
                     typedef T T2 __attribute__((ext_vector_type(2)));
@@ -889,10 +886,10 @@ template <int MODE>
 int launch_vjp_sweep_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, int tile0, int n_tiles,
                           const float* d_udf, const float* d_grad, const VjpLayout& V, char* stash_a, char* stash_z,
                           char* stash_s, int grid, const uint32_t* absmax, float* ldot, hipStream_t st, int32_t* err) {
-    if constexpr (MODE == EMAP_PREC_F16X3 && VJP_NW_256 == 8 && EMAP_SWEEP_MX) {
-        if (L.H == 256 && L.sweep_mx) return launch_vjp_sweep_t<256, MODE, VJP_NW_256, true>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
+    if constexpr (MODE == EMAP_PREC_F16X3) {
+        if (L.H == 256 && L.sweep_mx) return launch_vjp_sweep_t<256, MODE, 8, true>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
     }
-    if (L.H == 256) return launch_vjp_sweep_t<256, MODE, VJP_NW_256>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
+    if (L.H == 256) return launch_vjp_sweep_t<256, MODE, 8>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
     if (L.H == 128) return launch_vjp_sweep_t<128, MODE, 4>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
     set_error("no training-backward kernel for d_hidden=%d", L.H);
     return EMAP_E_INVALID;
