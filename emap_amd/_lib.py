@@ -23,7 +23,12 @@ PREC_F16X3E = 5    # f16x3 with f16 cross terms in both sweeps of the value+grad
 PRECISIONS = {"bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "f16x3": PREC_F16X3, "f16x3m": PREC_F16X3M, "f16x3e": PREC_F16X3E}
 UDF_TYPES = {"abs": 0, "square": 1, "sdf": 2}
 MAX_LIN = 12
-ABI_VERSION = 10
+ABI_VERSION = 11
+
+# EmapRenderParams.render_mode (ABI 11): use_unbias_render / use_norm_grad_for_cosine of the reference renderer
+RENDER_UNBIASED = 0
+RENDER_UNBIASED_NORMCOS = 1
+RENDER_PLAIN = 2
 
 F_NAN_SAMPLES = 1
 F_NAN_GRADERR = 2
@@ -47,7 +52,7 @@ class RenderParams(C.Structure):
                 ("cos_anneal_ratio", C.c_float), ("has_cos_anneal", C.c_int32), ("flip_saturation", C.c_float),
                 ("near_surface", C.c_float), ("sparse_scale", C.c_float), ("background", C.c_float),
                 ("has_background", C.c_int32), ("variance_dev", C.c_void_p), ("beta_dev", C.c_void_p),
-                ("gamma_dev", C.c_void_p), ("beta_min", C.c_float), ("reserved", C.c_int32)]
+                ("gamma_dev", C.c_void_p), ("beta_min", C.c_float), ("render_mode", C.c_int32)]
 
 
 class CompositeGrads(C.Structure):
@@ -93,6 +98,7 @@ SYMBOLS = {
     "emap_sample_pdf_u": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_upsample_step": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
                                      _P, _P, _P, _P]),
+    "emap_upsample_step_plain": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
     "emap_merge_sorted": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_composite_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,

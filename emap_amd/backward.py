@@ -206,6 +206,10 @@ class RenderFn(torch.autograd.Function):
                                "in-place edit in between): the gradient would be taken at other weights than the forward used")
         lay = r._layout()
         need = [p.requires_grad for p in lay.tensors]
+        if r.render_mode == _lib.RENDER_PLAIN and lay.extra:
+            # use_unbias_render=False: inv_s does not enter alpha (reference :551-559), so autograd never reaches `variance` there and its
+            # .grad stays None - not a zero gradient, on either path below (the kernels write 0 into its slot of the flat buffer)
+            need[next(i for i, q in enumerate(lay.tensors) if q is lay.extra[0])] = False
         ctx.v = None
         if getattr(r, "direct_param_grads", False) and all(p.grad is None for p, nd in zip(lay.tensors, need) if nd):
             # Fast path of the drop-in training step (dropin.patch_runner(train=True)): the kernels write into ONE persistent flat buffer

@@ -49,12 +49,13 @@ struct ProfScope {   // records a HIP event pair around one launch on its stream
 int launch_sample_pdf(const float*, const float*, int, int, int, float*, int64_t*, int32_t*, hipStream_t, const float* u = nullptr);
 int launch_upsample(const float*, const float*, const float*, const float*, int, int, int, const float*, float, float,
                     float, float*, int64_t*, int32_t*, hipStream_t);
+int launch_upsample_plain(const float*, const float*, int, int, int, const float*, float, float, float*, int64_t*, int32_t*, hipStream_t);
 int launch_merge(const float*, const float*, const float*, const float*, int, int, int, float*, float*, int64_t*,
                  hipStream_t);
 int launch_coarse(const float*, const float*, const float*, int, int, float*, float*, hipStream_t);
 int launch_composite(const float*, const float*, const float*, const float*, const float*, const float*, int, int,
                      const float*, float, float, float, float, int, float, float, float, float, int, const float*,
-                     const float*, const float*, float, const EmapCompositeOut*, float*, int32_t*, hipStream_t);
+                     const float*, const float*, float, const EmapCompositeOut*, float*, int32_t*, hipStream_t, int mode = EMAP_RENDER_UNBIASED);
 int fill_composite_args(const float*, const float*, const float*, const float*, const float*, const float*, int, int,
                         const float*, float, float, float, float, int, float, float, float, float, int, const float*,
                         const float*, const float*, float, const EmapCompositeOut*, float*, CompositeArgs*);
@@ -197,6 +198,14 @@ static int check_param_grads(const NetLayout& L, const EmapParamGrads* o, const 
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// EmapRenderParams.render_mode (ABI 11; the field was `reserved`, always 0, before)
+static int check_render_mode(const EmapRenderParams* p, const char* what) {
+    const int m = p->render_mode;
+    if (m == EMAP_RENDER_UNBIASED || m == EMAP_RENDER_UNBIASED_NORMCOS || m == EMAP_RENDER_PLAIN) return EMAP_OK;
+    set_error("%s: render_mode %d is not one of EMAP_RENDER_UNBIASED (0), EMAP_RENDER_UNBIASED_NORMCOS (1), EMAP_RENDER_PLAIN (2)", what, m);
+    return EMAP_E_INVALID;
+}
+
 struct Workspace {
     size_t sample_dist, z_a, z_b, udf_a, udf_b, z_new, z_new2, udf_new, partials, ray_cnt, rev, total;
 };
@@ -325,6 +334,14 @@ int emap_upsample_step(const float* rays_o, const float* rays_d, const float* z,
                            static_cast<hipStream_t>(stream));
 }
 
+int emap_upsample_step_plain(const float* rays_o, const float* rays_d, const float* z, const float* udf, int N, int n, int m,
+                             const float* sample_dist_dev, float beta, float gamma, float* z_new, int64_t* inds, int32_t* err_flags,
+                             void* stream) {
+    (void)rays_o; (void)rays_d;      // up_sample_no_occ_aware's sphere test is unused in the reference (:937-941)
+    if (N > 0 && (!z || !udf || !sample_dist_dev || !z_new)) { set_error("upsample_step_plain: null pointer"); return EMAP_E_INVALID; }
+    return launch_upsample_plain(z, udf, N, n, m, sample_dist_dev, beta, gamma, z_new, inds, err_flags, static_cast<hipStream_t>(stream));
+}
+
 int emap_merge_sorted(const float* z, const float* z_new, const float* udf, const float* udf_new, int N, int n, int m,
                       float* z_out, float* udf_out, int64_t* perm, void* stream) {
     if (N > 0 && (!z || !z_new || !z_out)) { set_error("merge_sorted: null pointer"); return EMAP_E_INVALID; }
@@ -347,10 +364,12 @@ int emap_composite_fwd_p(const float* rays_o, const float* rays_d, const float* 
                          const float* depth_scale, int N, int S, const float* sample_dist_dev, const EmapRenderParams* p,
                          const EmapCompositeOut* out, float* partials, int32_t* err_flags, void* stream) {
     if (!p || (N > 0 && (!rays_o || !rays_d || !z || !udf || !grad3 || !sample_dist_dev))) { set_error("composite_fwd_p: null pointer"); return EMAP_E_INVALID; }
+    const int rc = check_render_mode(p, "composite_fwd_p");
+    if (rc) return rc;
     return launch_composite(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, p->inv_s, p->beta, p->gamma,
                             p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
                             p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,
-                            partials, err_flags, static_cast<hipStream_t>(stream));
+                            partials, err_flags, static_cast<hipStream_t>(stream), p->render_mode);
 }
 
 int emap_render_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRenderParams* p, size_t* bytes) {
@@ -358,6 +377,7 @@ int emap_render_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRe
     const int rc = build_layout(cfg, prec, &L);
     if (rc) return rc;
     if (!p || !bytes) { set_error("render_workspace_bytes: null pointer"); return EMAP_E_INVALID; }
+    if (check_render_mode(p, "render_workspace_bytes")) return EMAP_E_INVALID;
     *bytes = plan_workspace(*p, &L).total;
     return EMAP_OK;
 }
@@ -373,6 +393,9 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
         set_error("render_fwd: null pointer");
         return EMAP_E_INVALID;
     }
+    rc = check_render_mode(p, "render_fwd");
+    if (rc) return rc;
+    const bool plain = p->render_mode == EMAP_RENDER_PLAIN;
     const int N = p->n_rays, Sc = p->n_samples, K = p->up_sample_steps;
     if (N <= 0) return EMAP_OK;
     if (Sc < 2 || p->n_importance < 0 || (p->n_importance > 0 && K < 1)) { set_error("render_fwd: bad sampling configuration"); return EMAP_E_INVALID; }
@@ -393,8 +416,9 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     // render_core's tail inside the final value + grad_x launch (ABI 9) where that launch is the reverse-sweep kernel: the first launch of
     // the render clears the per-ray arrival counters, the final one composites every ray as its last tile completes
     int32_t* ray_cnt = reinterpret_cast<int32_t*>(ws + w.ray_cnt);
-    const bool fuse_comp = g_fused_composite.load(std::memory_order_relaxed) && mlp_uses_rev(L, prec, (int64_t)N * S) &&
-                           comp_list_entries((int64_t)N * S, S) <= COMP_LIST_MAX;
+    // (the fused tail composites in the default render mode only: the other two run the separate compositing and reduction launches)
+    const bool fuse_comp = p->render_mode == EMAP_RENDER_UNBIASED && g_fused_composite.load(std::memory_order_relaxed) &&
+                           mlp_uses_rev(L, prec, (int64_t)N * S) && comp_list_entries((int64_t)N * S, S) <= COMP_LIST_MAX;
 
     if (steps == 0) {
         // no up-sampling: the coarse samples (render() :700-720) are the final z_vals
@@ -414,12 +438,16 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
         if (rc) return rc;
         src.coarse = 0; src.zero_cnt = nullptr; src.zero_n = 0;
         // everything from here to the final z_vals in ONE launch where the shape allows (16 new samples per ray and step, below 2048 rays):
-        // sampler steps and MLP passes alternate inside the workgroup that owns the rays (udf_mlp_kernel.inc, IS)
-        IsLaunch q;
-        q.rays_o = rays_o; q.rays_d = rays_d; q.near = near; q.far = far; q.t_rand = t_rand; q.sample_dist = sample_dist;
-        q.udf_coarse = ubuf[0]; q.z_final = z_vals; q.N = N; q.Sc = Sc; q.m = m; q.steps = steps;
-        rc = launch_importance(L, packed, prec, q, st, err_flags);
-        if (rc < 0) return rc;
+        // sampler steps and MLP passes alternate inside the workgroup that owns the rays (udf_mlp_kernel.inc, IS).  The fused kernel
+        // up-samples with up_sample_unbias only: EMAP_RENDER_PLAIN always takes the chain below
+        rc = IS_NOT_FUSED;
+        if (!plain) {
+            IsLaunch q;
+            q.rays_o = rays_o; q.rays_d = rays_d; q.near = near; q.far = far; q.t_rand = t_rand; q.sample_dist = sample_dist;
+            q.udf_coarse = ubuf[0]; q.z_final = z_vals; q.N = N; q.Sc = Sc; q.m = m; q.steps = steps;
+            rc = launch_importance(L, packed, prec, q, st, err_flags);
+            if (rc < 0) return rc;
+        }
         int cur = 0, n = Sc;
         for (int i = 0; rc == IS_NOT_FUSED && i < steps; ++i) {
             const bool last = (i + 1 == steps);
@@ -439,7 +467,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
                 cur ^= 1;
                 n += m;
             }
-            int rc2 = launch_sampler_step(i == 0, last, a, st);
+            int rc2 = launch_sampler_step(i == 0, last, a, st, plain);
             if (rc2) return rc2;
             if (!last) {
                 src.z = znew[i & 1]; src.n_per_ray = m;
@@ -473,7 +501,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, p->inv_s, p->beta, p->gamma,
                             p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
                             p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,
-                            partials, err_flags, st);
+                            partials, err_flags, st, p->render_mode);
 }
 
 int emap_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
@@ -483,6 +511,7 @@ int emap_composite_bwd(const float* rays_o, const float* rays_d, const float* z,
         set_error("composite_bwd: null pointer");
         return EMAP_E_INVALID;
     }
+    if (check_render_mode(p, "composite_bwd")) return EMAP_E_INVALID;
     return launch_composite_bwd(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, p, g, d_udf, d_grad3, partials,
                                 nullptr, static_cast<hipStream_t>(stream));
 }
@@ -533,6 +562,7 @@ int emap_render_bwd_workspace_bytes(const EmapNetConfig* cfg, int prec, const Em
     const int rc = build_layout(cfg, prec, &L);
     if (rc) return rc;
     if (!p || !bytes) { set_error("render_bwd_workspace_bytes: null pointer"); return EMAP_E_INVALID; }
+    if (check_render_mode(p, "render_bwd_workspace_bytes")) return EMAP_E_INVALID;
     size_t a, b, c;
     const size_t extra = render_bwd_extra(*p, &a, &b, &c);
     const int m = p->up_sample_steps > 0 ? p->n_importance / p->up_sample_steps : 0;
@@ -546,6 +576,7 @@ int emap_render_bwd_absmax_offset(const EmapNetConfig* cfg, int prec, const Emap
     const int rc = build_layout(cfg, prec, &L);
     if (rc) return rc;
     if (!p || !offset) { set_error("render_bwd_absmax_offset: null pointer"); return EMAP_E_INVALID; }
+    if (check_render_mode(p, "render_bwd_absmax_offset")) return EMAP_E_INVALID;
     size_t a, b, c;
     const size_t extra = render_bwd_extra(*p, &a, &b, &c);
     const int m = p->up_sample_steps > 0 ? p->n_importance / p->up_sample_steps : 0;
@@ -573,6 +604,8 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
         set_error("render_bwd: null pointer");
         return EMAP_E_INVALID;
     }
+    rc = check_render_mode(p, "render_bwd");
+    if (rc) return rc;
     rc = check_param_grads(L, out, "render_bwd");
     if (rc) return rc;
     const int N = p->n_rays;

@@ -175,7 +175,7 @@ struct StepArgs {
     float inv_s, beta, gamma;
     int32_t* err;
 };
-int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st);
+int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain = false);   // plain: up_sample_no_occ_aware
 
 // scratch: device buffer of at least rev_scratch_bytes(L) for the reverse-mode grad kernel (required when that kernel is
 // selected; mlp_uses_rev() tells)

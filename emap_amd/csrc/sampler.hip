@@ -57,6 +57,21 @@ __global__ __launch_bounds__(64) void upsample_kernel(const float* rays_o, const
                   inds ? inds + (size_t)ray * m : nullptr, err);
 }
 
+// up_sample_no_occ_aware (:920-975) of one step on its own: the step-level counterpart of upsample_kernel (use_unbias_render=False)
+__global__ __launch_bounds__(64) void upsample_plain_kernel(const float* z, const float* udf, int N, int n, int m, const float* sample_dist,
+                                                            float beta, float gamma, float* z_new, int64_t* inds, int32_t* err) {
+    __shared__ float s_z[MAXS], s_u[MAXS];
+    __shared__ UpsampleScratch w;
+    const int ray = blockIdx.x, lane = threadIdx.x;
+    const float sd = *sample_dist;
+    for (int e = lane; e < n; e += 64) {
+        s_z[e] = z[(size_t)ray * n + e];
+        s_u[e] = udf[(size_t)ray * n + e];
+    }
+    __syncthreads();
+    upsample_plain_body(sd, s_z, s_u, w, n, m, beta, gamma, lane, z_new + (size_t)ray * m, inds ? inds + (size_t)ray * m : nullptr, err);
+}
+
 // ---------------------------------------------------------------------------------------------
 // cat_z_vals: merge two sorted lists (stable: old samples first on ties), gather udf
 // (udf_renderer_blending.py:361-375)
@@ -84,11 +99,12 @@ __global__ __launch_bounds__(64) void merge_kernel(const float* z, const float* 
 //   [COARSE: the coarse z_vals of render() :705-720 computed in place (and sample_dist, :704)]
 //   [MERGE : cat_z_vals of the PREVIOUS step (:355-377): merge z/udf with the previous step's new samples]
 //   up_sample_unbias of this step (:228-353) on the merged lists, which never leave LDS
+//     [PLAIN : up_sample_no_occ_aware (:920-975) instead - use_unbias_render=False, :807-810]
 //   [TAIL  : cat_z_vals(last=True) of this step: the final z_vals]
-// The kernels the C ABI exposes one by one (emap_upsample_step, emap_merge_sorted) share the bodies.
+// The kernels the C ABI exposes one by one (emap_upsample_step[_plain], emap_merge_sorted) share the bodies.
 // ---------------------------------------------------------------------------------------------
 
-template <bool COARSE, bool MERGE, bool TAIL>
+template <bool COARSE, bool MERGE, bool TAIL, bool PLAIN = false>
 __global__ __launch_bounds__(64) void sampler_step_kernel(const StepArgs a) {
     __shared__ float s_z[MAXS], s_u[MAXS], s_n[MAXS];
     __shared__ UpsampleScratch w;
@@ -145,7 +161,8 @@ __global__ __launch_bounds__(64) void sampler_step_kernel(const StepArgs a) {
         }
     }
     __syncthreads();
-    upsample_body(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, a.inv_s, a.beta, a.gamma, lane, s_n, nullptr, a.err);
+    if constexpr (PLAIN) upsample_plain_body(sd, s_z, s_u, w, n, m, a.beta, a.gamma, lane, s_n, nullptr, a.err);
+    else upsample_body(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, a.inv_s, a.beta, a.gamma, lane, s_n, nullptr, a.err);
     __syncthreads();
     for (int e = lane; e < m; e += 64) a.z_new[(size_t)ray * m + e] = s_n[e];
     if constexpr (TAIL) {
@@ -185,12 +202,13 @@ __global__ __launch_bounds__(256) void coarse_z_kernel(const float* near, const 
 // ---------------------------------------------------------------------------------------------
 // render_core tail (udf_renderer_blending.py:435-455,463-677)
 // ---------------------------------------------------------------------------------------------
-#include "composite_dev.inc"     // CompositeArgs + composite_ray<C, COH>: the per-ray body, shared with udf_mlp_rev32.inc's fused tail
+#include "composite_dev.inc"     // CompositeArgs + composite_ray<C, COH> / composite_ray_mode<C, MODE>: the per-ray body, shared with udf_mlp_rev32.inc's fused tail
 
 
-template <int C>
+template <int C, int MODE = EMAP_RENDER_UNBIASED>
 __global__ __launch_bounds__(64) void composite_kernel(const CompositeArgs a) {
-    composite_ray<C, false>(a, blockIdx.x, threadIdx.x);
+    if constexpr (MODE == EMAP_RENDER_UNBIASED) composite_ray<C, false>(a, blockIdx.x, threadIdx.x);
+    else composite_ray_mode<C, MODE>(a, blockIdx.x, threadIdx.x);
 }
 
 // deterministic cross-ray reduction of the eikonal terms (:618-625) and sparse_error (:642-644)
@@ -284,7 +302,11 @@ __device__ __forceinline__ void sdf2alpha_bwd(const Sdf2AlphaKeep& k, float tabs
     d_tabs = (gn - gp) * inv_s * dists * 0.5f * dic;
 }
 
-template <int C>
+// MODE: composite_ray's render mode.  EMAP_RENDER_PLAIN: alpha = alpha_occ (:551-559), so the adjoint of alpha goes straight to raw ->
+// udf, beta, gamma; no inv_s gradient, grad_x udf only through the eikonal terms.  EMAP_RENDER_UNBIASED_NORMCOS: true_cos = d . g / (|g| + eps)
+// (:480), d true_cos / d g = d / (|g| + eps) - (d . g) g / (|g| (|g| + eps)^2) (checked against the reference's
+// autograd gradients, tests/golden/g17_normcos_*: tests/test_gpu_render_modes.py).
+template <int C, int MODE = EMAP_RENDER_UNBIASED>
 __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArgs a) {
     const int ray = blockIdx.x, lane = threadIdx.x, S = a.S;
     const size_t rb = (size_t)ray * S;
@@ -314,10 +336,19 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
     const float c_ns = a.d_ge_ns ? a.d_ge_ns[0] / (a.scalars[6] + 1e-5f) : 0.f;
     const bool anneal = a.anneal != 0;
 
+    float gi[C];                               // normalised cosine: |g| + 1e-5 (composite_ray's expression)
+    if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
 #pragma unroll
-    for (int i = 0; i < C; ++i) tc[i] = FADD(FADD(FMUL(dx, gx[i]), FMUL(dy, gy[i])), FMUL(dz, gz[i]));
+        for (int i = 0; i < C; ++i) {
+            gi[i] = FADD(sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
+            tc[i] = FADD(FADD(FMUL(dx, FDIV(gx[i], gi[i])), FMUL(dy, FDIV(gy[i], gi[i]))), FMUL(dz, FDIV(gz[i], gi[i])));
+        }
+    } else if constexpr (MODE == EMAP_RENDER_UNBIASED) {
+#pragma unroll
+        for (int i = 0; i < C; ++i) tc[i] = FADD(FADD(FMUL(dx, gx[i]), FMUL(dy, gy[i])), FMUL(dz, gz[i]));
+    }
     z[C] = dpp_next_f(0.f, z[0]);       // sample e+1 of a lane's last sample is the next lane's first
-    tc[C] = dpp_next_f(0.f, tc[0]);
+    if constexpr (MODE != EMAP_RENDER_PLAIN) tc[C] = dpp_next_f(0.f, tc[0]);
     float dists[C], E[C], opE[C], raw[C], eq[C], ain[C], av[C], vpr[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) {
@@ -326,21 +357,27 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
         opE[i] = FADD(1.0f, E[i]);
         raw[i] = FDIV(FMUL(beta_, E[i]), FMUL(opE[i], opE[i]));
         eq[i] = expf(FMUL(FMUL(-relu_(raw[i]), gamma_), dists[i]));            // 1 - alpha_occ up to rounding
-        const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);
-        const float occ = FSUB(1.0f, eq[i]);
-        ain[i] = FADD(FSUB(1.0f, occ), FMUL(a.flip_sat, vis_mask));
-        av[i] = FADD(clipf(ain[i], 0.0f, 1.0f), 1e-7f);
+        if constexpr (MODE != EMAP_RENDER_PLAIN) {
+            const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);
+            const float occ = FSUB(1.0f, eq[i]);
+            ain[i] = FADD(FSUB(1.0f, occ), FMUL(a.flip_sat, vis_mask));
+            av[i] = FADD(clipf(ain[i], 0.0f, 1.0f), 1e-7f);
+        }
     }
-    ray_prefix_prod<C>(av, ok, vpr);           // raw (unclipped) visibility product
+    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_prefix_prod<C>(av, ok, vpr);           // raw (unclipped) visibility product
     Sdf2AlphaKeep kp[C], km[C];
     float ap[C], am[C], vp[C], alpha[C], om[C], T[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        vp[i] = clipf(vpr[i], 0.0f, 1.0f);
-        const float tcn = -fabsf(tc[i]);
-        ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, a.car, kp[i]);
-        am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, a.car, km[i]);
-        alpha[i] = FADD(FMUL(ap[i], vp[i]), FMUL(am[i], FSUB(1.0f, vp[i])));
+        if constexpr (MODE == EMAP_RENDER_PLAIN) {
+            alpha[i] = FSUB(1.0f, eq[i]);                       // composite_ray's alpha, bit for bit
+        } else {
+            vp[i] = clipf(vpr[i], 0.0f, 1.0f);
+            const float tcn = -fabsf(tc[i]);
+            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, a.car, kp[i]);
+            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, a.car, km[i]);
+            alpha[i] = FADD(FMUL(ap[i], vp[i]), FMUL(am[i], FSUB(1.0f, vp[i])));
+        }
         om[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
     }
     ray_prefix_prod<C>(om, ok, T);             // transmittance
@@ -355,17 +392,24 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         dal[i] = dal[i] * T[i] - suf[i] * __builtin_amdgcn_rcpf(om[i]);
-        const float dvp = (vpr[i] >= 0.f && vpr[i] <= 1.f) ? dal[i] * (ap[i] - am[i]) : 0.f;
-        x[i] = dvp * vpr[i];
+        if constexpr (MODE != EMAP_RENDER_PLAIN) {
+            const float dvp = (vpr[i] >= 0.f && vpr[i] <= 1.f) ? dal[i] * (ap[i] - am[i]) : 0.f;
+            x[i] = dvp * vpr[i];
+        }
     }
-    ray_suffix_sum<C>(x, ok, suf, lane);
+    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_suffix_sum<C>(x, ok, suf, lane);
     double p_is = 0.0, p_beta = 0.0, p_gamma = 0.0;
     float mx_u = 0.f, mx_g = 0.f;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        // occlusion branch: a_i = clip(1 - occ + fs*vm) + 1e-7
-        const float da = suf[i] * __builtin_amdgcn_rcpf(av[i]);
-        const float docc = (ain[i] >= 0.f && ain[i] <= 1.f) ? -da : 0.f;
+        // occlusion branch: a_i = clip(1 - occ + fs*vm) + 1e-7; plain: alpha = occ itself
+        float docc;
+        if constexpr (MODE == EMAP_RENDER_PLAIN) {
+            docc = dal[i];
+        } else {
+            const float da = suf[i] * __builtin_amdgcn_rcpf(av[i]);
+            docc = (ain[i] >= 0.f && ain[i] <= 1.f) ? -da : 0.f;
+        }
         const float dq = docc * eq[i];
         const float r1 = __builtin_amdgcn_rcpf(opE[i]), r2 = r1 * r1;
         const float draw = (raw[i] > 0.f) ? dq * gamma_ * dists[i] : 0.f;
@@ -373,24 +417,36 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
         float du = draw * (-beta_ * beta_ * E[i] * fE);
         const float pb = draw * (E[i] * r2 - beta_ * u[i] * E[i] * fE), pg = dq * relu_(raw[i]) * dists[i];
         // alpha branch
-        const float tabs = fabsf(tc[i]);
-        float s1, t1, i1, s2, t2, i2;
-        sdf2alpha_bwd(kp[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * vp[i], s1, t1, i1);
-        sdf2alpha_bwd(km[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
-        du += s1 - s2;
-        const float dtc = (t1 + t2) * ((tc[i] > 0.f) ? 1.f : ((tc[i] < 0.f) ? -1.f : 0.f));
+        float dtc = 0.f, d_is = 0.f;
+        if constexpr (MODE != EMAP_RENDER_PLAIN) {
+            const float tabs = fabsf(tc[i]);
+            float s1, t1, i1, s2, t2, i2;
+            sdf2alpha_bwd(kp[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * vp[i], s1, t1, i1);
+            sdf2alpha_bwd(km[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
+            du += s1 - s2;
+            d_is = i1 + i2;
+            dtc = (t1 + t2) * ((tc[i] > 0.f) ? 1.f : ((tc[i] < 0.f) ? -1.f : 0.f));
+        }
         // eikonal terms (:612-625), masks detached
         const float px = FADD(ox, FMUL(dx, mid[i])), py = FADD(oy, FMUL(dy, mid[i])), pz = FADD(oz, FMUL(dz, mid[i]));
         const float pn = sqrtf(FADD(FADD(FMUL(px, px), FMUL(py, py)), FMUL(pz, pz)));
         const float gm = sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i])));
         const float relax = (pn < 2.4f) ? 1.0f : 0.0f, ns = (u[i] < a.near_surface) ? 1.0f : 0.0f;
         const float coef = (gm > 0.f) ? (c_ge * relax + c_ns * ns) * 2.0f * (gm - 1.0f) * __builtin_amdgcn_rcpf(gm) : 0.f;
-        const float ogx = dtc * dx + coef * gx[i], ogy = dtc * dy + coef * gy[i], ogz = dtc * dz + coef * gz[i];
+        float ogx = dtc * dx + coef * gx[i], ogy = dtc * dy + coef * gy[i], ogz = dtc * dz + coef * gz[i];
+        if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
+            // true_cos = d . g / (|g| + eps): its gradient in g is d / (|g| + eps) - (d . g) g / (|g| (|g| + eps)^2)
+            const float rgi = __builtin_amdgcn_rcpf(gi[i]);
+            const float k2 = (gm > 0.f) ? (dx * gx[i] + dy * gy[i] + dz * gz[i]) * rgi * rgi * __builtin_amdgcn_rcpf(gm) : 0.f;
+            ogx = dtc * (dx * rgi - k2 * gx[i]) + coef * gx[i];
+            ogy = dtc * (dy * rgi - k2 * gy[i]) + coef * gy[i];
+            ogz = dtc * (dz * rgi - k2 * gz[i]) + coef * gz[i];
+        }
         if (ok[i]) {
             const size_t q = rb + lane * C + i;
             a.d_udf[q] = du;
             a.d_grad[3 * q] = ogx; a.d_grad[3 * q + 1] = ogy; a.d_grad[3 * q + 2] = ogz;
-            p_is += (double)(i1 + i2); p_beta += (double)pb; p_gamma += (double)pg;
+            p_is += (double)d_is; p_beta += (double)pb; p_gamma += (double)pg;
             const float au = fabsf(du), ag = fmaxf(fmaxf(fabsf(ogx), fabsf(ogy)), fabsf(ogz));
             mx_u = (au < 3.0e38f) ? fmaxf(mx_u, au) : mx_u;
             mx_g = (ag < 3.0e38f) ? fmaxf(mx_g, ag) : mx_g;
@@ -501,6 +557,14 @@ int launch_upsample(const float* rays_o, const float* rays_d, const float* z, co
     return check_launch("upsample_step");
 }
 
+int launch_upsample_plain(const float* z, const float* udf, int N, int n, int m, const float* sample_dist, float beta, float gamma, float* z_new,
+                          int64_t* inds, int32_t* err, hipStream_t st) {
+    if (n < 2 || n > MAXS || m < 1 || m > MAXS) { set_error("upsample_step_plain: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
+    if (N <= 0) return EMAP_OK;
+    hipLaunchKernelGGL(upsample_plain_kernel, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
+    return check_launch("upsample_step_plain");
+}
+
 int launch_merge(const float* z, const float* z_new, const float* udf, const float* udf_new, int N, int n, int m,
                  float* z_out, float* udf_out, int64_t* perm, hipStream_t st) {
     if (n < 1 || n > MAXS || m < 1 || m > MAXS) { set_error("merge_sorted: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
@@ -510,11 +574,19 @@ int launch_merge(const float* z, const float* z_new, const float* udf, const flo
     return check_launch("merge_sorted");
 }
 
-int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st) {
+int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain) {
     const int n_out = a.n + (coarse ? 0 : a.m);
     if (a.n < 2 || n_out + a.m > MAXS || a.m < 1) { set_error("sampler_step: n=%d m=%d out of range (max %d)", a.n, a.m, MAXS); return EMAP_E_INVALID; }
     if (a.N <= 0) return EMAP_OK;
-    if (coarse) {
+    if (plain) {            // use_unbias_render=False: up_sample_no_occ_aware in every step
+        if (coarse) {
+            if (tail) hipLaunchKernelGGL((sampler_step_kernel<true, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL((sampler_step_kernel<true, false, false, true>), dim3(a.N), dim3(64), 0, st, a);
+        } else {
+            if (tail) hipLaunchKernelGGL((sampler_step_kernel<false, true, true, true>), dim3(a.N), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL((sampler_step_kernel<false, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
+        }
+    } else if (coarse) {
         if (tail) hipLaunchKernelGGL((sampler_step_kernel<true, false, true>), dim3(a.N), dim3(64), 0, st, a);
         else hipLaunchKernelGGL((sampler_step_kernel<true, false, false>), dim3(a.N), dim3(64), 0, st, a);
     } else {
@@ -560,13 +632,21 @@ int launch_composite(const float* rays_o, const float* rays_d, const float* z, c
                      const float* depth_scale, int N, int S, const float* sample_dist, float inv_s, float beta,
                      float gamma, float car, int anneal, float flip_sat, float near_surface, float sparse_scale,
                      float background, int has_bg, const float* var_p, const float* beta_p, const float* gamma_p,
-                     float beta_min, const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st) {
+                     float beta_min, const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st, int mode) {
     CompositeArgs a;
     const int rc = fill_composite_args(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, inv_s, beta, gamma, car, anneal, flip_sat,
                                        near_surface, sparse_scale, background, has_bg, var_p, beta_p, gamma_p, beta_min, out, partials, &a);
     if (rc) return rc;
     if (N <= 0) return EMAP_OK;
-    if (S <= 64) hipLaunchKernelGGL(composite_kernel<1>, dim3(N), dim3(64), 0, st, a);
+    if (mode == EMAP_RENDER_PLAIN) {
+        if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+    } else if (mode == EMAP_RENDER_UNBIASED_NORMCOS) {
+        if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+    } else if (S <= 64) hipLaunchKernelGGL(composite_kernel<1>, dim3(N), dim3(64), 0, st, a);
     else if (S <= 128) hipLaunchKernelGGL(composite_kernel<2>, dim3(N), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(composite_kernel<4>, dim3(N), dim3(64), 0, st, a);
     if (out->scalars) hipLaunchKernelGGL(composite_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, out->scalars, err, a);
@@ -591,7 +671,15 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
     a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail;
     a.raymax = absmax ? partials + (size_t)N * 4 : nullptr;     // internal callers (emap_render_bwd) size `partials` as (N,4) + (N,2)
     if ((a.d_ge || a.d_ge_ns) && !a.scalars) { set_error("composite_bwd: the eikonal gradients need the forward's scalars"); return EMAP_E_INVALID; }
-    if (S <= 64) hipLaunchKernelGGL(composite_bwd_kernel<1>, dim3(N), dim3(64), 0, st, a);
+    if (p->render_mode == EMAP_RENDER_PLAIN) {
+        if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+    } else if (p->render_mode == EMAP_RENDER_UNBIASED_NORMCOS) {
+        if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+    } else if (S <= 64) hipLaunchKernelGGL(composite_bwd_kernel<1>, dim3(N), dim3(64), 0, st, a);
     else if (S <= 128) hipLaunchKernelGGL(composite_bwd_kernel<2>, dim3(N), dim3(64), 0, st, a);
     else hipLaunchKernelGGL(composite_bwd_kernel<4>, dim3(N), dim3(64), 0, st, a);
     hipLaunchKernelGGL(composite_bwd_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, a, gr->d_variance, gr->d_beta,

@@ -288,6 +288,53 @@ __device__ __forceinline__ void upsample_body(float ox, float oy, float oz, floa
     else upsample_body_c<4>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
 }
 
+// ---------------------------------------------------------------------------------------------
+// up_sample_no_occ_aware (udf_renderer_blending.py:920-975) -> z_new (N,m): use_unbias_render=False
+// ---------------------------------------------------------------------------------------------
+// upsample_body_c's register layout and scan chunks without the occlusion terms: the weights of sample_pdf are the n - 1 interval
+// opacities alpha_occ = 1 - exp(-relu(udf2logistic(udf, beta)) gamma dists) themselves (:954-963) - no visibility product, no cosine,
+// no mid-point udf, no transmittance; inv_s and the sphere test of the reference are unused there.
+template <int C>
+__device__ __forceinline__ void upsample_plain_body_c(float sd, const float* s_z, const float* s_u, UpsampleScratch& w, int n, int m,
+                                                      float beta, float gamma, int lane, float* samples_out, int64_t* inds_out,
+                                                      int32_t* err) {
+    float z[C + 1], u[C], av[C], sb[C];
+    bool oki[C];                   // interval [e, e+1] exists
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        const int e = lane * C + i;
+        oki[i] = e < n - 1;
+        const int ec = (e < n) ? e : n - 1;
+        z[i] = s_z[ec]; u[i] = s_u[ec];
+    }
+    z[C] = dpp_next_f(0.f, z[0]);          // sample e+1 of a lane's last sample is the next lane's first
+    double part = 0.0;
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        const float dists = oki[i] ? FSUB(z[i + 1], z[i]) : sd;                             // :946-955
+        const float raw_occ = udf2logistic1(u[i], beta);                                    // :960
+        const float alpha_occ = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma), dists)));  // :962-964
+        av[i] = FADD(alpha_occ, 1e-5f);                                                     // sample_pdf :73 on alpha_occ[:, :-1]
+        if (oki[i]) part += (double)av[i];
+    }
+    const float total = (float)wave_sum_d(part);
+#pragma unroll
+    for (int i = 0; i < C; ++i) av[i] = FDIV(av[i], total);
+    ray_prefix_sum<C>(av, oki, sb);
+#pragma unroll
+    for (int i = 0; i < C; ++i) if (oki[i]) w.d[lane * C + i + 1] = sb[i];
+    if (lane == 0) w.d[0] = 0.0f;
+    sample_pdf_search(s_z, w.d, n, m, lane, samples_out, inds_out, err, nullptr);
+}
+
+template <int = 0>
+__device__ __forceinline__ void upsample_plain_body(float sd, const float* s_z, const float* s_u, UpsampleScratch& w, int n, int m,
+                                                    float beta, float gamma, int lane, float* samples_out, int64_t* inds_out, int32_t* err) {
+    if (n <= 64) upsample_plain_body_c<1>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+    else if (n <= 128) upsample_plain_body_c<2>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+    else upsample_plain_body_c<4>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+}
+
 // stable rank-merge of the sorted LDS lists s_z[n] (old) and s_n[m] (new): element e of cat([old, new]) goes to rank(e)
 __device__ __forceinline__ int merge_rank(const float* s_z, const float* s_n, int n, int m, int e, float& v) {
     if (e < n) {

@@ -266,10 +266,14 @@ class Trainer:
                              flat=flat_grad, scalars=scalars_glob)
 
     def _scalar_flags(self):
+        """Which of variance / beta / gamma the step updates: those with requires_grad, except `variance` under use_unbias_render=False,
+        which the plain render does not reach (reference :551-559; torch.optim.Adam leaves a parameter without gradient untouched)."""
         for p in self.geo:
             if not p.requires_grad:
                 raise NotImplementedError("Trainer: a UDF network parameter with requires_grad=False is not supported")
-        return tuple(bool(p.requires_grad) for p in self.scalars)
+        from . import _lib
+        plain = self.r.render_mode == _lib.RENDER_PLAIN
+        return tuple(bool(p.requires_grad) and not (plain and i == 0) for i, p in enumerate(self.scalars))
 
     def check_errors(self):
         """Host-side health check (synchronises): the renderer's device error word and - ``allreduce="oneshot"`` - the collective's
@@ -469,7 +473,7 @@ class Trainer:
                 stats = g[self.flat.numel:self.flat.numel + 5].clone()
         # torch.optim.Adam on the two flat parameters cannot skip single elements: a frozen scalar (requires_grad = False,
         # runner_udf.py:144-154) is put back and its moments cleared (CPU tests only; the native path masks inside the kernel)
-        frozen = [i for p in self.scalars if not p.requires_grad
+        frozen = [i for p, f in zip(self.scalars, self._scalar_flags()) if not f
                   for i in range(self.flat.offsets[id(p)] - self.flat.offsets[id(self.scalars[0])], self.flat.offsets[id(p)] - self.flat.offsets[id(self.scalars[0])] + p.numel())]
         keep = self.p_sc.data[frozen].clone() if frozen else None
         self.optimizer.step()

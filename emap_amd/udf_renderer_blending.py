@@ -5,9 +5,11 @@ current stream in ONE C call with no host synchronisation.  With trainable param
 the same forward runs inside ``emap_amd.backward.RenderFn`` and ``loss.backward()`` is ONE more C call
 (``emap_render_bwd``: composite_bwd + the MLP double-backward kernels); there is no PyTorch fallback.
 
-Supported configuration = what every EMAP conf selects (SURVEY.md par. 2 #5-#7):
-``sdf2alpha_type="numerical"``, ``upsampling_type="classical"``, ``use_unbias_render=True``,
-``use_norm_grad_for_cosine=False``, ``n_outside=0``.  Anything else raises at construction.
+Supported configuration: ``sdf2alpha_type="numerical"``, ``upsampling_type="classical"``, ``n_outside=0`` (what every EMAP
+conf selects, SURVEY.md par. 2 #5-#7), with ``use_unbias_render`` True (every shipped conf) or False (the plain, non-occlusion-aware
+rendering: up_sample_no_occ_aware and alpha = alpha_occ, reference :551-559,920-975) and ``use_norm_grad_for_cosine`` True or False
+(true_cos from the normalised gradient, :479-480; the reference ignores it when use_unbias_render=False).  Anything else raises at
+construction.
 """
 from __future__ import annotations
 
@@ -93,9 +95,8 @@ class UDFRendererBlending:
                  device="cuda", precision=None):
         if n_outside != 0 or nerf is not None:
             raise NotImplementedError("n_outside>0 / background NeRF is dead code in the reference (SURVEY par. 2 #7)")
-        if sdf2alpha_type != "numerical" or upsampling_type != "classical" or not use_unbias_render or use_norm_grad_for_cosine:
-            raise NotImplementedError("only sdf2alpha_type='numerical', upsampling_type='classical', "
-                                      "use_unbias_render=True, use_norm_grad_for_cosine=False are on the hot path")
+        if sdf2alpha_type != "numerical" or upsampling_type != "classical":
+            raise NotImplementedError("only sdf2alpha_type='numerical', upsampling_type='classical' are on the hot path")
         self.nerf = nerf
         self.udf_network = udf_network
         self.deviation_network = deviation_network
@@ -132,6 +133,14 @@ class UDFRendererBlending:
         m = self.n_importance // self.up_sample_steps if self.n_importance > 0 else 0
         return self.n_samples + m * (self.up_sample_steps if m > 0 else 0)
 
+    @property
+    def render_mode(self):
+        """EmapRenderParams.render_mode of this renderer's two options (use_norm_grad_for_cosine acts only together with
+        use_unbias_render=True, reference :479-482)."""
+        if not self.use_unbias_render:
+            return _lib.RENDER_PLAIN
+        return _lib.RENDER_UNBIASED_NORMCOS if self.use_norm_grad_for_cosine else _lib.RENDER_UNBIASED
+
     def _params(self, N, cos_anneal_ratio, flip_saturation, background_rgb):
         p = _lib.RenderParams()
         p.n_rays, p.n_samples, p.n_importance, p.up_sample_steps = N, self.n_samples, self.n_importance, self.up_sample_steps
@@ -152,6 +161,7 @@ class UDFRendererBlending:
         p.beta_dev = self.beta_network.beta.data_ptr()
         p.gamma_dev = self.beta_network.gamma.data_ptr()
         p.beta_min = float(self.beta_network.beta_min)
+        p.render_mode = self.render_mode
         return p
 
     def error_flags(self) -> int:

@@ -27,13 +27,18 @@
 extern "C" {
 #endif
 
-#define EMAP_ABI_VERSION 10
+#define EMAP_ABI_VERSION 11
 
 /* error codes */
 #define EMAP_OK 0
 #define EMAP_E_INVALID (-1)     /* bad argument / unsupported configuration */
 #define EMAP_E_LAUNCH (-2)      /* HIP launch error                          */
 #define EMAP_E_WORKSPACE (-3)   /* workspace too small                       */
+
+/* EmapRenderParams.render_mode (ABI v11): the reference's use_unbias_render / use_norm_grad_for_cosine (udf_renderer_blending.py:479-559,807-810) */
+#define EMAP_RENDER_UNBIASED 0          /* use_unbias_render=True, use_norm_grad_for_cosine=False (every shipped conf)               */
+#define EMAP_RENDER_UNBIASED_NORMCOS 1  /* use_unbias_render=True, use_norm_grad_for_cosine=True: true_cos from g / (|g| + 1e-5)      */
+#define EMAP_RENDER_PLAIN 2             /* use_unbias_render=False: up_sample_no_occ_aware, alpha = 1 - exp(-relu(raw) gamma dists)   */
 
 /* err_flags bits */
 #define EMAP_F_NAN_SAMPLES 1    /* sample_pdf produced NaN   (udf_renderer_blending.py:102)  */
@@ -108,6 +113,9 @@ int emap_embed(const float* x, int64_t P, int multires, float* pe, void* stream)
  *                      bins (N,n), weights (N,n-1) -> samples (N,m), inds int64 (N,m) (may be NULL)
  * emap_upsample_step : up_sample_unbias                        (udf_renderer_blending.py:228-353)
  *                      z,udf (N,n) -> z_new (N,m), inds (N,m) (may be NULL)
+ * emap_upsample_step_plain : up_sample_no_occ_aware            (udf_renderer_blending.py:920-975; ABI v11)
+ *                      the same shapes; the step of use_unbias_render=False.  Its inv_s and rays are unused in the reference
+ *                      (no cosine, no sphere test): inv_s is not an argument, rays_o / rays_d are accepted and may be NULL
  * emap_merge_sorted  : the cat + sort + gather of cat_z_vals   (udf_renderer_blending.py:361-375)
  *                      z (N,n), z_new (N,m) [, udf (N,n), udf_new (N,m)] -> z_out, udf_out (N,n+m),
  *                      perm int64 (N,n+m) (may be NULL); udf/udf_new/udf_out may be NULL (last=True) */
@@ -120,6 +128,9 @@ int emap_sample_pdf_u(const float* bins, const float* weights, const float* u, i
 int emap_upsample_step(const float* rays_o, const float* rays_d, const float* z, const float* udf, int N, int n,
                        int m, const float* sample_dist_dev, float inv_s, float beta, float gamma, float* z_new,
                        int64_t* inds, int32_t* err_flags, void* stream);
+int emap_upsample_step_plain(const float* rays_o, const float* rays_d, const float* z, const float* udf, int N, int n,
+                             int m, const float* sample_dist_dev, float beta, float gamma, float* z_new, int64_t* inds,
+                             int32_t* err_flags, void* stream);
 int emap_merge_sorted(const float* z, const float* z_new, const float* udf, const float* udf_new, int N, int n,
                       int m, float* z_out, float* udf_out, int64_t* perm, void* stream);
 
@@ -157,7 +168,8 @@ int emap_composite_fwd(const float* rays_o, const float* rays_d, const float* z,
 
 /* ---- fused forward render ------------------------------------------------------------------
  * UDFRendererBlending.render (udf_renderer_blending.py:679-800) for upsampling_type="classical",
- * use_unbias_render=True, n_outside=0: coarse z_vals (:705-720) -> importance_sample (:802-841) ->
+ * sdf2alpha_type="numerical", n_outside=0, in the render mode of EmapRenderParams.render_mode (use_unbias_render True or
+ * False, use_norm_grad_for_cosine True or False): coarse z_vals (:705-720) -> importance_sample (:802-841) ->
  * render_core (:418-677).  near/far are (N) device arrays; t_rand (N) may be NULL (no jitter).
  * The whole sequence is enqueued on `stream` with no host synchronisation.
  * z_vals (N,S), udf (N,S), grad3 (N,S,3) are outputs as well (S = n_samples + n_importance//steps*steps). */
@@ -183,7 +195,12 @@ typedef struct EmapRenderParams {
     const float* beta_dev;
     const float* gamma_dev;
     float beta_min;
-    int32_t reserved;
+    /* ABI v11 (was `reserved`, 0): EMAP_RENDER_*.  Honoured by emap_render_fwd, emap_composite_fwd_p, emap_composite_bwd,
+     * emap_render_bwd[_staged] and the workspace-size calls; any other value is EMAP_E_INVALID.  emap_composite_fwd (no params
+     * struct) is EMAP_RENDER_UNBIASED only.  Only EMAP_RENDER_UNBIASED runs render_core's tail inside the final value + grad_x launch
+     * (emap_set_fused_composite); EMAP_RENDER_PLAIN always up-samples through the chain of 2 K - 1 launches (emap_set_fused_sampling
+     * does not apply to it). */
+    int32_t render_mode;
 } EmapRenderParams;
 
 /* same, with inv_s/beta/gamma taken from raw device parameters (see EmapRenderParams) */
