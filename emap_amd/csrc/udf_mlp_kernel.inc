@@ -44,17 +44,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #include "sampler_dev.inc"      // per-ray device code of sampler.hip: the fused importance-sampling instantiations (IS) run it between their MLP passes
 #include "composite_dev.inc"    // render_core's tail for one ray: the fused tail of the value + grad_x kernel (udf_mlp_rev32.inc, COMP)
 
-#ifndef EMAP_IS_RING
-#define EMAP_IS_RING 0     // 1: fused importance sampling, 8-wave geometries: K-steps 2, 3 of every pair's next GEMM are fetched into an LDS side ring under the
-                           // epilogue (RING below).  Built, bit-identical, measured in round 6 and NOT adopted: render 0.5376 / 0.5391 ms against 0.5332 / 0.5308
-                           // without it (profiles/r06_is_side_ring.txt)
-#endif
-#ifndef EMAP_FS2_FUSE_LAST
-#define EMAP_FS2_FUSE_LAST 0   // 1: the output layer's row is applied in the epilogues of the last hidden layer (LASTH in udf_mlp_fs2_kernel) - built, parity-green (248 GPU tests,
-                               // geometry-independent bits), measured in round 6 and NOT adopted: value passes 35.8 / 98.8 us against 35.8 / 98.4 at 8 192 / 32 768 points, render
-                               // 0.5447 against 0.5463 ms (profiles/r06_ab_fs2_lasth.txt) - the K-loop it removes ran on one wave beside seven idle ones for ~2 k cycles of a
-                               // 65 k-cycle pass, and the wait for w exposes the rolled prologue's L2 round trip instead; 0: the output layer as a ninth GEMM (rounds 2-6)
-#endif
 #ifndef EMAP_ROLL_NCT
 #define EMAP_ROLL_NCT 2
 #endif
@@ -348,16 +337,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
     // NEXT pair's first PD K-steps and bias before the current pair's epilogue and the layer barriers; the wide tiles have no
     // registers for it
     constexpr bool ROLL = (NCT <= EMAP_ROLL_MAX_NCT) && !GRAD;
-    // RING (round 6, an experiment kept behind EMAP_IS_RING; the 8-wave fused importance-sampling geometries): the timeline of the narrow pass
-    // (profiles/r06_fs2_timeline.txt) shows only the rolled prologue (K-steps 0, 1 of the next GEMM) in flight under the epilogue, the output stores
-    // and the barrier, and there are no registers for more.  With RING, K-steps 2 and 3 of the next GEMM are requested at the same point by LDS-DMA
-    // into a per-wave 8 KiB ring in the LDS the kernel leaves free; the K-loop reads them back with ds_read_b128 and issues its register loads two
-    // K-steps earlier.  Bit-identical - and slower: the K-loop of a layer loses 400 cycles (4850 -> 4446), the epilogue gains 690 and the barrier wait
-    // 340 (profiles/r06_is_side_ring.txt).  What a K-step costs is not the latency of its fragments but their 32 KiB per CU through the 64 B/clk
-    // vector-memory path (K-steps whose fragments are already resident take the same ~600 cycles), and a wave that issues vector-memory
-    // instructions under its epilogue does not run its epilogue meanwhile.
-    constexpr bool RING = IS && (NW == 8) && ROLL && (PD == 2) && (NPART == 2) && (H == 256) && (EMAP_IS_RING != 0);
-    constexpr int RING_BYTES = 2 * NFR * FRAG_BYTES;      // K-steps 2, 3 of one pair: 8 KiB per wave
+    // (round 6: an LDS side ring for K-steps 2, 3 of the next GEMM in the 8-wave fused importance-sampling geometries - bit-identical and slower,
+    // profiles/r06_is_side_ring.txt - was retired; it is in git history)
     static_assert(!GRAD || NCT == 4, "fs2 grad kernel uses the 4-column-tile layout");
     static_assert(PPW >= 1 && PPW * NW == NPAIR, "H/32 must be a multiple of the waves per workgroup");
 
@@ -382,43 +363,14 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
 
     V8 afr[PD + 1][NFR];           // weight fragments in flight (ROLL: the ring persists from pair to pair)
     f32x4 br0 = {0.f, 0.f, 0.f, 0.f}, br1 = {0.f, 0.f, 0.f, 0.f};
-    // LASTH (round 6): the output layer has ONE real row w.  Rounds 2-6a ran it as a ninth GEMM: the last hidden layer's activations published through
-    // the exchange buffer (two barriers), then a K-loop over all K-steps on wave 0 alone - seven waves idle for most of a hidden layer's K-loop time.
-    // Now every wave applies w to the outputs it holds at the end of the last hidden layer's epilogue (fp32 FMAs on the fp32 activations, not a GEMM on
-    // their split-f16 parts): per pair of 32 features a partial sum per column (8 registers per lane, then the four lane groups), left in LDS (the PE
-    // block's area: no layer reads it any more) and added up pair by pair by wave 0 behind ONE barrier.  The order of the additions - registers of a pair,
-    // lane groups, pairs 0 .. n-1, bias - does not depend on the tile geometry: every geometry, the fused sampler and the launch chain give the same bits.
-    // Condition (wave-uniform): the last hidden layer is an ordinary one and the output layer reads no PE block.
-    constexpr bool FUSE = (EMAP_FS2_FUSE_LAST != 0) && !RING;
-    bool fuse_last = false;
-    if constexpr (FUSE) {
-        if (a.n_lin >= 2) {
-            const LayerDesc Lh = a.layer[a.n_lin - 2], Lo = a.layer[a.n_lin - 1];
-            fuse_last = (Lh.h_ks != 0) && !Lh.pe_ks && !Lo.pe_ks;
-        }
-    }
-    const int n_layers = a.n_lin - (fuse_last ? 1 : 0);
+    // (round 6: the output layer's row applied in the last hidden layer's epilogues, LASTH - time-neutral, profiles/r06_ab_fs2_lasth.txt - was
+    // retired; it is in git history.  The output layer runs as one more GEMM on wave 0.)
     auto pairs_of = [&](int ln) __attribute__((always_inline)) -> int {
-        return (ln == a.n_lin - 1) ? ((wave == 0 && !fuse_last) ? 1 : 0) : min(max(a.layer[ln].n_pairs - wave * PPW, 0), PPW);
+        return (ln == a.n_lin - 1) ? (wave == 0 ? 1 : 0) : min(max(a.layer[ln].n_pairs - wave * PPW, 0), PPW);
     };
-    // (RING) this wave's side ring: behind the exchange buffers, the PE block and the rays' lists
-    const unsigned ring_lds = (unsigned)(size_t)smem + (unsigned)(((PP ? 2 : 1) * NKS + PE_KS) * NCT * NPART * FRAG_BYTES) +
-                              (unsigned)((NCT * sizeof(IsRay) + 15) & ~(size_t)15) + (unsigned)wave * RING_BYTES;
-    const char* const ring_rd = smem + (ring_lds - (unsigned)(size_t)smem) + lane * 16;
     auto issue_prologue = [&](int ln, int pn) __attribute__((always_inline)) {
         const LayerDesc Ln = a.layer[ln];
         const char* wbn = wbase + (size_t)(Ln.frag_off + pn * (Ln.pe_ks + Ln.h_ks) * NFR) * FRAG_BYTES;
-        if constexpr (RING) {
-            // K-steps 2, 3 of the pair (a GEMM with hidden K-steps has >= 8): requested BEFORE the register prologue - everything issued here has
-            // landed when the next K-loop starts (it drains the queue at its first step), and the prologue's registers are needed first
-            if (Ln.h_ks > 0) {
-                const unsigned rl = __builtin_amdgcn_readfirstlane(ring_lds);
-                static_for<2 * NFR>([&](auto i_c) __attribute__((always_inline)) {
-                    constexpr int i = decltype(i_c)::value;
-                    asm_dma16<0>(rl + i * FRAG_BYTES, wvoff, wbn + (2 * NFR + i) * FRAG_BYTES);      // no immediate offset: it would move the LDS address too
-                });
-            }
-        }
 #pragma unroll
         for (int sp = 0; sp < PD; ++sp)
 #pragma unroll
@@ -548,10 +500,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
         __syncthreads();
         FTL(true, 17);
 
-        for (int l = 0; l < n_layers; ++l) {
+        for (int l = 0; l < a.n_lin; ++l) {
             const LayerDesc L = a.layer[l];
             const bool last = (l == a.n_lin - 1);
-            const bool lasth = fuse_last && (l == a.n_lin - 2);
             FTL(l == 2, 0);
             const int kind = (L.h_ks == 0) ? KIND_FIRST : (L.pe_ks ? KIND_SKIP : KIND_NORMAL);
             const char* xr = (cur ? xb1 : xb0) + lane * 16;
@@ -589,33 +540,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                     b1 = *reinterpret_cast<const f32x4*>(a.bias + l * H + 32 * p + 16 + 4 * g);
                 }
                 V8 bh[NCT], bl[NCT];
-                // RING schedule of a GEMM with NS >= 8 K-steps: steps 0, 1 from the rolled prologue (register slots 0, 1), steps 2, 3 from the LDS side
-                // ring, step t >= 4 in register slot (t - 2) % 3, requested at the top of step t - 4 (t <= 6: the slot is free) or t - 2 (its slot's
-                // previous occupant t - 3 was consumed one step earlier); waits count the loads issued inside this K-loop only (see s == 0)
-                constexpr bool RK = RING && NS >= 8;
-                V8 ar[NFR];
                 static_for<NS>([&](auto s_c) __attribute__((always_inline)) {
                     constexpr int s = decltype(s_c)::value;
-                    if constexpr (s == 0) {
-                        asm volatile("" : "+v"(b0), "+v"(b1));   // bias (and the prologue) have landed
-                        if constexpr (RK) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // ... and the side ring (older than the bias loads)
-                    }
-                    constexpr int sa = RK ? (s <= 1 ? s : (s + 1) % 3) : s % (PD + 1);          // RK: (s - 2) % 3 for s >= 4
-                    constexpr bool FROM_RING = RK && (s == 2 || s == 3);
-                    if constexpr (RK) {
-                        constexpr int t = (s <= 2) ? s + 4 : ((s >= 5) ? s + 2 : -1);            // the step requested at the top of step s
-                        if constexpr (t >= 4 && t < NS) {
-#pragma unroll
-                            for (int f = 0; f < NFR; ++f) asm_gload16(af[(t + 1) % 3][f], wvoff, wb + (t * NFR + f) * FRAG_BYTES);
-                        }
-                        if constexpr (FROM_RING) {
-#pragma unroll
-                            for (int f = 0; f < NFR; ++f) ar[f] = *reinterpret_cast<const V8*>(ring_rd + ((s - 2) * NFR + f) * FRAG_BYTES);
-                        }
-                    } else {
-                        if constexpr (s + PD < NS) load_a(std::integral_constant<int, s + PD>{});
-                    }
-                    auto& Aop = [&]() __attribute__((always_inline)) -> V8 (&)[NFR] { if constexpr (FROM_RING) return ar; else return af[sa]; }();
+                    if constexpr (s == 0) asm volatile("" : "+v"(b0), "+v"(b1));   // bias (and the prologue) have landed
+                    constexpr int sa = s % (PD + 1);
+                    if constexpr (s + PD < NS) load_a(std::integral_constant<int, s + PD>{});
                     constexpr bool is_pe = (KIND == KIND_FIRST) || (KIND == KIND_SKIP && s < PE_KS);
                     constexpr int sb = is_pe ? s : ((KIND == KIND_SKIP) ? s - PE_KS : s);
 #pragma unroll
@@ -624,24 +553,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                         bh[ct] = *reinterpret_cast<const V8*>(base + ((sb * NCT + ct) * NPART + 0) * FRAG_BYTES);
                         bl[ct] = *reinterpret_cast<const V8*>(base + ((sb * NCT + ct) * NPART + (NPART - 1)) * FRAG_BYTES);
                     }
-                    if constexpr (RK) {
-                        if constexpr (s <= 1) {       // the prologue's registers landed with the drain at s == 0; the wait NAMES them (no use may move above it)
+                    constexpr int younger = ((s + PD < NS) ? PD : (NS - 1 - s)) * NFR;
 #pragma unroll
-                            for (int f = 0; f < NFR; f += 2) asm_wait_vm<(s + 1) * NFR>(af[sa][f], af[sa][f + 1]);
-                        }
-                        if constexpr (s >= 4) {
-                            // loads issued in this K-loop that are younger than step s's: steps t > s requested at a step <= s
-                            constexpr auto req = [](int t) constexpr { return t <= 6 ? t - 4 : t - 2; };
-                            constexpr int younger = ((s + 1 < NS && req(s + 1) <= s) ? NFR : 0) + ((s + 2 < NS && req(s + 2) <= s) ? NFR : 0) +
-                                                    ((s + 3 < NS && req(s + 3) <= s) ? NFR : 0);
-#pragma unroll
-                            for (int f = 0; f < NFR; f += 2) asm_wait_vm<younger>(af[sa][f], af[sa][f + 1]);
-                        }
-                    } else {
-                        constexpr int younger = ((s + PD < NS) ? PD : (NS - 1 - s)) * NFR;
-#pragma unroll
-                        for (int f = 0; f < NFR; f += 2) asm_wait_vm<younger>(af[sa][f], af[sa][f + 1]);
-                    }
+                    for (int f = 0; f < NFR; f += 2) asm_wait_vm<younger>(af[sa][f], af[sa][f + 1]);
                     FTL(l == 2 && KIND == KIND_NORMAL, 5 + s + 24 * (p - p0));      // K-step s (of the wave's pair p - p0): its fragments have landed
                     if constexpr (s == 0) {
                         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -656,24 +570,24 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                     if constexpr (NPART == 1) {
 #pragma unroll
                         for (int ct = 0; ct < NCT; ++ct) {
-                            acc[0][ct] = mfma16(Aop[0], bh[ct], acc[0][ct]);
-                            acc[1][ct] = mfma16(Aop[1], bh[ct], acc[1][ct]);
+                            acc[0][ct] = mfma16(af[sa][0], bh[ct], acc[0][ct]);
+                            acc[1][ct] = mfma16(af[sa][1], bh[ct], acc[1][ct]);
                         }
                     } else {
 #pragma unroll
                         for (int ct = 0; ct < NCT; ++ct) {
-                            if constexpr (SCALED) { accx[0][ct] = mfma16(Aop[0], bl[ct], accx[0][ct]); accx[1][ct] = mfma16(Aop[2], bl[ct], accx[1][ct]); }
-                            else { acc[0][ct] = mfma16(Aop[0], bl[ct], acc[0][ct]); acc[1][ct] = mfma16(Aop[2], bl[ct], acc[1][ct]); }
+                            if constexpr (SCALED) { accx[0][ct] = mfma16(af[sa][0], bl[ct], accx[0][ct]); accx[1][ct] = mfma16(af[sa][2], bl[ct], accx[1][ct]); }
+                            else { acc[0][ct] = mfma16(af[sa][0], bl[ct], acc[0][ct]); acc[1][ct] = mfma16(af[sa][2], bl[ct], acc[1][ct]); }
                         }
 #pragma unroll
                         for (int ct = 0; ct < NCT; ++ct) {
-                            acc[0][ct] = mfma16(Aop[0], bh[ct], acc[0][ct]);
-                            acc[1][ct] = mfma16(Aop[2], bh[ct], acc[1][ct]);
+                            acc[0][ct] = mfma16(af[sa][0], bh[ct], acc[0][ct]);
+                            acc[1][ct] = mfma16(af[sa][2], bh[ct], acc[1][ct]);
                         }
 #pragma unroll
                         for (int ct = 0; ct < NCT; ++ct) {
-                            if constexpr (SCALED) { accx[0][ct] = mfma16(Aop[1], bh[ct], accx[0][ct]); accx[1][ct] = mfma16(Aop[3], bh[ct], accx[1][ct]); }
-                            else { acc[0][ct] = mfma16(Aop[1], bh[ct], acc[0][ct]); acc[1][ct] = mfma16(Aop[3], bh[ct], acc[1][ct]); }
+                            if constexpr (SCALED) { accx[0][ct] = mfma16(af[sa][1], bh[ct], accx[0][ct]); accx[1][ct] = mfma16(af[sa][3], bh[ct], accx[1][ct]); }
+                            else { acc[0][ct] = mfma16(af[sa][1], bh[ct], acc[0][ct]); acc[1][ct] = mfma16(af[sa][3], bh[ct], acc[1][ct]); }
                         }
                     }
                 });
@@ -697,40 +611,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                         }
                         issue_prologue(ln, pn);
                     }
-                    if (lasth) {
-                        // the eight rows of w this lane's accumulators belong to (tile 0 / tile 1 of the pair): PLAIN loads behind the rolled prologue - the
-                        // compiler's wait for them covers the prologue too, which is older and lands first; their own latency passes under the activations
-                        const f32x4 wl0 = *reinterpret_cast<const f32x4*>(a.wlast + 32 * p + 4 * g);
-                        const f32x4 wl1 = *reinterpret_cast<const f32x4*>(a.wlast + 32 * p + 16 + 4 * g);
-                        float hp[NCT];
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) hp[ct] = 0.f;
-                        static_for<4>([&](auto q_c) __attribute__((always_inline)) {
-                            constexpr int t = decltype(q_c)::value >> 1, r = 2 * (decltype(q_c)::value & 1);
-                            const float w0 = t ? wl1[r] : wl0[r], w1 = t ? wl1[r + 1] : wl0[r + 1];
-                            float s0 = 0.f, s1 = 0.f;
-                            static_for<NCT>([&](auto ct_c) __attribute__((always_inline)) {
-                                constexpr int ct = decltype(ct_c)::value;
-                                float x0, x1;
-                                if constexpr (!GRAD) { x0 = softplus_fast(zval(t, ct, r)); x1 = softplus_fast(zval(t, ct, r + 1)); }
-                                else if constexpr (ct == 0) { softplus_sig_fast(zval(t, 0, r), x0, s0); softplus_sig_fast(zval(t, 0, r + 1), x1, s1); }
-                                else { x0 = s0 * zval(t, ct, r); x1 = s1 * zval(t, ct, r + 1); }
-                                // scalar_only(): a chain of FMAs into one accumulator must stay scalar VALU code here (udf_mlp_rev32.inc: pe_rows, lasth_epilogue)
-                                hp[ct] = fmaf(x0, w0, hp[ct]);
-                                scalar_only(hp[ct]);
-                                hp[ct] = fmaf(x1, w1, hp[ct]);
-                                scalar_only(hp[ct]);
-                            });
-                        });
-                        float* const red = reinterpret_cast<float*>(pebuf);
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) {
-                            float v = hp[ct];
-                            v += __shfl_xor(v, 16);
-                            v += __shfl_xor(v, 32);
-                            if (g == 0) red[(p * NCT + ct) * 16 + j] = v;
-                        }
-                    } else {
                     if (!last) {
                         // (round 6: split_f16_pair here, 2.5 instead of 5 instructions per value, brought no gain - step 0.5206 / 0.5211 against
                         // 0.5193 / 0.5175 ms - and was retired; it is in git history)
@@ -762,52 +642,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
                             }
                         });
                     }
-                    }
                     FTL(l == 2, 20 + 24 * pi);      // this pair's epilogue done
                 }
             });
 
             FTL(l == 2, 2);
-            if (lasth) {
-                __syncthreads();   // the partial sums of every pair are in LDS
-                if (wave == 0) {
-                    const float* const red = reinterpret_cast<const float*>(pebuf);
-                    const float inv_scale = 1.0f / a.scale;
-                    const float b_last = a.bias[(a.n_lin - 1) * H];
-                    const int npl = L.n_pairs;
-                    auto out_sum = [&](int ct, float bias) __attribute__((always_inline)) -> float {
-                        float h = 0.f;
-                        for (int pp = 0; pp < npl; ++pp) h += red[(pp * NCT + ct) * 16 + j];      // pairs in order, then the bias
-                        return h + bias;
-                    };
-                    if constexpr (!GRAD) {
-                        for (int ct = g; ct < NCT; ct += 4) {       // lane group g takes column tiles g, g + 4
-                            const long long pp = pbase + 16 * ct + j;
-                            const float h = out_sum(ct, b_last);
-                            const float u = (a.udf_type == EMAP_UDF_ABS) ? fabsf(h) : ((a.udf_type == EMAP_UDF_SQUARE) ? h * h : h);
-                            if constexpr (IS) { if (j < a.is_m) { is_rays[ct].nu[j] = u * inv_scale; if (a.err && !(fabsf(h) <= 3.0e38f)) atomicOr(a.err, EMAP_F_MLP_NONFINITE); } }
-                            else if (pp < a.P) { a.udf[pp] = u * inv_scale; if (a.err && !(fabsf(h) <= 3.0e38f)) atomicOr(a.err, EMAP_F_MLP_NONFINITE); }
-                        }
-                    } else if (g == 0) {
-                        const long long pp = pbase + j;
-                        const float h = out_sum(0, b_last), t1 = out_sum(1, 0.f), t2 = out_sum(2, 0.f), t3 = out_sum(3, 0.f);
-                        float u, m;
-                        if (a.udf_type == EMAP_UDF_ABS) { u = fabsf(h); m = (h > 0.f) ? 1.f : ((h < 0.f) ? -1.f : 0.f); }
-                        else if (a.udf_type == EMAP_UDF_SQUARE) { u = h * h; m = 2.f * h; }
-                        else { u = h; m = 1.f; }
-                        if (pp < a.P) {
-                            a.udf[pp] = u * inv_scale;
-                            a.grad[3 * pp + 0] = m * t1;
-                            a.grad[3 * pp + 1] = m * t2;
-                            a.grad[3 * pp + 2] = m * t3;
-                            if (a.err && !(fabsf(h) + fabsf(t1) + fabsf(t2) + fabsf(t3) <= 3.0e38f)) atomicOr(a.err, EMAP_F_MLP_NONFINITE);
-                        }
-                    }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                FTL(true, 18);
-                __syncthreads();   // the tile is done with xbuf / pebuf before the next tile's PE overwrites them
-            } else if (!last) {
+            if (!last) {
                 if constexpr (!PP) __syncthreads();   // barrier A: every wave has finished reading this layer's input
                 char* const xbuf = (cur ^ (PP ? 1 : 0)) ? xb1 : xb0;
                 static_for<PPW>([&](auto pi_c) __attribute__((always_inline)) {
@@ -877,7 +717,6 @@ static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointS
     a.n_tiles = (int)((P + PT - 1) / PT);
     a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
     for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
-    a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
     const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES;   // <= 80 KiB: two workgroups per CU (8 waves: one, two exchange buffers)
     static uint64_t attr_mask = 0;   // per device: the LDS-size attribute is a property of (function, device)
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, GRAD, NW>;
@@ -902,8 +741,6 @@ static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointS
 // (round 5: 64-point tiles as ONE 8-wave workgroup per CU at 512 .. 1023 tiles measured +15 us at the coarse pass of the 512-ray render against two
 // 4-wave workgroups per CU; that form was retired and is in git history)
 template <int MODE>
-int launch_mlp_val32_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, hipStream_t st, int32_t* err);   // udf_mlp_rev32.inc
-template <int MODE>
 int launch_mlp_fs2_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, float* grad3,
                         hipStream_t st, int32_t* err) {
     const bool grad = grad3 != nullptr;
@@ -926,9 +763,6 @@ int launch_mlp_fs2_mode(const NetLayout& L, const void* packed, const PointSourc
             if (P <= 8192) return launch_mlp_fs2_t<256, MODE, 2, false, 8>(L, packed, src, P, udf, grad3, st, err);
             if (P <= 12288) return launch_mlp_fs2_t<256, MODE, 3, false, 8>(L, packed, src, P, udf, grad3, st, err);
             if (P <= 16384) return launch_mlp_fs2_t<256, MODE, 4, false, 8>(L, packed, src, P, udf, grad3, st, err);
-            // opt-in (emap_set_value_tile_mode): wide launches as the forward sweep of the 32x32 kernel (udf_mlp_rev32.inc, VAL); its forward fragments are plain hi / lo
-            // ones unless the mode is f16x3m (mixed MX layout: that mode's value passes stay here)
-            if (tiles(64) >= 512 && value_tile_mode() && L.has_rev && !L.mx_fwd) return launch_mlp_val32_mode<MODE>(L, packed, src, P, udf, st, err);
             if (P <= 24576) return launch_mlp_fs2_t<256, MODE, 3, false, 4>(L, packed, src, P, udf, grad3, st, err);
             if (P > 32768 && P <= 36864) return launch_mlp_fs2_t<256, MODE, 3, false, 8>(L, packed, src, P, udf, grad3, st, err);
             if (P > 32768 && P <= 49152) return launch_mlp_fs2_t<256, MODE, 4, false, 8>(L, packed, src, P, udf, grad3, st, err);
@@ -982,10 +816,7 @@ static int launch_is_t(const NetLayout& L, const void* packed, const IsLaunch& q
     a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
     for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
     a.is_udf_coarse = q.udf_coarse; a.is_z_final = q.z_final; a.is_n_rays = q.N; a.is_sc = q.Sc; a.is_m = q.m; a.is_steps = q.steps;
-    a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
-    // + the side ring of the 8-wave geometries (RING in the kernel: 8 KiB per wave behind the rays' lists)
-    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15) +
-                       ((NW == 8 && NPART == 2 && H == 256 && EMAP_IS_RING) ? (size_t)NW * 2 * 2 * NPART * FRAG_BYTES : 0);
+    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15);
     static uint64_t attr_mask = 0;
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, false, NW, true>;
     if (attr_needed(attr_mask)) {

@@ -87,12 +87,7 @@ __device__ __forceinline__ void asm_wait_vm1(V8& r0) {
 // place +1 % at 512 rays, +2 % at 4096; counters per tile, compositing deferred: +0.6 % / +1.7 %).  Same arithmetic per ray whoever runs
 // it: bit-identical to the two-launch form.
 struct NoFuse {};
-// VAL (round 6): the forward sweep ALONE as a value kernel - no sigma' stash, no reverse sweep, udf out.  The coarse value pass of a render
-// (>= 512 tiles of 64 points) runs it instead of udf_mlp_fs2_kernel<.., 4, false, 4>: same tile geometry (4 waves, 64 points, two workgroups per
-// CU, 80 KiB of LDS), but half the MFMA instructions for the same FLOPs and the pinned K-loop / head prefetch of this file, for which the 16x16
-// kernel has no registers on its 64-point tile (udf_mlp_kernel.inc: ROLL).  Also clears the arrival counters of the fused compositing tail,
-// as every first launch of a render does (PointSource::zero_cnt).
-template <int H, int MODE, int NW = 4, int NC = 2, bool FWD6 = false, bool BWD6 = true, bool COMP = false, bool VAL = false>
+template <int H, int MODE, int NW = 4, int NC = 2, bool FWD6 = false, bool BWD6 = true, bool COMP = false>
 __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs a, const std::conditional_t<COMP, CompositeFuse, NoFuse> cf) {
     using T = typename Prec<MODE>::T;
     using V8 = typename Prec<MODE>::V;
@@ -159,11 +154,6 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
 
     clock_stamp(a.clk, 0);
     static_assert(!COMP || NC == 2, "the fused compositing tail writes a tile's 64 outputs from one wave");
-    static_assert(!VAL || (!COMP && !FWD6), "value-only form: plain f16 / bf16 forward sweep, nothing to composite");
-    if constexpr (VAL) {
-        if (a.src.zero_cnt)
-            for (int i = blockIdx.x * (NW * 64) + tid; i < a.src.zero_n; i += gridDim.x * (NW * 64)) a.src.zero_cnt[i] = 0;
-    }
     for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
         const long long pbase = (long long)tile * PT;
 
@@ -772,11 +762,9 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
 
         // LASTH applies when the last hidden layer is an ordinary one (hidden input only) and the output layer reads no PE block (wave-uniform)
         bool fuse_last = false;
-        if constexpr (!VAL) {
-            if (n_hidden >= 1) {
-                const LayerDesc Lh = a.layer[n_hidden - 1];
-                fuse_last = (Lh.h_ks != 0) && !Lh.pe_ks && (a.tpe_off[a.n_lin - 1] < 0);
-            }
+        if (n_hidden >= 1) {
+            const LayerDesc Lh = a.layer[n_hidden - 1];
+            fuse_last = (Lh.h_ks != 0) && !Lh.pe_ks && (a.tpe_off[a.n_lin - 1] < 0);
         }
         // ================= forward sweep: hidden layers 0 .. n_lin-2 =================
         // (the LASTH layer is peeled off the loop: with a run-time branch around its body INSIDE the loop, the output fragments of the other
@@ -808,16 +796,6 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
                     if constexpr (pi + 1 < PPW)               // the next tile's head, under this tile's epilogue
                         prefetch_head(ns_c, yes_t{}, wb + (size_t)NS_ * NFR * FRAG_BYTES, bp + 32);
                     if constexpr (LASTH) { lasth_epilogue(pi_c); return; }
-                    if constexpr (VAL) {      // value only: softplus, hi / lo split - nothing else leaves the epilogue
-                        static_for<NC>([&](auto c_c) __attribute__((always_inline)) {
-                            constexpr int c = decltype(c_c)::value;
-                            static_for<8>([&](auto rp_c) __attribute__((always_inline)) {
-                                constexpr int r = 2 * decltype(rp_c)::value;
-                                put2(pi_c, c_c, std::integral_constant<int, r>{}, softplus_fast(zval(c, r)), softplus_fast(zval(c, r + 1)));
-                            });
-                        });
-                        return;
-                    }
                     // activation, sigma' stash (unorm16, 16 dwords per lane per row tile; SG24: + 8 dwords of low bytes)
                     uint32_t sg[8 * NC], sgl[SG24 ? 8 * NC : 1];
                     static_for<NC>([&](auto c_c) __attribute__((always_inline)) {
@@ -906,9 +884,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             }
         };
         for (int l = 0; l < n_loop; ++l) fwd_layer(l, no_t{});
-        if constexpr (!VAL) {
-            if (fuse_last) fwd_layer(n_hidden - 1, yes_t{});
-        }
+        if (fuse_last) fwd_layer(n_hidden - 1, yes_t{});
 
         // ================= last layer: one real output row, split along K (LASTH: done in the epilogues above) =================
         if (!fuse_last) {
@@ -920,7 +896,6 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             for (int c = 0; c < NC; ++c) { hpart[c] = zval(c, 0); asm volatile("" : "+v"(hpart[c])); }   // scalars now: frees the accumulators
         }
 
-        if constexpr (!VAL) {
         // ================= reverse sweep =================
         // delta_z[b-1] = sigma'(z[b-1]) (.) delta_a[b-1] for the row tile whose delta_a sits in the accumulators
         auto bwd_epilogue = [&](auto pi_c) __attribute__((always_inline)) {
@@ -1000,7 +975,6 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
         for (int b = a.n_lin - 2; b >= 1; --b) rev_layer(b);
         // layer 0: only PE rows
         pe_rows(a.tpe_off[0]);
-        }   // !VAL
 
         // ================= reduction over lane halves and waves, output =================
         __syncthreads();   // everyone is done with xbuf: reuse it as red[wave][c][4][32]
@@ -1011,7 +985,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             // hpart: the output row of the K-split GEMM sits in the lower lane half; LASTH: every lane holds the partial of its own 32 features
             float v[4] = {(hh == 0 || fuse_last) ? hpart[c] : 0.f, hh ? g3[c][2] : g3[c][0], hh ? g3[c][0] : g3[c][1], hh ? g3[c][1] : g3[c][2]};
 #pragma unroll
-            for (int k = 0; k < (VAL ? 1 : 4); ++k) {
+            for (int k = 0; k < 4; ++k) {
                 v[k] += __shfl_xor(v[k], 32);
                 if (hh == 0) red[((wave * NC + c) * 4 + k) * 32 + j] = v[k];
             }
@@ -1025,7 +999,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
             const float b_last = a.bias[(a.n_lin - 1) * H];
             float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int k = 0; k < (VAL ? 1 : 4); ++k) {
+            for (int k = 0; k < 4; ++k) {
                 float acc_w = 0.f;
 #pragma unroll
                 for (int w = 0; w < NW; ++w) acc_w += red[((w * NC + c) * 4 + k) * 32 + j];
@@ -1043,8 +1017,6 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
                     __hip_atomic_store(a.grad + 3 * pp + 0, m * v[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(a.grad + 3 * pp + 1, m * v[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(a.grad + 3 * pp + 2, m * v[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else if constexpr (VAL) {
-                    a.udf[pp] = u * inv_scale;
                 } else {
                     a.udf[pp] = u * inv_scale;
                     a.grad[3 * pp + 0] = m * v[1];
@@ -1161,43 +1133,6 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
     if (fuse) hipLaunchKernelGGL(kern_c, dim3(grid), dim3(NW * 64), lds, st, a, *fuse);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, NoFuse{});
     return check_launch("udf_mlp_rev32");
-}
-
-// The forward sweep alone (VAL): the coarse value pass of a render.  No scratch: nothing is stashed.
-template <int H, int MODE>
-static int launch_mlp_val32_t(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, hipStream_t st, int32_t* err) {
-    constexpr int NPART = Prec<MODE>::NPART;
-    constexpr int NW = 4, NC = 2, PT = 32 * NC;
-    MlpArgs a;
-    memset(&a, 0, sizeof(a));
-    const char* pk = static_cast<const char*>(packed);
-    a.frags = pk + L.r32_frag_off_bytes;
-    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
-    a.src = src; a.P = P; a.udf = udf; a.err = err;
-    a.n_tiles = (int)((P + PT - 1) / PT);
-    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
-    for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
-    const size_t lds = (size_t)((H / 32) + PE_KS) * 2 * NC * NPART * FRAG_BYTES;
-    static uint64_t attr_mask = 0;
-    auto kern = udf_mlp_rev32_kernel<H, MODE, NW, NC, false, true, false, true>;
-    if (attr_needed(attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-            return EMAP_E_LAUNCH;
-        }
-    }
-    if (a.n_tiles <= 0) return EMAP_OK;
-    const int grid = a.n_tiles < 4096 ? a.n_tiles : 4096;
-    a.clk = prof_clk_here();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, NoFuse{});
-    return check_launch("udf_mlp_val32");
-}
-
-template <int MODE>
-int launch_mlp_val32_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, hipStream_t st, int32_t* err) {
-    if (L.H == 256) return launch_mlp_val32_t<256, MODE>(L, packed, src, P, udf, st, err);
-    set_error("no 32x32 value kernel for d_hidden=%d", L.H);
-    return EMAP_E_INVALID;
 }
 
 template <int MODE>

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     const int xm_lane = g * (NCT * NPART * FRAG_BYTES) + FRAG_BYTES;   // + j * {16, 8, 4} inside the slot (k_run_mx)
     const char* xmr = xb0 + xm_lane;
     const char* per = pebuf + lane * 16;
-    const int p0 = wave * PPW;     // this wave's first tile pair
+    const int p0 = wave * PPW;     // this wave's tile pair
     // selectors of the stash transposition (see header): B operand lane (kg = g, n = j) of S_h holds S_h[8g + e][j] = [phi(g, e) == 16h + j]
     V8 sel[2];
 #pragma unroll
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
 
         f32x4 acc[2][NCT];
         f32x4 accx[SCALED ? 2 : 1][NCT];
-        V8 o[PPW][NCT][NPART];
+        V8 o[NCT][NPART];             // this wave's output tile pair (PPW == 1)
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
         auto zval = [&](int t, int ct, int r) __attribute__((always_inline)) -> float {
@@ -529,26 +529,22 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
         auto k_run = [&](auto ns_c, auto npe_c, auto init_c, const char* wb, int xs0, int pes0, const float* bp) __attribute__((always_inline)) {
             k_run_p(ns_c, npe_c, init_c, std::false_type{}, wb, xs0, pes0, bp);
         };
-        auto put1 = [&](auto pi_c, int ct, int e, float x) __attribute__((always_inline)) -> T {
-            constexpr int pi = decltype(pi_c)::value;
+        auto put1 = [&](int ct, int e, float x) __attribute__((always_inline)) -> T {
             const T h = (T)x;
-            o[pi][ct][0][e] = h;
-            if constexpr (NPART == 2) o[pi][ct][1][e] = (T)((x - (float)h) * LO_SCALE);
+            o[ct][0][e] = h;
+            if constexpr (NPART == 2) o[ct][1][e] = (T)((x - (float)h) * LO_SCALE);
             return h;
         };
         auto publish = [&](int n_pairs) __attribute__((always_inline)) {
             if constexpr (!PP) __syncthreads();   // barrier A: every wave has finished reading the exchange buffer
             char* const xbuf = (cur ^ (PP ? 1 : 0)) ? xb1 : xb0;
-            static_for<PPW>([&](auto pi_c) __attribute__((always_inline)) {
-                constexpr int pi = decltype(pi_c)::value;
-                if (p0 + pi < n_pairs) {
+            if (p0 < n_pairs) {
 #pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct)
+                for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                        for (int pt = 0; pt < (SMX ? 1 : NPART); ++pt)      // SMX: the lo parts leave as fp6 entries only (below)
-                            *reinterpret_cast<V8*>(xbuf + (((p0 + pi) * NCT + ct) * NPART + pt) * FRAG_BYTES + lane * 16) = o[pi][ct][pt];
-                }
-            });
+                    for (int pt = 0; pt < (SMX ? 1 : NPART); ++pt)      // SMX: the lo parts leave as fp6 entries only (below)
+                        *reinterpret_cast<V8*>(xbuf + ((p0 * NCT + ct) * NPART + pt) * FRAG_BYTES + lane * 16) = o[ct][pt];
+            }
             if constexpr (SMX) {
                 // MX B operands: lane (g, j) converts column j of column tile g - the 32 values of the pair that sit, 8 each, in the four lanes
                 // (g', j) of this wave.  They are gathered WITHOUT an LDS round trip: for every dword d of the output fragments, the four
@@ -564,8 +560,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     for (int pt = 0; pt < 2; ++pt)
 #pragma unroll
                         for (int d = 0; d < 4; ++d) {
-                            const uint32_t x0 = __builtin_bit_cast(u32x4, o[0][0][pt])[d], x1 = __builtin_bit_cast(u32x4, o[0][1][pt])[d];
-                            const uint32_t x2 = __builtin_bit_cast(u32x4, o[0][2][pt])[d], x3 = __builtin_bit_cast(u32x4, o[0][3][pt])[d];
+                            const uint32_t x0 = __builtin_bit_cast(u32x4, o[0][pt])[d], x1 = __builtin_bit_cast(u32x4, o[1][pt])[d];
+                            const uint32_t x2 = __builtin_bit_cast(u32x4, o[2][pt])[d], x3 = __builtin_bit_cast(u32x4, o[3][pt])[d];
                             const auto s02 = __builtin_amdgcn_permlane32_swap(x0, x2, false, false);
                             const auto s13 = __builtin_amdgcn_permlane32_swap(x1, x3, false, false);
                             const auto w01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
@@ -618,10 +614,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
         for (int l = 0; l < n_hidden; ++l) {
             const LayerDesc L = a.layer[l];
             const int kind = (L.h_ks == 0) ? KIND_FIRST : (L.pe_ks ? KIND_SKIP : KIND_NORMAL);
-            static_for<PPW>([&](auto pi_c) __attribute__((always_inline)) {
-                constexpr int pi = decltype(pi_c)::value;
-                const int p = p0 + pi;
-                if (p < L.n_pairs) {
+            const int p = p0;
+            if (p < L.n_pairs) {
                 const float* bp = a.bias + l * H + 32 * p + 4 * g;
                 const int ns = L.pe_ks + L.h_ks;
                 const char* wb = wbase + (size_t)(L.frag_off + p * ns * NFR) * FRAG_BYTES;
@@ -645,10 +639,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     softplus_sig_fast(zval(t, 0, r), a0, s0);
                     softplus_sig_fast(zval(t, 1, r), a1, s1);
                     const float t0 = s0 * zval(t, 2, r), t1 = s1 * zval(t, 3, r);
-                    put1(pi_c, 0, 4 * t + r, a0);
-                    put1(pi_c, 1, 4 * t + r, a1);
+                    put1(0, 4 * t + r, a0);
+                    put1(1, 4 * t + r, a1);
                     typedef T T2 __attribute__((ext_vector_type(2)));
-                    const T2 ap2 = {put1(pi_c, 2, 4 * t + r, t0), put1(pi_c, 3, 4 * t + r, t1)};
+                    const T2 ap2 = {put1(2, 4 * t + r, t0), put1(3, 4 * t + r, t1)};
                     bk[2 * q] = __builtin_bit_cast(uint32_t, ap2);
                     bk[2 * q + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pknorm_u16(s0, s1));
                     if constexpr (SLABLO) {
@@ -657,20 +651,19 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     }
                 });
                 {
-                    const V8 xh[4] = {o[pi][0][0], o[pi][1][0], o[pi][2][0], o[pi][3][0]};
+                    const V8 xh[4] = {o[0][0], o[1][0], o[2][0], o[3][0]};
                     stash_store(sa + (size_t)va.V.a_off[l + 1] * 1024 + (2 * p) * 2048, xh, 2);
                 }
                 if constexpr (LO_STASH) {
                     if (stash_lo) {
-                        const V8 xl[4] = {o[pi][0][NPART - 1], o[pi][1][NPART - 1], o[pi][2][NPART - 1], o[pi][3][NPART - 1]};
+                        const V8 xl[4] = {o[0][NPART - 1], o[1][NPART - 1], o[2][NPART - 1], o[3][NPART - 1]};
                         stash_store(sa + va.V.lo_a_delta + (size_t)va.V.a_off[l + 1] * 1024 + (2 * p) * 2048, xl, 2);
                     }
                 }
                 u32x4* dst = reinterpret_cast<u32x4*>(slab + ((size_t)(l * NPAIR + p) * NSLAB) * 1024 + lane * 16);
 #pragma unroll
                 for (int c = 0; c < NSLAB; ++c) dst[c * 64] = u32x4{bk[4 * c], bk[4 * c + 1], bk[4 * c + 2], bk[4 * c + 3]};
-                }
-            });
+            }
             publish(L.n_pairs);
         }
 
@@ -773,10 +766,8 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
         // ================= reverse sweep: adjoints of the pre-activations of layers n_lin-2 .. 0 =================
         for (int b = a.n_lin - 1; b >= 1; --b) {
             const int lz = b - 1;                         // the layer whose zb, zb' this step produces
-            static_for<PPW>([&](auto pi_c) __attribute__((always_inline)) {
-                constexpr int pi = decltype(pi_c)::value;
-                const int p = p0 + pi;
-                if (p < a.layer[lz].n_pairs) {
+            const int p = p0;
+            if (p < a.layer[lz].n_pairs) {
                 // this lane's slab entry of layer lz: a' (hi) and sigma' of its rows and points; the loads are older than every
                 // fragment load of the GEMM below, so they have landed by its first counted wait
                 load_slab(slab + ((size_t)(lz * NPAIR + p) * NSLAB) * 1024);
@@ -822,23 +813,22 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
                     const float av0 = zval(t, 0, r), av1 = zval(t, 1, r), at0 = zval(t, 2, r), at1 = zval(t, 3, r);
                     const float zb0 = fmaf(100.0f * (1.0f - s0) * ap0, at0, s0 * av0);
                     const float zb1 = fmaf(100.0f * (1.0f - s1) * ap1, at1, s1 * av1);
-                    put1(pi_c, 0, 4 * t + r, zb0);
-                    put1(pi_c, 1, 4 * t + r, zb1);
-                    put1(pi_c, 2, 4 * t + r, s0 * at0);
-                    put1(pi_c, 3, 4 * t + r, s1 * at1);
+                    put1(0, 4 * t + r, zb0);
+                    put1(1, 4 * t + r, zb1);
+                    put1(2, 4 * t + r, s0 * at0);
+                    put1(3, 4 * t + r, s1 * at1);
                 });
                 {
-                    const V8 xh[4] = {o[pi][0][0], o[pi][1][0], o[pi][2][0], o[pi][3][0]};
+                    const V8 xh[4] = {o[0][0], o[1][0], o[2][0], o[3][0]};
                     stash_store(sz + (size_t)va.V.z_off[lz] * 1024 + (2 * p) * 2048, xh, 2);
                 }
                 if constexpr (LO_STASH) {
                     if (stash_lo) {
-                        const V8 xl[4] = {o[pi][0][NPART - 1], o[pi][1][NPART - 1], o[pi][2][NPART - 1], o[pi][3][NPART - 1]};
+                        const V8 xl[4] = {o[0][NPART - 1], o[1][NPART - 1], o[2][NPART - 1], o[3][NPART - 1]};
                         stash_store(sz + va.V.lo_z_delta + (size_t)va.V.z_off[lz] * 1024 + (2 * p) * 2048, xl, 2);
                     }
                 }
-                }
-            });
+            }
             if (b > 1) publish(a.layer[lz].n_pairs);
         }
         __syncthreads();   // the tile is done with xbuf / pebuf / red before the next tile's PE overwrites them

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """s_memtime stamps of hidden layer 2 of the FIRST MLP pass inside the fused importance-sampling kernel (udf_mlp_fs2_kernel<256,f16x3,2,false,8,IS>, 512 rays)
-in a -DEMAP_TIMELINE -DEMAP_TIMELINE_IS build (scripts/build_variant.sh tlis -DEMAP_TIMELINE -DEMAP_TIMELINE_IS [-DEMAP_IS_RING=0]); stamps as in fs2_timeline.py."""
+in a -DEMAP_TIMELINE -DEMAP_TIMELINE_IS build (scripts/build_variant.sh tlis -DEMAP_TIMELINE -DEMAP_TIMELINE_IS); stamps as in fs2_timeline.py."""
 import ctypes as C, json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -464,8 +464,9 @@ def test_ctypes_structs_match_the_header_field_for_field(tmp_path):
         assert n_members == len(cls._fields_), (cname, n_members, len(cls._fields_))
 
 
-def test_round6_switches_and_argument_checks():
-    """ABI 9 host-only entry points: the process-wide switches return their previous value; the one-shot all-reduce's time-out is range-checked."""
+def test_host_switches_and_argument_checks():
+    """ABI 9 host-only entry points: the process-wide switches return their previous value; the one-shot all-reduce's time-out is range-checked.
+    ABI 12 removed the value-tile switch (emap_set_value_tile_mode): the library no longer exports it."""
     L = _lib.lib()
     assert L.emap_set_fused_composite(0) == 1 and L.emap_set_fused_composite(1) == 0 and L.emap_set_fused_composite(1) == 1
     prev = L.emap_set_fused_sampling(2)
@@ -473,10 +474,7 @@ def test_round6_switches_and_argument_checks():
     assert L.emap_ar_set_timeout_ms(0) == -1 and b"ar_set_timeout_ms" in L.emap_last_error()
     assert L.emap_ar_set_timeout_ms(10 ** 7) == -1
     assert L.emap_ar_set_timeout_ms(10000) == 0
-    # ABI 10: the 32x32 forward sweep for the wide value launches - off unless EMAP_VALUE32=1 was set at load
-    import os
-    d = 1 if os.environ.get("EMAP_VALUE32", "")[:1] == "1" else 0
-    assert L.emap_set_value_tile_mode(1) == d and L.emap_set_value_tile_mode(0) == 1 and L.emap_set_value_tile_mode(d) == 0
+    assert L.emap_abi_version() == 12 and not hasattr(C.CDLL(_lib.LIB_PATH), "emap_set_value_tile_mode")
 
 
 def test_render_workspace_grows_with_the_arrival_counters_and_the_24_bit_stash():
