@@ -23,6 +23,7 @@ PREC_F16X3E = 5    # f16x3 with f16 cross terms in both sweeps of the value+grad
 PRECISIONS = {"bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "f16x3": PREC_F16X3, "f16x3m": PREC_F16X3M, "f16x3e": PREC_F16X3E}
 UDF_TYPES = {"abs": 0, "square": 1, "sdf": 2}
 MAX_LIN = 12
+MAX_SAMPLES_PER_RAY = 1024   # EMAP_MAX_SAMPLES_PER_RAY: S = n_samples + up_sample_steps * (n_importance // up_sample_steps)
 ABI_VERSION = 12   # ABI 12 removed emap_set_value_tile_mode (the 32x32 value kernel)
 
 # EmapRenderParams.render_mode (ABI 11): use_unbias_render / use_norm_grad_for_cosine of the reference renderer

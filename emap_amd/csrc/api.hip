@@ -401,7 +401,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     const int m = (p->n_importance > 0) ? p->n_importance / K : 0;
     const int steps = (m > 0) ? K : 0;
     const int S = Sc + m * steps;
-    if (S > 256) { set_error("render_fwd: %d samples per ray exceed the kernel limit of 256", S); return EMAP_E_INVALID; }
+    if (S > EMAP_MAX_SAMPLES_PER_RAY) { set_error("render_fwd: %d samples per ray exceed the kernel limit of %d", S, EMAP_MAX_SAMPLES_PER_RAY); return EMAP_E_INVALID; }
     const Workspace w = plan_workspace(*p, &L);
     if (workspace_bytes < w.total) { set_error("render_fwd: workspace %zu < %zu bytes", workspace_bytes, w.total); return EMAP_E_WORKSPACE; }
     char* ws = static_cast<char*>(workspace);
@@ -415,8 +415,9 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     // render_core's tail inside the final value + grad_x launch (ABI 9) where that launch is the reverse-sweep kernel: the first launch of
     // the render clears the per-ray arrival counters, the final one composites every ray as its last tile completes
     int32_t* ray_cnt = reinterpret_cast<int32_t*>(ws + w.ray_cnt);
-    // (the fused tail composites in the default render mode only: the other two run the separate compositing and reduction launches)
-    const bool fuse_comp = p->render_mode == EMAP_RENDER_UNBIASED && g_fused_composite.load(std::memory_order_relaxed) &&
+    // (the fused tail composites in the default render mode and up to COMP_FUSED_MAX_S = 256 samples per ray only: the other shapes run the
+    // separate compositing and reduction launches)
+    const bool fuse_comp = p->render_mode == EMAP_RENDER_UNBIASED && S <= COMP_FUSED_MAX_S && g_fused_composite.load(std::memory_order_relaxed) &&
                            mlp_uses_rev(L, prec, (int64_t)N * S) && comp_list_entries((int64_t)N * S, S) <= COMP_LIST_MAX;
 
     if (steps == 0) {
@@ -611,6 +612,7 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
     if (N <= 0) return EMAP_OK;
     const int m = p->up_sample_steps > 0 && p->n_importance > 0 ? p->n_importance / p->up_sample_steps : 0;
     const int S = p->n_samples + m * (m > 0 ? p->up_sample_steps : 0);
+    if (S > EMAP_MAX_SAMPLES_PER_RAY) { set_error("render_bwd: %d samples per ray exceed the kernel limit of %d", S, EMAP_MAX_SAMPLES_PER_RAY); return EMAP_E_INVALID; }
     size_t o_du, o_dg, o_part;
     const size_t extra = render_bwd_extra(*p, &o_du, &o_dg, &o_part);
     const VjpPlan pl = plan_vjp(L, (int64_t)N * S, workspace_bytes > extra ? workspace_bytes - extra : 1);

@@ -157,6 +157,9 @@ struct CompositeFuse {
 // upper bound on the rays ONE workgroup of the value + grad_x kernel can come to own (its list lives in the kernel's exchange buffer): every tile
 // it runs (64 points, <= 512 workgroups) can complete at most 64 / S + 2 rays
 constexpr int COMP_LIST_MAX = 8192;
+// samples per ray of the fused tail: it composites with lane chunks of C <= 4 (udf_mlp_rev32.inc); longer rays take the separate
+// compositing and reduction launches (sampler.hip, C = 8 / 16)
+constexpr int COMP_FUSED_MAX_S = 256;
 inline long long comp_list_entries(long long P, int S) {
     const long long tiles = (P + 63) / 64, grid = tiles < 512 ? tiles : 512;
     return ((tiles + grid - 1) / (grid > 0 ? grid : 1)) * (64 / (S > 0 ? S : 1) + 2);

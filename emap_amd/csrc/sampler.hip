@@ -27,9 +27,11 @@ static float linspace_at_host(float start, float end, int steps, int i) {
     return (i < steps / 2) ? start + a : end - b;
 }
 
+// CAP: LDS capacity in samples per ray, MAXS or MAXS_WIDE (the launchers take MAXS whenever the shape fits it)
+template <int CAP>
 __global__ __launch_bounds__(64) void sample_pdf_kernel(const float* bins, const float* weights, int N, int n, int m,
                                                         float* samples, int64_t* inds, int32_t* err, const float* u) {
-    __shared__ float s_bins[MAXS], s_w[MAXS], s_pdf[MAXS], s_cdf[MAXS + 1];
+    __shared__ float s_bins[CAP], s_w[CAP], s_pdf[CAP], s_cdf[CAP + 1];
     const int ray = blockIdx.x, lane = threadIdx.x;
     for (int e = lane; e < n; e += 64) s_bins[e] = bins[(size_t)ray * n + e];
     for (int e = lane; e < n - 1; e += 64) s_w[e] = weights[(size_t)ray * (n - 1) + e];
@@ -38,12 +40,13 @@ __global__ __launch_bounds__(64) void sample_pdf_kernel(const float* bins, const
                     u ? u + (size_t)ray * m : nullptr);
 }
 
+template <int CAP>
 __global__ __launch_bounds__(64) void upsample_kernel(const float* rays_o, const float* rays_d, const float* z,
                                                       const float* udf, int N, int n, int m, const float* sample_dist,
                                                       float inv_s, float beta, float gamma, float* z_new, int64_t* inds,
                                                       int32_t* err) {
-    __shared__ float s_z[MAXS], s_u[MAXS];
-    __shared__ UpsampleScratch w;
+    __shared__ float s_z[CAP], s_u[CAP];
+    __shared__ UpsampleScratch<CAP> w;
     const int ray = blockIdx.x, lane = threadIdx.x;
     const float ox = rays_o[3 * ray], oy = rays_o[3 * ray + 1], oz = rays_o[3 * ray + 2];
     const float dx = rays_d[3 * ray], dy = rays_d[3 * ray + 1], dz = rays_d[3 * ray + 2];
@@ -58,10 +61,11 @@ __global__ __launch_bounds__(64) void upsample_kernel(const float* rays_o, const
 }
 
 // up_sample_no_occ_aware (:920-975) of one step on its own: the step-level counterpart of upsample_kernel (use_unbias_render=False)
+template <int CAP>
 __global__ __launch_bounds__(64) void upsample_plain_kernel(const float* z, const float* udf, int N, int n, int m, const float* sample_dist,
                                                             float beta, float gamma, float* z_new, int64_t* inds, int32_t* err) {
-    __shared__ float s_z[MAXS], s_u[MAXS];
-    __shared__ UpsampleScratch w;
+    __shared__ float s_z[CAP], s_u[CAP];
+    __shared__ UpsampleScratch<CAP> w;
     const int ray = blockIdx.x, lane = threadIdx.x;
     const float sd = *sample_dist;
     for (int e = lane; e < n; e += 64) {
@@ -76,10 +80,11 @@ __global__ __launch_bounds__(64) void upsample_plain_kernel(const float* z, cons
 // cat_z_vals: merge two sorted lists (stable: old samples first on ties), gather udf
 // (udf_renderer_blending.py:361-375)
 // ---------------------------------------------------------------------------------------------
+template <int CAP>
 __global__ __launch_bounds__(64) void merge_kernel(const float* z, const float* z_new, const float* udf,
                                                    const float* udf_new, int N, int n, int m, float* z_out,
                                                    float* udf_out, int64_t* perm) {
-    __shared__ float s_z[MAXS], s_n[MAXS];
+    __shared__ float s_z[CAP], s_n[CAP];
     const int ray = blockIdx.x, lane = threadIdx.x;
     for (int e = lane; e < n; e += 64) s_z[e] = z[(size_t)ray * n + e];
     for (int e = lane; e < m; e += 64) s_n[e] = z_new[(size_t)ray * m + e];
@@ -104,10 +109,11 @@ __global__ __launch_bounds__(64) void merge_kernel(const float* z, const float* 
 // The kernels the C ABI exposes one by one (emap_upsample_step[_plain], emap_merge_sorted) share the bodies.
 // ---------------------------------------------------------------------------------------------
 
-template <bool COARSE, bool MERGE, bool TAIL, bool PLAIN = false>
+// CAP: LDS capacity (MAXS, or MAXS_WIDE: 5 x 4 KiB of LDS per one-wave workgroup); n + m <= CAP after the merge and n_final + m before the tail
+template <int CAP, bool COARSE, bool MERGE, bool TAIL, bool PLAIN = false>
 __global__ __launch_bounds__(64) void sampler_step_kernel(const StepArgs a) {
-    __shared__ float s_z[MAXS], s_u[MAXS], s_n[MAXS];
-    __shared__ UpsampleScratch w;
+    __shared__ float s_z[CAP], s_u[CAP], s_n[CAP];
+    __shared__ UpsampleScratch<CAP> w;
     const int ray = blockIdx.x, lane = threadIdx.x;
     const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
     const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
@@ -134,9 +140,9 @@ __global__ __launch_bounds__(64) void sampler_step_kernel(const StepArgs a) {
         if constexpr (MERGE) {
             // all four global reads of the step are requested before anything waits on them: one memory round trip, not two (the
             // kernel is one latency chain per ray - 23 k cycles, of which this block was 5.4-6.8 k)
-            float uu[(MAXS + 63) / 64];
+            float uu[(CAP + 63) / 64];
 #pragma unroll
-            for (int i = 0; i < (MAXS + 63) / 64; ++i) {
+            for (int i = 0; i < (CAP + 63) / 64; ++i) {
                 const int e = lane + 64 * i;
                 uu[i] = (e < n) ? a.udf[(size_t)ray * n + e] : ((e < n + m) ? a.udf_prev[(size_t)ray * m + (e - n)] : 0.f);
             }
@@ -145,7 +151,7 @@ __global__ __launch_bounds__(64) void sampler_step_kernel(const StepArgs a) {
             __syncthreads();
             const size_t ob = (size_t)ray * (n + m);
 #pragma unroll
-            for (int i = 0; i < (MAXS + 63) / 64; ++i) {
+            for (int i = 0; i < (CAP + 63) / 64; ++i) {
                 const int e = lane + 64 * i;
                 if (e < n + m) {
                     float v;
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(256) void composite_reduce_kernel(const float* part
 // the forward quantities are recomputed with the forward kernel's own expressions so that every clip / mask decision is
 // the one the forward took; the two cumprod adjoints are exclusive suffix sums (fp64 wave scans).
 //
-// Round 5: the ray lives in REGISTERS - lane l holds the C = 1, 2 or 4 consecutive samples [l C, (l+1) C) (the chunking wave_scan uses,
+// Round 5: the ray lives in REGISTERS - lane l holds the C = 1, 2, 4 (8, 16: S > 256) consecutive samples [l C, (l+1) C) (the chunking wave_scan uses,
 // so the two prefix products are bit-identical to the forward kernel's), every input is fetched by one burst of loads at the top (one
 // memory round trip instead of one per pass and loop iteration), neighbours (z, true_cos of sample e+1) come over the DPP network, and
 // the sigmoids / exponentials of the forward recomputation are kept for the adjoint instead of being evaluated a second time.  No LDS,
@@ -270,6 +276,10 @@ __device__ __forceinline__ void ray_suffix_sum(const float (&in)[C], const bool 
 #pragma unroll
     for (int i = C - 1; i >= 0; --i) { out[i] = (float)run; if (ok[i]) run += (double)in[i]; }
 }
+
+// a copy of v the compiler cannot prove equal to v: an expression recomputed from it is evaluated again instead of being merged with (and kept
+// alive from) its first evaluation on v.  No instruction is emitted.
+__device__ __forceinline__ float opaque_f(float v) { asm volatile("" : "+v"(v)); return v; }
 
 // sdf2alpha (the forward's expressions, bit for bit) that also hands back what its adjoint needs
 struct Sdf2AlphaKeep { float val, pc, nc, den, en, ep; };
@@ -336,12 +346,17 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
     const float c_ns = a.d_ge_ns ? a.d_ge_ns[0] / (a.scalars[6] + 1e-5f) : 0.f;
     const bool anneal = a.anneal != 0;
 
-    float gi[C];                               // normalised cosine: |g| + 1e-5 (composite_ray's expression)
+    // C >= 8 (S > 256): the per-sample pieces of the forward recomputation that the adjoint reuses (udf2logistic's, sdf2alpha_keep's, |g| + 1e-5)
+    // do not all stay in registers next to the rest (C = 16 spilled to scratch): they are evaluated a second time where the adjoint needs them -
+    // same expressions on the same inputs, same bits.  C <= 4 keeps them in arrays, as it always did.
+    constexpr bool KEEP = C <= 4;
+    float gi[KEEP ? C : 1];                    // normalised cosine: |g| + 1e-5 (composite_ray's expression)
     if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
 #pragma unroll
         for (int i = 0; i < C; ++i) {
-            gi[i] = FADD(sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
-            tc[i] = FADD(FADD(FMUL(dx, FDIV(gx[i], gi[i])), FMUL(dy, FDIV(gy[i], gi[i]))), FMUL(dz, FDIV(gz[i], gi[i])));
+            const int k = KEEP ? i : 0;
+            gi[k] = FADD(sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
+            tc[i] = FADD(FADD(FMUL(dx, FDIV(gx[i], gi[k])), FMUL(dy, FDIV(gy[i], gi[k]))), FMUL(dz, FDIV(gz[i], gi[k])));
         }
     } else if constexpr (MODE == EMAP_RENDER_UNBIASED) {
 #pragma unroll
@@ -349,33 +364,38 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
     }
     z[C] = dpp_next_f(0.f, z[0]);       // sample e+1 of a lane's last sample is the next lane's first
     if constexpr (MODE != EMAP_RENDER_PLAIN) tc[C] = dpp_next_f(0.f, tc[0]);
-    float dists[C], E[C], opE[C], raw[C], eq[C], ain[C], av[C], vpr[C];
+    float dists[C], E[KEEP ? C : 1], opE[KEEP ? C : 1], raw[KEEP ? C : 1], eq[KEEP ? C : 1], ain[C], av[C], vpr[C];
+    constexpr bool PLAIN_NOKEEP = MODE == EMAP_RENDER_PLAIN && !KEEP;
+    float aocc[PLAIN_NOKEEP ? C : 1];          // PLAIN, C >= 8: alpha = 1 - eq, taken while eq of the sample is at hand
 #pragma unroll
     for (int i = 0; i < C; ++i) {
+        const int k = KEEP ? i : 0;
         dists[i] = last[i] ? sd : FSUB(z[i + 1], z[i]);
-        E[i] = expf(FMUL(-beta_, u[i]));                        // udf2logistic1(u, beta) with its pieces kept
-        opE[i] = FADD(1.0f, E[i]);
-        raw[i] = FDIV(FMUL(beta_, E[i]), FMUL(opE[i], opE[i]));
-        eq[i] = expf(FMUL(FMUL(-relu_(raw[i]), gamma_), dists[i]));            // 1 - alpha_occ up to rounding
+        E[k] = expf(FMUL(-beta_, u[i]));                        // udf2logistic1(u, beta) with its pieces kept
+        opE[k] = FADD(1.0f, E[k]);
+        raw[k] = FDIV(FMUL(beta_, E[k]), FMUL(opE[k], opE[k]));
+        eq[k] = expf(FMUL(FMUL(-relu_(raw[k]), gamma_), dists[i]));            // 1 - alpha_occ up to rounding
+        if constexpr (PLAIN_NOKEEP) aocc[i] = FSUB(1.0f, eq[0]);
         if constexpr (MODE != EMAP_RENDER_PLAIN) {
             const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);
-            const float occ = FSUB(1.0f, eq[i]);
+            const float occ = FSUB(1.0f, eq[k]);
             ain[i] = FADD(FSUB(1.0f, occ), FMUL(a.flip_sat, vis_mask));
             av[i] = FADD(clipf(ain[i], 0.0f, 1.0f), 1e-7f);
         }
     }
     if constexpr (MODE != EMAP_RENDER_PLAIN) ray_prefix_prod<C>(av, ok, vpr);           // raw (unclipped) visibility product
-    Sdf2AlphaKeep kp[C], km[C];
+    Sdf2AlphaKeep kp[KEEP ? C : 1], km[KEEP ? C : 1];
     float ap[C], am[C], vp[C], alpha[C], om[C], T[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         if constexpr (MODE == EMAP_RENDER_PLAIN) {
-            alpha[i] = FSUB(1.0f, eq[i]);                       // composite_ray's alpha, bit for bit
+            if constexpr (PLAIN_NOKEEP) alpha[i] = aocc[i];
+            else alpha[i] = FSUB(1.0f, eq[i]);                  // composite_ray's alpha, bit for bit
         } else {
             vp[i] = clipf(vpr[i], 0.0f, 1.0f);
             const float tcn = -fabsf(tc[i]);
-            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, a.car, kp[i]);
-            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, a.car, km[i]);
+            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, a.car, kp[KEEP ? i : 0]);
+            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, a.car, km[KEEP ? i : 0]);
             alpha[i] = FADD(FMUL(ap[i], vp[i]), FMUL(am[i], FSUB(1.0f, vp[i])));
         }
         om[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
@@ -402,6 +422,19 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
     float mx_u = 0.f, mx_g = 0.f;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
+        const int k = KEEP ? i : 0;
+        float uk = u[i];
+        if constexpr (!KEEP) {
+            uk = opaque_f(u[i]);
+            E[0] = expf(FMUL(-beta_, uk));
+            opE[0] = FADD(1.0f, E[0]);
+            raw[0] = FDIV(FMUL(beta_, E[0]), FMUL(opE[0], opE[0]));
+            eq[0] = expf(FMUL(FMUL(-relu_(raw[0]), gamma_), dists[i]));
+            if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
+                const float gxk = opaque_f(gx[i]);
+                gi[0] = FADD(sqrtf(FADD(FADD(FMUL(gxk, gxk), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
+            }
+        }
         // occlusion branch: a_i = clip(1 - occ + fs*vm) + 1e-7; plain: alpha = occ itself
         float docc;
         if constexpr (MODE == EMAP_RENDER_PLAIN) {
@@ -410,19 +443,23 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
             const float da = suf[i] * __builtin_amdgcn_rcpf(av[i]);
             docc = (ain[i] >= 0.f && ain[i] <= 1.f) ? -da : 0.f;
         }
-        const float dq = docc * eq[i];
-        const float r1 = __builtin_amdgcn_rcpf(opE[i]), r2 = r1 * r1;
-        const float draw = (raw[i] > 0.f) ? dq * gamma_ * dists[i] : 0.f;
-        const float fE = (1.0f - E[i]) * r2 * r1;
-        float du = draw * (-beta_ * beta_ * E[i] * fE);
-        const float pb = draw * (E[i] * r2 - beta_ * u[i] * E[i] * fE), pg = dq * relu_(raw[i]) * dists[i];
+        const float dq = docc * eq[k];
+        const float r1 = __builtin_amdgcn_rcpf(opE[k]), r2 = r1 * r1;
+        const float draw = (raw[k] > 0.f) ? dq * gamma_ * dists[i] : 0.f;
+        const float fE = (1.0f - E[k]) * r2 * r1;
+        float du = draw * (-beta_ * beta_ * E[k] * fE);
+        const float pb = draw * (E[k] * r2 - beta_ * u[i] * E[k] * fE), pg = dq * relu_(raw[k]) * dists[i];
         // alpha branch
         float dtc = 0.f, d_is = 0.f;
         if constexpr (MODE != EMAP_RENDER_PLAIN) {
             const float tabs = fabsf(tc[i]);
             float s1, t1, i1, s2, t2, i2;
-            sdf2alpha_bwd(kp[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * vp[i], s1, t1, i1);
-            sdf2alpha_bwd(km[i], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
+            if constexpr (!KEEP) {
+                (void)sdf2alpha_keep(uk, -tabs, dists[i], inv_s_, anneal, a.car, kp[0]);
+                (void)sdf2alpha_keep(-uk, -tabs, dists[i], inv_s_, anneal, a.car, km[0]);
+            }
+            sdf2alpha_bwd(kp[k], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * vp[i], s1, t1, i1);
+            sdf2alpha_bwd(km[k], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
             du += s1 - s2;
             d_is = i1 + i2;
             dtc = (t1 + t2) * ((tc[i] > 0.f) ? 1.f : ((tc[i] < 0.f) ? -1.f : 0.f));
@@ -436,7 +473,7 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
         float ogx = dtc * dx + coef * gx[i], ogy = dtc * dy + coef * gy[i], ogz = dtc * dz + coef * gz[i];
         if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
             // true_cos = d . g / (|g| + eps): its gradient in g is d / (|g| + eps) - (d . g) g / (|g| (|g| + eps)^2)
-            const float rgi = __builtin_amdgcn_rcpf(gi[i]);
+            const float rgi = __builtin_amdgcn_rcpf(gi[k]);
             const float k2 = (gm > 0.f) ? (dx * gx[i] + dy * gy[i] + dz * gz[i]) * rgi * rgi * __builtin_amdgcn_rcpf(gm) : 0.f;
             ogx = dtc * (dx * rgi - k2 * gx[i]) + coef * gx[i];
             ogy = dtc * (dy * rgi - k2 * gy[i]) + coef * gy[i];
@@ -541,58 +578,70 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* x, long long P,
 // ---------------------------------------------------------------------------------------------
 int launch_sample_pdf(const float* bins, const float* weights, int N, int n, int m, float* samples, int64_t* inds,
                       int32_t* err, hipStream_t st, const float* u) {
-    if (n < 2 || n > MAXS || m < 1 || m > MAXS) { set_error("sample_pdf: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
+    if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("sample_pdf: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    hipLaunchKernelGGL(sample_pdf_kernel, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u);
+    // the samples go straight to global memory: only the n bins take LDS
+    if (n <= MAXS) hipLaunchKernelGGL(sample_pdf_kernel<MAXS>, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u);
+    else hipLaunchKernelGGL(sample_pdf_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u);
     return check_launch("sample_pdf");
 }
 
 int launch_upsample(const float* rays_o, const float* rays_d, const float* z, const float* udf, int N, int n, int m,
                     const float* sample_dist, float inv_s, float beta, float gamma, float* z_new, int64_t* inds,
                     int32_t* err, hipStream_t st) {
-    if (n < 2 || n > MAXS || m < 1 || m > MAXS) { set_error("upsample_step: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
+    if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("upsample_step: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    hipLaunchKernelGGL(upsample_kernel, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta,
-                       gamma, z_new, inds, err);
+    if (n <= MAXS) hipLaunchKernelGGL(upsample_kernel<MAXS>, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta,
+                                      gamma, z_new, inds, err);
+    else hipLaunchKernelGGL(upsample_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta,
+                            gamma, z_new, inds, err);
     return check_launch("upsample_step");
 }
 
 int launch_upsample_plain(const float* z, const float* udf, int N, int n, int m, const float* sample_dist, float beta, float gamma, float* z_new,
                           int64_t* inds, int32_t* err, hipStream_t st) {
-    if (n < 2 || n > MAXS || m < 1 || m > MAXS) { set_error("upsample_step_plain: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
+    if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("upsample_step_plain: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    hipLaunchKernelGGL(upsample_plain_kernel, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
+    if (n <= MAXS) hipLaunchKernelGGL(upsample_plain_kernel<MAXS>, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
+    else hipLaunchKernelGGL(upsample_plain_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
     return check_launch("upsample_step_plain");
 }
 
 int launch_merge(const float* z, const float* z_new, const float* udf, const float* udf_new, int N, int n, int m,
                  float* z_out, float* udf_out, int64_t* perm, hipStream_t st) {
-    if (n < 1 || n > MAXS || m < 1 || m > MAXS) { set_error("merge_sorted: n=%d m=%d out of range (max %d)", n, m, MAXS); return EMAP_E_INVALID; }
+    if (n < 1 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("merge_sorted: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (udf_out && (!udf || !udf_new)) { set_error("merge_sorted: udf_out needs udf and udf_new"); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    hipLaunchKernelGGL(merge_kernel, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
+    if (n <= MAXS && m <= MAXS) hipLaunchKernelGGL(merge_kernel<MAXS>, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
+    else hipLaunchKernelGGL(merge_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
     return check_launch("merge_sorted");
+}
+
+template <int CAP>
+static void launch_sampler_step_t(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain) {
+    if (plain) {            // use_unbias_render=False: up_sample_no_occ_aware in every step
+        if (coarse) {
+            if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, false, true>), dim3(a.N), dim3(64), 0, st, a);
+        } else {
+            if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, true, true>), dim3(a.N), dim3(64), 0, st, a);
+            else hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
+        }
+    } else if (coarse) {
+        if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, false>), dim3(a.N), dim3(64), 0, st, a);
+    } else {
+        if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, false>), dim3(a.N), dim3(64), 0, st, a);
+    }
 }
 
 int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain) {
     const int n_out = a.n + (coarse ? 0 : a.m);
-    if (a.n < 2 || n_out + a.m > MAXS || a.m < 1) { set_error("sampler_step: n=%d m=%d out of range (max %d)", a.n, a.m, MAXS); return EMAP_E_INVALID; }
+    if (a.n < 2 || n_out + a.m > MAXS_WIDE || a.m < 1) { set_error("sampler_step: n=%d m=%d out of range (max %d)", a.n, a.m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (a.N <= 0) return EMAP_OK;
-    if (plain) {            // use_unbias_render=False: up_sample_no_occ_aware in every step
-        if (coarse) {
-            if (tail) hipLaunchKernelGGL((sampler_step_kernel<true, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL((sampler_step_kernel<true, false, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        } else {
-            if (tail) hipLaunchKernelGGL((sampler_step_kernel<false, true, true, true>), dim3(a.N), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL((sampler_step_kernel<false, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        }
-    } else if (coarse) {
-        if (tail) hipLaunchKernelGGL((sampler_step_kernel<true, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((sampler_step_kernel<true, false, false>), dim3(a.N), dim3(64), 0, st, a);
-    } else {
-        if (tail) hipLaunchKernelGGL((sampler_step_kernel<false, true, true>), dim3(a.N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((sampler_step_kernel<false, true, false>), dim3(a.N), dim3(64), 0, st, a);
-    }
+    if (n_out + a.m <= MAXS) launch_sampler_step_t<MAXS>(coarse, tail, a, st, plain);
+    else launch_sampler_step_t<MAXS_WIDE>(coarse, tail, a, st, plain);
     return check_launch("sampler_step");
 }
 
@@ -610,7 +659,7 @@ int fill_composite_args(const float* rays_o, const float* rays_d, const float* z
                         float gamma, float car, int anneal, float flip_sat, float near_surface, float sparse_scale,
                         float background, int has_bg, const float* var_p, const float* beta_p, const float* gamma_p,
                         float beta_min, const EmapCompositeOut* out, float* partials, CompositeArgs* pa) {
-    if (S < 1 || S > MAXS) { set_error("composite: S=%d out of range (max %d)", S, MAXS); return EMAP_E_INVALID; }
+    if (S < 1 || S > MAXS_WIDE) { set_error("composite: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (!out || !partials) { set_error("composite: out/partials must not be null"); return EMAP_E_INVALID; }
     if (var_p && (!beta_p || !gamma_p)) { set_error("composite: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
     CompositeArgs& a = *pa;
@@ -641,14 +690,20 @@ int launch_composite(const float* rays_o, const float* rays_d, const float* z, c
     if (mode == EMAP_RENDER_PLAIN) {
         if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
         else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 256) hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 512) hipLaunchKernelGGL((composite_kernel<8, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_kernel<16, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
     } else if (mode == EMAP_RENDER_UNBIASED_NORMCOS) {
         if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
         else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 256) hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 512) hipLaunchKernelGGL((composite_kernel<8, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_kernel<16, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
     } else if (S <= 64) hipLaunchKernelGGL(composite_kernel<1>, dim3(N), dim3(64), 0, st, a);
     else if (S <= 128) hipLaunchKernelGGL(composite_kernel<2>, dim3(N), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(composite_kernel<4>, dim3(N), dim3(64), 0, st, a);
+    else if (S <= 256) hipLaunchKernelGGL(composite_kernel<4>, dim3(N), dim3(64), 0, st, a);
+    else if (S <= 512) hipLaunchKernelGGL(composite_kernel<8>, dim3(N), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(composite_kernel<16>, dim3(N), dim3(64), 0, st, a);
     if (out->scalars) hipLaunchKernelGGL(composite_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, out->scalars, err, a);
     return check_launch("composite");
 }
@@ -657,7 +712,7 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
                          const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams* p,
                          const EmapCompositeGrads* gr, float* d_udf, float* d_grad3, float* partials, uint32_t* absmax,
                          hipStream_t st) {
-    if (S < 1 || S > MAXS) { set_error("composite_bwd: S=%d out of range (max %d)", S, MAXS); return EMAP_E_INVALID; }
+    if (S < 1 || S > MAXS_WIDE) { set_error("composite_bwd: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
     CompositeBwdArgs a;
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
@@ -674,14 +729,20 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
     if (p->render_mode == EMAP_RENDER_PLAIN) {
         if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
         else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 256) hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 512) hipLaunchKernelGGL((composite_bwd_kernel<8, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_bwd_kernel<16, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
     } else if (p->render_mode == EMAP_RENDER_UNBIASED_NORMCOS) {
         if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
         else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 256) hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else if (S <= 512) hipLaunchKernelGGL((composite_bwd_kernel<8, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((composite_bwd_kernel<16, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
     } else if (S <= 64) hipLaunchKernelGGL(composite_bwd_kernel<1>, dim3(N), dim3(64), 0, st, a);
     else if (S <= 128) hipLaunchKernelGGL(composite_bwd_kernel<2>, dim3(N), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(composite_bwd_kernel<4>, dim3(N), dim3(64), 0, st, a);
+    else if (S <= 256) hipLaunchKernelGGL(composite_bwd_kernel<4>, dim3(N), dim3(64), 0, st, a);
+    else if (S <= 512) hipLaunchKernelGGL(composite_bwd_kernel<8>, dim3(N), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(composite_bwd_kernel<16>, dim3(N), dim3(64), 0, st, a);
     hipLaunchKernelGGL(composite_bwd_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, a, gr->d_variance, gr->d_beta,
                        gr->d_gamma, gr->grad_scale, gr->accumulate);
     return check_launch("composite_bwd");

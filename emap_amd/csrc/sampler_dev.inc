@@ -2,7 +2,13 @@
 // separately rounded arithmetic, fp64 wave scans on the DPP network, sdf2alpha / udf2logistic, sample_pdf's inverse-CDF look-up, the
 // register-resident up_sample_unbias body, the stable rank-merge.  Included inside namespace emap.
 #pragma once
-constexpr int MAXS = 256;  // max samples per ray handled by the per-ray kernels
+// Samples per ray: the per-ray kernels of sampler.hip come in two LDS capacities, MAXS (the one every shape up to 256 samples runs, with
+// the LDS footprint and occupancy it always had) and MAXS_WIDE (= EMAP_MAX_SAMPLES_PER_RAY: 257 ... 1024 samples, chunks of C = 8 or 16
+// samples per lane).  The fused importance-sampling kernel (udf_mlp_kernel.inc, IS_MAXS) and the compositing tail fused into the
+// reverse-sweep kernel (udf_mlp_rev32.inc) stay at 256.
+constexpr int MAXS = 256;
+constexpr int MAXS_WIDE = EMAP_MAX_SAMPLES_PER_RAY;
+static_assert(MAXS_WIDE == 1024, "the C = 8 / 16 dispatches below cover 1024 samples per ray");
 
 // Separately rounded fp32 arithmetic - what the reference's elementwise torch ops do (one kernel per op: a * b + c is never an fma there).
 // Round 6 finding: HIP's __fmul_rn / __fadd_rn are plain `x * y` / `x + y` in a header compiled under hipcc's default -ffp-contract=fast, so
@@ -56,7 +62,7 @@ __device__ __forceinline__ double readlane63_d(double v) {
 }
 __device__ __forceinline__ double wave_sum_d(double v) { return readlane63_d(wave_scan_incl_d<false>(v)); }
 
-// Exclusive prefix product (MUL=true) or inclusive prefix sum (MUL=false) over n <= MAXS values in
+// Exclusive prefix product (MUL=true) or inclusive prefix sum (MUL=false) over n <= MAXS_WIDE values in
 // LDS, fp64 accumulation, fp32 outputs.  Each lane owns a contiguous chunk of C = ceil(n/64) values.
 //   MUL : out[i] = prod_{k<i} in[k]   (cumprod(cat([1, x]))[:-1], udf_renderer_blending.py:308-319)
 //   SUM : out[i] = sum_{k<=i} in[k]   (cumsum, :75)
@@ -200,7 +206,8 @@ __device__ __forceinline__ void sample_pdf_wave(const float* bins, const float* 
 // ---------------------------------------------------------------------------------------------
 // up_sample_unbias (udf_renderer_blending.py:228-353) -> z_new (N,m)
 // ---------------------------------------------------------------------------------------------
-struct UpsampleScratch { float a[MAXS], d[MAXS + 1]; };      // a: staging of the merge, d: cdf of sample_pdf
+template <int CAP>
+struct UpsampleScratch { float a[CAP], d[CAP + 1]; };        // a: staging of the merge, d: cdf of sample_pdf
 
 // the whole of up_sample_unbias on the LDS lists s_z, s_u (n entries, filled and synchronised by the caller); the m new samples go to
 // samples_out (global or LDS), their searchsorted indices to inds_out (may be null).
@@ -208,9 +215,9 @@ struct UpsampleScratch { float a[MAXS], d[MAXS + 1]; };      // a: staging of th
 // holds the C consecutive samples [l C, (l+1) C) and the intervals that start at them, neighbours come over the DPP network, the three scans
 // run on the same chunks as the LDS scans did.  Same expressions, same results (the fp64 sum of the weights is exact in any order: floats
 // between 1e-5 and ~1); rounds 1-4 made eight passes over six LDS arrays with a barrier after each.
-template <int C>
+template <int C, int CAP>
 __device__ __forceinline__ void upsample_body_c(float ox, float oy, float oz, float dx, float dy, float dz, float sd, const float* s_z,
-                                                const float* s_u, UpsampleScratch& w, int n, int m, float inv_s, float beta, float gamma,
+                                                const float* s_u, UpsampleScratch<CAP>& w, int n, int m, float inv_s, float beta, float gamma,
                                                 int lane, float* samples_out, int64_t* inds_out, int32_t* err) {
     float z[C + 1], u[C + 1], rad[C + 1], tc[C];
     bool ok[C], oki[C];            // sample e exists / interval [e, e+1] exists
@@ -280,12 +287,22 @@ __device__ __forceinline__ void upsample_body_c(float ox, float oy, float oz, fl
     sample_pdf_search(s_z, w.d, n, m, lane, samples_out, inds_out, err, nullptr);
 }
 
+// n <= CAP samples: lane chunks of C = ceil(n / 64) rounded up to a power of two; C = 8 and 16 only in the MAXS_WIDE instantiations
+template <int CAP>
 __device__ __forceinline__ void upsample_body(float ox, float oy, float oz, float dx, float dy, float dz, float sd, const float* s_z,
-                                              const float* s_u, UpsampleScratch& w, int n, int m, float inv_s, float beta, float gamma,
+                                              const float* s_u, UpsampleScratch<CAP>& w, int n, int m, float inv_s, float beta, float gamma,
                                               int lane, float* samples_out, int64_t* inds_out, int32_t* err) {
-    if (n <= 64) upsample_body_c<1>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
-    else if (n <= 128) upsample_body_c<2>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
-    else upsample_body_c<4>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+    if constexpr (CAP <= MAXS) {
+        if (n <= 64) upsample_body_c<1>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 128) upsample_body_c<2>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else upsample_body_c<4>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+    } else {
+        if (n <= 64) upsample_body_c<1>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 128) upsample_body_c<2>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 256) upsample_body_c<4>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 512) upsample_body_c<8>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+        else upsample_body_c<16>(ox, oy, oz, dx, dy, dz, sd, s_z, s_u, w, n, m, inv_s, beta, gamma, lane, samples_out, inds_out, err);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -294,8 +311,8 @@ __device__ __forceinline__ void upsample_body(float ox, float oy, float oz, floa
 // upsample_body_c's register layout and scan chunks without the occlusion terms: the weights of sample_pdf are the n - 1 interval
 // opacities alpha_occ = 1 - exp(-relu(udf2logistic(udf, beta)) gamma dists) themselves (:954-963) - no visibility product, no cosine,
 // no mid-point udf, no transmittance; inv_s and the sphere test of the reference are unused there.
-template <int C>
-__device__ __forceinline__ void upsample_plain_body_c(float sd, const float* s_z, const float* s_u, UpsampleScratch& w, int n, int m,
+template <int C, int CAP>
+__device__ __forceinline__ void upsample_plain_body_c(float sd, const float* s_z, const float* s_u, UpsampleScratch<CAP>& w, int n, int m,
                                                       float beta, float gamma, int lane, float* samples_out, int64_t* inds_out,
                                                       int32_t* err) {
     float z[C + 1], u[C], av[C], sb[C];
@@ -327,12 +344,20 @@ __device__ __forceinline__ void upsample_plain_body_c(float sd, const float* s_z
     sample_pdf_search(s_z, w.d, n, m, lane, samples_out, inds_out, err, nullptr);
 }
 
-template <int = 0>
-__device__ __forceinline__ void upsample_plain_body(float sd, const float* s_z, const float* s_u, UpsampleScratch& w, int n, int m,
+template <int CAP>
+__device__ __forceinline__ void upsample_plain_body(float sd, const float* s_z, const float* s_u, UpsampleScratch<CAP>& w, int n, int m,
                                                     float beta, float gamma, int lane, float* samples_out, int64_t* inds_out, int32_t* err) {
-    if (n <= 64) upsample_plain_body_c<1>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
-    else if (n <= 128) upsample_plain_body_c<2>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
-    else upsample_plain_body_c<4>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+    if constexpr (CAP <= MAXS) {
+        if (n <= 64) upsample_plain_body_c<1>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 128) upsample_plain_body_c<2>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else upsample_plain_body_c<4>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+    } else {
+        if (n <= 64) upsample_plain_body_c<1>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 128) upsample_plain_body_c<2>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 256) upsample_plain_body_c<4>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else if (n <= 512) upsample_plain_body_c<8>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+        else upsample_plain_body_c<16>(sd, s_z, s_u, w, n, m, beta, gamma, lane, samples_out, inds_out, err);
+    }
 }
 
 // stable rank-merge of the sorted LDS lists s_z[n] (old) and s_n[m] (new): element e of cat([old, new]) goes to rank(e)

@@ -88,9 +88,10 @@ struct MlpArgs {
 #define EMAP_IS_FUSED_MAX_RAYS 512
 #endif
 constexpr int IS_M = 16;       // columns of a ray's tile; the step's m <= IS_M new samples occupy the first m
+constexpr int IS_MAXS = 256;   // samples per ray of the fused kernel (its LDS per ray); longer rays take the chain of per-ray and MLP launches
 struct IsRay {
-    float z[MAXS], u[MAXS], nz[IS_M], nu[IS_M];
-    UpsampleScratch w;
+    float z[IS_MAXS], u[IS_MAXS], nz[IS_M], nu[IS_M];
+    UpsampleScratch<IS_MAXS> w;
 };
 
 // shader clock of a launch: s_memtime counts shader cycles, s_memrealtime a constant 100 MHz (scripts/probes/clock_probe.hip)
@@ -413,16 +414,16 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
             }
         } else {
             // cat_z_vals of the previous step (:355-377): stable rank-merge of (z, u)[n] with the m new samples and their udf
-            float uu[(MAXS + 63) / 64];
+            float uu[(IS_MAXS + 63) / 64];
 #pragma unroll
-            for (int i = 0; i < (MAXS + 63) / 64; ++i) {
+            for (int i = 0; i < (IS_MAXS + 63) / 64; ++i) {
                 const int e = lane + 64 * i;
                 uu[i] = (e < n) ? R.u[e] : ((e < n + m) ? R.nu[e - n] : 0.f);
             }
             for (int e = lane; e < n; e += 64) R.w.a[e] = R.z[e];
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
-            for (int i = 0; i < (MAXS + 63) / 64; ++i) {
+            for (int i = 0; i < (IS_MAXS + 63) / 64; ++i) {
                 const int e = lane + 64 * i;
                 if (e < n + m) {
                     float v;
@@ -833,7 +834,7 @@ template <int MODE>
 int launch_is_mode(const NetLayout& L, const void* packed, const IsLaunch& q, hipStream_t st, int32_t* err) {
     // 1 <= m <= 16 new samples per ray and step: one 16-column tile of the MLP pass per ray, columns m .. 15 masked (round 6: the reference's
     // own default n_importance = 50 in 5 steps is m = 10, confs/ABC.conf:108-111)
-    if (q.m < 1 || q.m > IS_M || q.steps < 1 || q.Sc < 2 || q.Sc + q.steps * q.m > MAXS) return IS_NOT_FUSED;
+    if (q.m < 1 || q.m > IS_M || q.steps < 1 || q.Sc < 2 || q.Sc + q.steps * q.m > IS_MAXS) return IS_NOT_FUSED;
     const int64_t P = (int64_t)q.N * IS_M;
     auto tiles = [&](int pts) { return (P + pts - 1) / pts; };
     // from 2048 rays on the chain runs 64-point tiles (two workgroups per CU at 80 KiB each leave no LDS for the rays); the fused kernel keeps its

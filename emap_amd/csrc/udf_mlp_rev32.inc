@@ -1123,6 +1123,10 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
         set_error("udf_mlp_rev32: the fused compositing tail needs P = N * S points written to the buffers it composites from");
         return EMAP_E_INVALID;
     }
+    if (fuse && fuse->c.S > COMP_FUSED_MAX_S) {
+        set_error("udf_mlp_rev32: the fused compositing tail takes at most %d samples per ray (S = %d)", COMP_FUSED_MAX_S, fuse->c.S);
+        return EMAP_E_INVALID;
+    }
     if (a.n_tiles <= 0) return EMAP_OK;
     const int wg_cap = (NW == 8) ? REV_MAX_WG / 3 : (REV_MAX_WG * 2) / 3;   // resident workgroups: one (8 waves, 128 points) or two per CU
     const int grid = a.n_tiles < wg_cap ? a.n_tiles : wg_cap;

@@ -16,6 +16,16 @@ import numpy as np
 import torch
 
 
+def default_launch_rays(S):
+    """Rays per render call of ``render_image(launch_rays=None)`` at S samples per ray: 2**18 up to S = 256 - one call for any image up
+    to 512 x 512; the workspace of a call is ~2 KiB per ray at S = 128 and grows linearly in S - and beyond that 2**18 * 256 / S rounded
+    down to a power of two, which keeps a call's workspace at most what it is at S = 256."""
+    if S <= 256:
+        return 1 << 18
+    n = (1 << 18) * 256 // S
+    return 1 << (n.bit_length() - 1)
+
+
 def render_image(renderer, rays_o, rays_d, near, far, depth_scale, batch_size, cos_anneal_ratio=None, background_rgb=None,
                  launch_rays=None, to_numpy=True):
     """rays_o, rays_d (H,W,3) or (n,3); depth_scale (H,W,1) or (n,1).  Returns {"edge": (n,1), "depth": (n,1),
@@ -25,7 +35,7 @@ def render_image(renderer, rays_o, rays_d, near, far, depth_scale, batch_size, c
     ds = depth_scale.reshape(-1, 1)
     n = ro.shape[0]
     if launch_rays is None:
-        launch_rays = 1 << 18      # one call for any image up to 512 x 512; the workspace of a call is ~2 KiB per ray
+        launch_rays = default_launch_rays(renderer.samples_per_ray)
     # jitter: one draw per reference chunk, in the reference's order (render() :718-720 with perturb_overwrite = -1)
     t_rand = None
     if renderer.perturb > 0:

@@ -66,6 +66,10 @@ extern "C" {
 
 #define EMAP_MAX_LIN 12
 
+/* samples per ray, S = n_samples + up_sample_steps * (n_importance / up_sample_steps), that emap_render_fwd, emap_render_bwd[_staged],
+ * the per-ray sampler calls (n, m and n + m) and the compositing calls accept; larger shapes are EMAP_E_INVALID */
+#define EMAP_MAX_SAMPLES_PER_RAY 1024
+
 /* Constructor arguments of UDFNetwork that the kernels need (udf_model.py:8-21,24-45). */
 typedef struct EmapNetConfig {
     int32_t d_hidden;   /* 128 or 256                                   */
@@ -118,7 +122,9 @@ int emap_embed(const float* x, int64_t P, int multires, float* pe, void* stream)
  *                      (no cosine, no sphere test): inv_s is not an argument, rays_o / rays_d are accepted and may be NULL
  * emap_merge_sorted  : the cat + sort + gather of cat_z_vals   (udf_renderer_blending.py:361-375)
  *                      z (N,n), z_new (N,m) [, udf (N,n), udf_new (N,m)] -> z_out, udf_out (N,n+m),
- *                      perm int64 (N,n+m) (may be NULL); udf/udf_new/udf_out may be NULL (last=True) */
+ *                      perm int64 (N,n+m) (may be NULL); udf/udf_new/udf_out may be NULL (last=True)
+ * n and m of all four go up to EMAP_MAX_SAMPLES_PER_RAY (1024); larger is EMAP_E_INVALID, checked before the N <= 0 return.  Up to 256 the
+ * kernels keep their LDS footprint; above, wider instantiations (lane chunks of 8 or 16 samples) run. */
 int emap_sample_pdf(const float* bins, const float* weights, int N, int n, int m, float* samples,
                     int64_t* inds, int32_t* err_flags, void* stream);
 /* emap_sample_pdf_u : the same with the caller's uniform draws u (N, m) instead of the deterministic grid: sample_pdf(det=False)
@@ -172,7 +178,9 @@ int emap_composite_fwd(const float* rays_o, const float* rays_d, const float* z,
  * False, use_norm_grad_for_cosine True or False): coarse z_vals (:705-720) -> importance_sample (:802-841) ->
  * render_core (:418-677).  near/far are (N) device arrays; t_rand (N) may be NULL (no jitter).
  * The whole sequence is enqueued on `stream` with no host synchronisation.
- * z_vals (N,S), udf (N,S), grad3 (N,S,3) are outputs as well (S = n_samples + n_importance//steps*steps). */
+ * z_vals (N,S), udf (N,S), grad3 (N,S,3) are outputs as well (S = n_samples + n_importance//steps*steps).
+ * S <= EMAP_MAX_SAMPLES_PER_RAY (1024), also for emap_composite_fwd[_p] / emap_composite_bwd and emap_render_bwd[_staged]; above 256 samples
+ * the fused importance sampling and the fused compositing tail do not apply (the chain and the separate launches run, same results). */
 typedef struct EmapRenderParams {
     int32_t n_rays;
     int32_t n_samples;
