@@ -46,46 +46,6 @@ struct ProfScope {   // records a HIP event pair around one launch on its stream
     ~ProfScope() { if (on) { (void)hipEventRecord(g_prof_ev[k][g_prof_n[k]][1], st); ++g_prof_n[k]; } }
 };
 
-int launch_sample_pdf(const float*, const float*, int, int, int, float*, int64_t*, int32_t*, hipStream_t, const float* u = nullptr);
-int launch_upsample(const float*, const float*, const float*, const float*, int, int, int, const float*, float, float,
-                    float, float*, int64_t*, int32_t*, hipStream_t);
-int launch_upsample_plain(const float*, const float*, int, int, int, const float*, float, float, float*, int64_t*, int32_t*, hipStream_t);
-int launch_merge(const float*, const float*, const float*, const float*, int, int, int, float*, float*, int64_t*,
-                 hipStream_t);
-int launch_coarse(const float*, const float*, const float*, int, int, float*, float*, hipStream_t);
-int launch_composite(const float*, const float*, const float*, const float*, const float*, const float*, int, int,
-                     const float*, float, float, float, float, int, float, float, float, float, int, const float*,
-                     const float*, const float*, float, const EmapCompositeOut*, float*, int32_t*, hipStream_t, int mode = EMAP_RENDER_UNBIASED);
-int fill_composite_args(const float*, const float*, const float*, const float*, const float*, const float*, int, int,
-                        const float*, float, float, float, float, int, float, float, float, float, int, const float*,
-                        const float*, const float*, float, const EmapCompositeOut*, float*, CompositeArgs*);
-int launch_composite_reduce(const CompositeArgs&, int32_t*, hipStream_t);
-int launch_embed(const float*, int64_t, int, float*, hipStream_t);
-void linspace_host(float, float, int, float*);
-int launch_sample_rays(const EmapRayDataset*, int, int, int, uint64_t, uint64_t, uint64_t*, const int64_t*, const EmapRayBatch*,
-                       hipStream_t);
-int launch_composite_bwd(const float*, const float*, const float*, const float*, const float*, const float*, int, int,
-                         const float*, const EmapRenderParams*, const EmapCompositeGrads*, float*, float*, float*, uint32_t*,
-                         hipStream_t);
-
-// ---- scalar tail of a training step (train.hip) ----
-int launch_train_stats(const float*, const float*, const float*, int, float, float*, float*, hipStream_t);
-int launch_train_loss(const float*, float, float, float, float*, hipStream_t);
-int launch_adam(float*, const float*, float*, float*, float*, int64_t, int64_t, float, float, double, double, float, const float*, float*, hipStream_t);
-// ---- training backward (udf_mlp_vjp.inc, wgrad.hip) ----
-#define EMAP_VJP_DECL(m) \
-    int launch_vjp_sweep_##m(const NetLayout&, const void*, const PointSource&, int64_t, int, int, const float*, const float*, \
-                             const VjpLayout&, char*, char*, char*, int, const uint32_t*, float*, hipStream_t, int32_t*);
-EMAP_VJP_DECL(bf16) EMAP_VJP_DECL(bf16x3) EMAP_VJP_DECL(f16) EMAP_VJP_DECL(f16x3)
-#undef EMAP_VJP_DECL
-size_t plan_wgrad(const NetLayout&, const VjpLayout&, int, WgradJob*, int*, int*, int*, int*);
-int launch_absmax(const float*, const float*, int64_t, uint32_t*, hipStream_t);
-int launch_wgrad(const NetLayout&, const VjpLayout&, const WgradJob*, int, int, const char*, const char*, float*, int, int,
-                 hipStream_t, float scale = 1.0f, int no_bias = 0);
-int launch_wgrad_reduce(const NetLayout&, const WgradJob*, int, const int*, const int*, const float*, const uint32_t*, const float*, int,
-                        const float* const*, const float* const*, float* const*, float* const*, float* const*, int, int, float,
-                        hipStream_t);
-
 static int device_cus() {
     static int n = 0;
     if (n == 0) {
@@ -152,18 +112,16 @@ static int run_vjp(const NetLayout& L, const void* packed, int prec, const Point
     float* partial = reinterpret_cast<float*>(ws + pl.off_partial);
     float* ldot = reinterpret_cast<float*>(ws + pl.off_ldot);
     const int64_t tiles = (P + VJP_PT - 1) / VJP_PT;
+    const MlpUnit* unit = mlp_unit(prec);
+    if (!unit) return EMAP_E_INVALID;
     int chunk = 0;
     for (int64_t t0 = 0; t0 < tiles || chunk == 0; t0 += pl.chunk_tiles, ++chunk) {
         const int nt = (int)std::min<int64_t>(pl.chunk_tiles, std::max<int64_t>(tiles - t0, 0));
         int rc = EMAP_OK;
         {
         ProfScope ps(1, st);
-        switch (prec) {
-            case EMAP_PREC_BF16: rc = launch_vjp_sweep_bf16(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax, ldot, st, err); break;
-            case EMAP_PREC_BF16X3: rc = launch_vjp_sweep_bf16x3(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax, ldot, st, err); break;
-            case EMAP_PREC_F16: rc = launch_vjp_sweep_f16(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax, ldot, st, err); break;
-            default: rc = launch_vjp_sweep_f16x3(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax, ldot, st, err); break;
-        }
+        rc = unit->vjp_sweep(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax,
+                             ldot, st, err);
         }
         if (rc) return rc;
         ProfScope pw(2, st);
@@ -206,6 +164,21 @@ static int check_render_mode(const EmapRenderParams* p, const char* what) {
     return EMAP_E_INVALID;
 }
 
+// the sample counts of a render: m new samples per ray in each of `steps` up-sampling steps (none unless n_importance > 0 and
+// up_sample_steps > 0, the rule of UDFRendererBlending), S = n_samples + steps * m samples per ray in the end
+struct RenderShape {
+    int N, n_samples, m, steps, S;
+};
+static RenderShape render_shape(const EmapRenderParams& p) {
+    RenderShape r;
+    r.N = std::max(p.n_rays, 0);
+    r.n_samples = p.n_samples;
+    r.m = (p.n_importance > 0 && p.up_sample_steps > 0) ? p.n_importance / p.up_sample_steps : 0;
+    r.steps = r.m > 0 ? p.up_sample_steps : 0;
+    r.S = p.n_samples + r.m * r.steps;
+    return r;
+}
+
 struct Workspace {
     size_t sample_dist, z_a, z_b, udf_a, udf_b, z_new, z_new2, udf_new, partials, ray_cnt, rev, total;
 };
@@ -218,10 +191,9 @@ static int fused_composite_from_env() {
 }
 static std::atomic<int> g_fused_composite{fused_composite_from_env()};
 
-static Workspace plan_workspace(const EmapRenderParams& p, const NetLayout* L = nullptr) {
-    const size_t N = (size_t)std::max(p.n_rays, 0);
-    const int m = p.up_sample_steps > 0 ? p.n_importance / p.up_sample_steps : 0;
-    const size_t S = (size_t)p.n_samples + (size_t)m * std::max(p.up_sample_steps, 0);
+static Workspace plan_workspace(const RenderShape& r, const NetLayout* L = nullptr) {
+    const size_t N = (size_t)r.N, S = (size_t)r.S;
+    const int m = r.m;
     Workspace w;
     size_t off = 0;
     w.sample_dist = off; off += 256;
@@ -237,6 +209,15 @@ static Workspace plan_workspace(const EmapRenderParams& p, const NetLayout* L = 
     w.rev = off; off += L ? align256(rev_scratch_bytes(*L)) : 0;   // sigma' slabs of the reverse-mode value+gradient kernel
     w.total = off;
     return w;
+}
+
+// render_core's tail inside the final value + grad_x launch (CompositeFuse): the default render mode, at most COMP_FUSED_MAX_S samples per ray,
+// a launch that runs the reverse-sweep kernel and whose rays fit the per-workgroup ray lists; the other renders run the separate compositing
+// and reduction launches
+static bool composite_fused(const NetLayout& L, int prec, const EmapRenderParams& p, const RenderShape& r) {
+    const int64_t P = (int64_t)r.N * r.S;
+    return p.render_mode == EMAP_RENDER_UNBIASED && r.S <= COMP_FUSED_MAX_S && g_fused_composite.load(std::memory_order_relaxed) &&
+           mlp_uses_rev(L, prec, P) && comp_list_entries(P, r.S) <= COMP_LIST_MAX;
 }
 
 }  // namespace emap
@@ -353,9 +334,12 @@ int emap_composite_fwd(const float* rays_o, const float* rays_d, const float* z,
                        float near_surface, float sparse_scale, float background, int has_background,
                        const EmapCompositeOut* out, float* partials, int32_t* err_flags, void* stream) {
     if (N > 0 && (!rays_o || !rays_d || !z || !udf || !grad3 || !sample_dist_dev)) { set_error("composite_fwd: null pointer"); return EMAP_E_INVALID; }
-    return launch_composite(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, inv_s, beta, gamma,
-                            cos_anneal_ratio, has_cos_anneal, flip_saturation, near_surface, sparse_scale, background,
-                            has_background, nullptr, nullptr, nullptr, 0.f, out, partials, err_flags,
+    EmapRenderParams p;
+    memset(&p, 0, sizeof(p));      // no *_dev parameters, beta_min 0, EMAP_RENDER_UNBIASED
+    p.inv_s = inv_s; p.beta = beta; p.gamma = gamma; p.cos_anneal_ratio = cos_anneal_ratio; p.has_cos_anneal = has_cos_anneal;
+    p.flip_saturation = flip_saturation; p.near_surface = near_surface; p.sparse_scale = sparse_scale; p.background = background;
+    p.has_background = has_background;
+    return launch_composite(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, p, out, partials, err_flags,
                             static_cast<hipStream_t>(stream));
 }
 
@@ -365,10 +349,8 @@ int emap_composite_fwd_p(const float* rays_o, const float* rays_d, const float* 
     if (!p || (N > 0 && (!rays_o || !rays_d || !z || !udf || !grad3 || !sample_dist_dev))) { set_error("composite_fwd_p: null pointer"); return EMAP_E_INVALID; }
     const int rc = check_render_mode(p, "composite_fwd_p");
     if (rc) return rc;
-    return launch_composite(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, p->inv_s, p->beta, p->gamma,
-                            p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
-                            p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,
-                            partials, err_flags, static_cast<hipStream_t>(stream), p->render_mode);
+    return launch_composite(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist_dev, *p, out, partials, err_flags,
+                            static_cast<hipStream_t>(stream));
 }
 
 int emap_render_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRenderParams* p, size_t* bytes) {
@@ -377,7 +359,7 @@ int emap_render_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRe
     if (rc) return rc;
     if (!p || !bytes) { set_error("render_workspace_bytes: null pointer"); return EMAP_E_INVALID; }
     if (check_render_mode(p, "render_workspace_bytes")) return EMAP_E_INVALID;
-    *bytes = plan_workspace(*p, &L).total;
+    *bytes = plan_workspace(render_shape(*p), &L).total;
     return EMAP_OK;
 }
 
@@ -395,14 +377,12 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     rc = check_render_mode(p, "render_fwd");
     if (rc) return rc;
     const bool plain = p->render_mode == EMAP_RENDER_PLAIN;
-    const int N = p->n_rays, Sc = p->n_samples, K = p->up_sample_steps;
+    const RenderShape r = render_shape(*p);
+    const int N = r.N, Sc = r.n_samples, m = r.m, steps = r.steps, S = r.S;
     if (N <= 0) return EMAP_OK;
-    if (Sc < 2 || p->n_importance < 0 || (p->n_importance > 0 && K < 1)) { set_error("render_fwd: bad sampling configuration"); return EMAP_E_INVALID; }
-    const int m = (p->n_importance > 0) ? p->n_importance / K : 0;
-    const int steps = (m > 0) ? K : 0;
-    const int S = Sc + m * steps;
+    if (Sc < 2 || p->n_importance < 0 || (p->n_importance > 0 && p->up_sample_steps < 1)) { set_error("render_fwd: bad sampling configuration"); return EMAP_E_INVALID; }
     if (S > EMAP_MAX_SAMPLES_PER_RAY) { set_error("render_fwd: %d samples per ray exceed the kernel limit of %d", S, EMAP_MAX_SAMPLES_PER_RAY); return EMAP_E_INVALID; }
-    const Workspace w = plan_workspace(*p, &L);
+    const Workspace w = plan_workspace(r, &L);
     if (workspace_bytes < w.total) { set_error("render_fwd: workspace %zu < %zu bytes", workspace_bytes, w.total); return EMAP_E_WORKSPACE; }
     char* ws = static_cast<char*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -415,10 +395,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     // render_core's tail inside the final value + grad_x launch (ABI 9) where that launch is the reverse-sweep kernel: the first launch of
     // the render clears the per-ray arrival counters, the final one composites every ray as its last tile completes
     int32_t* ray_cnt = reinterpret_cast<int32_t*>(ws + w.ray_cnt);
-    // (the fused tail composites in the default render mode and up to COMP_FUSED_MAX_S = 256 samples per ray only: the other shapes run the
-    // separate compositing and reduction launches)
-    const bool fuse_comp = p->render_mode == EMAP_RENDER_UNBIASED && S <= COMP_FUSED_MAX_S && g_fused_composite.load(std::memory_order_relaxed) &&
-                           mlp_uses_rev(L, prec, (int64_t)N * S) && comp_list_entries((int64_t)N * S, S) <= COMP_LIST_MAX;
+    const bool fuse_comp = composite_fused(L, prec, *p, r);
 
     if (steps == 0) {
         // no up-sampling: the coarse samples (render() :700-720) are the final z_vals
@@ -456,7 +433,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
             a.rays_o = rays_o; a.rays_d = rays_d; a.N = N; a.m = m; a.err = err_flags; a.sample_dist = sample_dist;
             a.inv_s = 64.0f * (float)(1 << i);                                          // :826
             a.beta = 64.0f * (float)(1 << (i + 1));                                     // :828
-            a.gamma = std::min(std::max(20.0f * (float)(1 << (K - i)), 20.0f), 320.0f);  // :830
+            a.gamma = std::min(std::max(20.0f * (float)(1 << (steps - i)), 20.0f), 320.0f);  // :830
             a.z_new = znew[i & 1];
             a.z_final = last ? z_vals : nullptr;
             if (i == 0) {
@@ -483,10 +460,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     fin.rays_o = rays_o; fin.rays_d = rays_d; fin.z = z_vals; fin.n_per_ray = S; fin.mid = 1; fin.sample_dist = sample_dist;
     CompositeFuse cf;
     if (fuse_comp) {
-        rc = fill_composite_args(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, p->inv_s, p->beta, p->gamma,
-                                 p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
-                                 p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,
-                                 partials, &cf.c);
+        rc = fill_composite_args(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, &cf.c);
         if (rc) return rc;
         cf.ray_cnt = ray_cnt;
         cf.done_cnt = ray_cnt + N;   // the fused tail also runs the cross-ray reduction
@@ -498,10 +472,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     if (rc) return rc;
     // 3 launches per render: value pass, importance_sample, value + grad_x + compositing + cross-ray reduction
     if (fuse_comp) return cf.c.out.scalars ? EMAP_OK : launch_composite_reduce(cf.c, err_flags, st);
-    return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, p->inv_s, p->beta, p->gamma,
-                            p->cos_anneal_ratio, p->has_cos_anneal, p->flip_saturation, p->near_surface, p->sparse_scale,
-                            p->background, p->has_background, p->variance_dev, p->beta_dev, p->gamma_dev, p->beta_min, out,
-                            partials, err_flags, st, p->render_mode);
+    return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, err_flags, st);
 }
 
 int emap_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
@@ -546,10 +517,8 @@ int emap_udf_vjp(const EmapNetConfig* cfg, const void* packed, int prec, const f
     return run_vjp(L, packed, prec, src, P, d_udf, d_grad3, out, pl, ws, err_flags, st);
 }
 
-static size_t render_bwd_extra(const EmapRenderParams& p, size_t* off_du, size_t* off_dg, size_t* off_part) {
-    const size_t N = (size_t)std::max(p.n_rays, 0);
-    const int m = p.up_sample_steps > 0 ? p.n_importance / p.up_sample_steps : 0;
-    const size_t S = (size_t)p.n_samples + (size_t)m * std::max(p.up_sample_steps, 0);
+static size_t render_bwd_extra(const RenderShape& r, size_t* off_du, size_t* off_dg, size_t* off_part) {
+    const size_t N = (size_t)r.N, S = (size_t)r.S;
     size_t off = 0;
     *off_du = off; off += align256(N * S * 4);
     *off_dg = off; off += align256(N * S * 12);
@@ -563,11 +532,9 @@ int emap_render_bwd_workspace_bytes(const EmapNetConfig* cfg, int prec, const Em
     if (rc) return rc;
     if (!p || !bytes) { set_error("render_bwd_workspace_bytes: null pointer"); return EMAP_E_INVALID; }
     if (check_render_mode(p, "render_bwd_workspace_bytes")) return EMAP_E_INVALID;
+    const RenderShape r = render_shape(*p);
     size_t a, b, c;
-    const size_t extra = render_bwd_extra(*p, &a, &b, &c);
-    const int m = p->up_sample_steps > 0 ? p->n_importance / p->up_sample_steps : 0;
-    const int64_t S = (int64_t)p->n_samples + (int64_t)m * std::max(p->up_sample_steps, 0);
-    *bytes = extra + plan_vjp(L, (int64_t)std::max(p->n_rays, 0) * S).total;
+    *bytes = render_bwd_extra(r, &a, &b, &c) + plan_vjp(L, (int64_t)r.N * r.S).total;
     return EMAP_OK;
 }
 
@@ -577,11 +544,9 @@ int emap_render_bwd_absmax_offset(const EmapNetConfig* cfg, int prec, const Emap
     if (rc) return rc;
     if (!p || !offset) { set_error("render_bwd_absmax_offset: null pointer"); return EMAP_E_INVALID; }
     if (check_render_mode(p, "render_bwd_absmax_offset")) return EMAP_E_INVALID;
+    const RenderShape r = render_shape(*p);
     size_t a, b, c;
-    const size_t extra = render_bwd_extra(*p, &a, &b, &c);
-    const int m = p->up_sample_steps > 0 ? p->n_importance / p->up_sample_steps : 0;
-    const int64_t S = (int64_t)p->n_samples + (int64_t)m * std::max(p->up_sample_steps, 0);
-    *offset = extra + plan_vjp(L, (int64_t)std::max(p->n_rays, 0) * S).off_absmax;
+    *offset = render_bwd_extra(r, &a, &b, &c) + plan_vjp(L, (int64_t)r.N * r.S).off_absmax;
     return EMAP_OK;
 }
 
@@ -608,13 +573,12 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
     if (rc) return rc;
     rc = check_param_grads(L, out, "render_bwd");
     if (rc) return rc;
-    const int N = p->n_rays;
+    const RenderShape r = render_shape(*p);
+    const int N = r.N, S = r.S;
     if (N <= 0) return EMAP_OK;
-    const int m = p->up_sample_steps > 0 && p->n_importance > 0 ? p->n_importance / p->up_sample_steps : 0;
-    const int S = p->n_samples + m * (m > 0 ? p->up_sample_steps : 0);
     if (S > EMAP_MAX_SAMPLES_PER_RAY) { set_error("render_bwd: %d samples per ray exceed the kernel limit of %d", S, EMAP_MAX_SAMPLES_PER_RAY); return EMAP_E_INVALID; }
     size_t o_du, o_dg, o_part;
-    const size_t extra = render_bwd_extra(*p, &o_du, &o_dg, &o_part);
+    const size_t extra = render_bwd_extra(r, &o_du, &o_dg, &o_part);
     const VjpPlan pl = plan_vjp(L, (int64_t)N * S, workspace_bytes > extra ? workspace_bytes - extra : 1);
     if (pl.chunk_tiles <= 0) { set_error("render_bwd: workspace %zu < %zu bytes (minimum; emap_render_bwd_workspace_bytes is the preferred size)", workspace_bytes, extra + vjp_min_bytes(L, (int64_t)N * S)); return EMAP_E_WORKSPACE; }
     char* ws = static_cast<char*>(workspace);

@@ -154,14 +154,18 @@ struct CompositeFuse {
     // deterministic cross-ray reduction (composite_reduce_body, the body of composite_reduce_kernel): the render ends with this launch.
     int32_t* done_cnt;
 };
+constexpr int REV_MAX_WG = 768;      // persistent workgroups of the reverse-mode kernel (3 per CU)
+// grid cap of the reverse-mode kernel's 4-wave form (two resident workgroups per CU), the only form that runs the fused tail
+// (launch_mlp_rev32_t's wg_cap, which asserts the equality)
+constexpr int REV_WG_CAP_4W = REV_MAX_WG * 2 / 3;
 // upper bound on the rays ONE workgroup of the value + grad_x kernel can come to own (its list lives in the kernel's exchange buffer): every tile
-// it runs (64 points, <= 512 workgroups) can complete at most 64 / S + 2 rays
+// it runs (64 points, <= REV_WG_CAP_4W workgroups) can complete at most 64 / S + 2 rays
 constexpr int COMP_LIST_MAX = 8192;
 // samples per ray of the fused tail: it composites with lane chunks of C <= 4 (udf_mlp_rev32.inc); longer rays take the separate
 // compositing and reduction launches (sampler.hip, C = 8 / 16)
 constexpr int COMP_FUSED_MAX_S = 256;
 inline long long comp_list_entries(long long P, int S) {
-    const long long tiles = (P + 63) / 64, grid = tiles < 512 ? tiles : 512;
+    const long long tiles = (P + 63) / 64, grid = tiles < REV_WG_CAP_4W ? tiles : REV_WG_CAP_4W;
     return ((tiles + grid - 1) / (grid > 0 ? grid : 1)) * (64 / (S > 0 ? S : 1) + 2);
 }
 // one fused step of importance_sample (sampler.hip:sampler_step_kernel)
@@ -243,13 +247,71 @@ int set_grad_mode(int mode);   // -1 by launch size, 0 forward-mode tangents, 1 
 extern int g_prof_clk_device;
 long long* prof_clk_here();   // g_prof_clk if the current device is the one it was allocated on, else null
 extern long long* g_prof_clk;   // device buffer of 8 x int64 while emap_profile_enable(1) is in effect, else null (clock_stamp in udf_mlp_kernel.inc)
-constexpr int REV_MAX_WG = 768;      // persistent workgroups of the reverse-mode kernel (3 per CU)
 // sigma' stash of the reverse-mode kernel per row tile and column tile of 32 points: 16 values per lane x 64 lanes, 3 bytes reserved per value
 // (unorm16 planes; precision mode f16x3e adds one plane of low bytes - udf_mlp_rev32.inc, SG24)
 constexpr int REV_SG_BYTES_PER_NC = 3072;
 inline size_t rev_scratch_bytes(const NetLayout& L) {   // sigmoid stash: [workgroup][layer][pair][6][64 lanes x 16 B]
     // + 8 KiB per workgroup: the lo parts of the tile's PE block (MX6F: their LDS slots hold the fp6 forms; read back by the PE rows)
-    return L.has_rev ? (size_t)(REV_MAX_WG * 2 / 3) * ((size_t)(L.n_lin - 1) * (size_t)(L.H / 32) * (2 * REV_SG_BYTES_PER_NC) + 8192) : 0;   // 2 resident workgroups per CU
+    return L.has_rev ? (size_t)REV_WG_CAP_4W * ((size_t)(L.n_lin - 1) * (size_t)(L.H / 32) * (2 * REV_SG_BYTES_PER_NC) + 8192) : 0;   // 2 resident workgroups per CU
 }
+
+// ---- host launchers (defined in the unit named above each group; every caller and the definition see these declarations) --------
+// sampler.hip
+int launch_sample_pdf(const float* bins, const float* weights, int N, int n, int m, float* samples, int64_t* inds, int32_t* err,
+                      hipStream_t st, const float* u = nullptr);
+int launch_upsample(const float* rays_o, const float* rays_d, const float* z, const float* udf, int N, int n, int m, const float* sample_dist,
+                    float inv_s, float beta, float gamma, float* z_new, int64_t* inds, int32_t* err, hipStream_t st);
+int launch_upsample_plain(const float* z, const float* udf, int N, int n, int m, const float* sample_dist, float beta, float gamma, float* z_new,
+                          int64_t* inds, int32_t* err, hipStream_t st);
+int launch_merge(const float* z, const float* z_new, const float* udf, const float* udf_new, int N, int n, int m, float* z_out, float* udf_out,
+                 int64_t* perm, hipStream_t st);
+int launch_coarse(const float* near, const float* far, const float* t_rand, int N, int n_samples, float* z, float* sample_dist, hipStream_t st);
+// render_core's tail: the render scalars and the mode (render_mode) come from p; fill_composite_args checks the arguments and fills *a
+int fill_composite_args(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
+                        int N, int S, const float* sample_dist, const EmapRenderParams& p, const EmapCompositeOut* out, float* partials,
+                        CompositeArgs* a);
+int launch_composite(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
+                     int N, int S, const float* sample_dist, const EmapRenderParams& p, const EmapCompositeOut* out, float* partials,
+                     int32_t* err, hipStream_t st);
+int launch_composite_reduce(const CompositeArgs& a, int32_t* err, hipStream_t st);
+int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
+                         int N, int S, const float* sample_dist, const EmapRenderParams* p, const EmapCompositeGrads* gr, float* d_udf,
+                         float* d_grad3, float* partials, uint32_t* absmax, hipStream_t st);
+int launch_embed(const float* x, int64_t P, int L, float* pe, hipStream_t st);
+void linspace_host(float start, float end, int steps, float* out);
+// rays.hip
+int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset, uint64_t* counter,
+                       const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st);
+// train.hip: the scalar tail of a training step
+int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
+                       hipStream_t st);
+int launch_train_loss(const float* stats, float w_over_n, float igr, float igr_ns, float* out, hipStream_t st);
+int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64_t n, int64_t n_geo, float lr_geo, float lr, double b1,
+                double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st);
+// wgrad.hip: the training backward's weight-gradient GEMMs
+size_t plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget, WgradJob* jobs, int* n_jobs, int* job_h, int* job_pe, int* total_wg);
+int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hipStream_t st);
+int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradJob* jobs, int n_jobs, int total_wg, const char* stash_a,
+                 const char* stash_z, float* partial, int n_tiles, int accumulate, hipStream_t st, float scale = 1.0f, int no_bias = 0);
+int launch_wgrad_reduce(const NetLayout& L, const WgradJob* jobs, int n_jobs, const int* job_h, const int* job_pe, const float* partial,
+                        const uint32_t* absmax, const float* ldot, int n_tiles, const float* const* g, const float* const* v, float* const* dg,
+                        float* const* dv, float* const* db, int weight_norm, int accumulate, float grad_scale, hipStream_t st);
+
+// The entry points of one precision unit (udf_mlp_<mode>.hip, one instantiation of udf_mlp_kernel.inc each).  variant: mlp_variant (udf_mlp.hip)
+struct MlpUnit {
+    int (*mlp)(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, float* grad3, hipStream_t st,
+               int variant, int32_t* err, void* scratch, const CompositeFuse* fuse);
+    int (*importance)(const NetLayout& L, const void* packed, const IsLaunch& q, hipStream_t st, int32_t* err);
+    // the training backward's per-point sweep over tiles [tile0, tile0 + n_tiles) (udf_mlp_vjp.inc)
+    int (*vjp_sweep)(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, int tile0, int n_tiles, const float* d_udf,
+                     const float* d_grad, const VjpLayout& V, char* stash_a, char* stash_z, char* stash_s, int grid, const uint32_t* absmax,
+                     float* ldot, hipStream_t st, int32_t* err);
+};
+const MlpUnit* mlp_unit_bf16();
+const MlpUnit* mlp_unit_bf16x3();
+const MlpUnit* mlp_unit_f16();
+const MlpUnit* mlp_unit_f16x3();
+// the unit of precision mode prec (f16x3e and f16x3m are f16x3: NetLayout selects their kernels); null with the error text set for an unknown mode
+const MlpUnit* mlp_unit(int prec);
 
 }  // namespace emap

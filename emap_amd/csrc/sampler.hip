@@ -14,6 +14,8 @@
 // fp64 and round each output to fp32, which is what torch's CPU cumsum/cumprod do
 // (acc_type<float, /*is_cuda=*/false> == double).
 #include "emap_common.h"
+#include <algorithm>
+#include <type_traits>
 
 namespace emap {
 
@@ -208,13 +210,11 @@ __global__ __launch_bounds__(256) void coarse_z_kernel(const float* near, const 
 // ---------------------------------------------------------------------------------------------
 // render_core tail (udf_renderer_blending.py:435-455,463-677)
 // ---------------------------------------------------------------------------------------------
-#include "composite_dev.inc"     // CompositeArgs + composite_ray<C, COH> / composite_ray_mode<C, MODE>: the per-ray body, shared with udf_mlp_rev32.inc's fused tail
-
+#include "composite_dev.inc"     // composite_ray<C, COH, MODE>: the per-ray body, shared with udf_mlp_rev32.inc's fused tail
 
 template <int C, int MODE = EMAP_RENDER_UNBIASED>
 __global__ __launch_bounds__(64) void composite_kernel(const CompositeArgs a) {
-    if constexpr (MODE == EMAP_RENDER_UNBIASED) composite_ray<C, false>(a, blockIdx.x, threadIdx.x);
-    else composite_ray_mode<C, MODE>(a, blockIdx.x, threadIdx.x);
+    composite_ray<C, false, MODE>(a, blockIdx.x, threadIdx.x);
 }
 
 // deterministic cross-ray reduction of the eikonal terms (:618-625) and sparse_error (:642-644)
@@ -576,13 +576,41 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* x, long long P,
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
+// A runtime value as a compile-time constant: each helper calls f with the std::integral_constant it maps the value to, so that one launch
+// statement names the kernel for every case.
+template <int V> using Int = std::integral_constant<int, V>;
+// CAP: LDS capacity in samples per ray - MAXS whenever n of them fit, else MAXS_WIDE (callers range-check n first)
+template <class F> void with_cap(int n, F&& f) {
+    if (n <= MAXS) f(Int<MAXS>{});
+    else f(Int<MAXS_WIDE>{});
+}
+// C: samples per lane of a one-wave-per-ray kernel over S <= 64 C samples (callers range-check S <= MAXS_WIDE = 64 * 16 first)
+template <class F> void with_chunk(int S, F&& f) {
+    if (S <= 64) f(Int<1>{});
+    else if (S <= 128) f(Int<2>{});
+    else if (S <= 256) f(Int<4>{});
+    else if (S <= 512) f(Int<8>{});
+    else f(Int<16>{});
+}
+// EmapRenderParams.render_mode (checked by the entry points): anything else is the default mode
+template <class F> void with_render_mode(int mode, F&& f) {
+    if (mode == EMAP_RENDER_PLAIN) f(Int<EMAP_RENDER_PLAIN>{});
+    else if (mode == EMAP_RENDER_UNBIASED_NORMCOS) f(Int<EMAP_RENDER_UNBIASED_NORMCOS>{});
+    else f(Int<EMAP_RENDER_UNBIASED>{});
+}
+// f(std::bool_constant<b>...) for the flags b...
+template <class F> void with_flags(F&& f) { f(); }
+template <class F, class... B> void with_flags(F&& f, bool b, B... rest) {
+    if (b) with_flags([&](auto... v) { f(std::true_type{}, v...); }, rest...);
+    else with_flags([&](auto... v) { f(std::false_type{}, v...); }, rest...);
+}
+
 int launch_sample_pdf(const float* bins, const float* weights, int N, int n, int m, float* samples, int64_t* inds,
                       int32_t* err, hipStream_t st, const float* u) {
     if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("sample_pdf: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
     // the samples go straight to global memory: only the n bins take LDS
-    if (n <= MAXS) hipLaunchKernelGGL(sample_pdf_kernel<MAXS>, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u);
-    else hipLaunchKernelGGL(sample_pdf_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u);
+    with_cap(n, [&](auto cap) { hipLaunchKernelGGL(sample_pdf_kernel<cap>, dim3(N), dim3(64), 0, st, bins, weights, N, n, m, samples, inds, err, u); });
     return check_launch("sample_pdf");
 }
 
@@ -591,10 +619,9 @@ int launch_upsample(const float* rays_o, const float* rays_d, const float* z, co
                     int32_t* err, hipStream_t st) {
     if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("upsample_step: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    if (n <= MAXS) hipLaunchKernelGGL(upsample_kernel<MAXS>, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta,
-                                      gamma, z_new, inds, err);
-    else hipLaunchKernelGGL(upsample_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta,
-                            gamma, z_new, inds, err);
+    with_cap(n, [&](auto cap) {
+        hipLaunchKernelGGL(upsample_kernel<cap>, dim3(N), dim3(64), 0, st, rays_o, rays_d, z, udf, N, n, m, sample_dist, inv_s, beta, gamma, z_new, inds, err);
+    });
     return check_launch("upsample_step");
 }
 
@@ -602,8 +629,9 @@ int launch_upsample_plain(const float* z, const float* udf, int N, int n, int m,
                           int64_t* inds, int32_t* err, hipStream_t st) {
     if (n < 2 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("upsample_step_plain: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    if (n <= MAXS) hipLaunchKernelGGL(upsample_plain_kernel<MAXS>, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
-    else hipLaunchKernelGGL(upsample_plain_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
+    with_cap(n, [&](auto cap) {
+        hipLaunchKernelGGL(upsample_plain_kernel<cap>, dim3(N), dim3(64), 0, st, z, udf, N, n, m, sample_dist, beta, gamma, z_new, inds, err);
+    });
     return check_launch("upsample_step_plain");
 }
 
@@ -612,36 +640,22 @@ int launch_merge(const float* z, const float* z_new, const float* udf, const flo
     if (n < 1 || n > MAXS_WIDE || m < 1 || m > MAXS_WIDE) { set_error("merge_sorted: n=%d m=%d out of range (max %d)", n, m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (udf_out && (!udf || !udf_new)) { set_error("merge_sorted: udf_out needs udf and udf_new"); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
-    if (n <= MAXS && m <= MAXS) hipLaunchKernelGGL(merge_kernel<MAXS>, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
-    else hipLaunchKernelGGL(merge_kernel<MAXS_WIDE>, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
+    with_cap(std::max(n, m), [&](auto cap) {
+        hipLaunchKernelGGL(merge_kernel<cap>, dim3(N), dim3(64), 0, st, z, z_new, udf, udf_new, N, n, m, z_out, udf_out, perm);
+    });
     return check_launch("merge_sorted");
 }
 
-template <int CAP>
-static void launch_sampler_step_t(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain) {
-    if (plain) {            // use_unbias_render=False: up_sample_no_occ_aware in every step
-        if (coarse) {
-            if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        } else {
-            if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, true, true>), dim3(a.N), dim3(64), 0, st, a);
-            else hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        }
-    } else if (coarse) {
-        if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, true>), dim3(a.N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((sampler_step_kernel<CAP, true, false, false>), dim3(a.N), dim3(64), 0, st, a);
-    } else {
-        if (tail) hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, true>), dim3(a.N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((sampler_step_kernel<CAP, false, true, false>), dim3(a.N), dim3(64), 0, st, a);
-    }
-}
-
+// plain: use_unbias_render=False, up_sample_no_occ_aware in every step.  Every step after the first merges (MERGE = !COARSE)
 int launch_sampler_step(bool coarse, bool tail, const StepArgs& a, hipStream_t st, bool plain) {
     const int n_out = a.n + (coarse ? 0 : a.m);
     if (a.n < 2 || n_out + a.m > MAXS_WIDE || a.m < 1) { set_error("sampler_step: n=%d m=%d out of range (max %d)", a.n, a.m, MAXS_WIDE); return EMAP_E_INVALID; }
     if (a.N <= 0) return EMAP_OK;
-    if (n_out + a.m <= MAXS) launch_sampler_step_t<MAXS>(coarse, tail, a, st, plain);
-    else launch_sampler_step_t<MAXS_WIDE>(coarse, tail, a, st, plain);
+    with_cap(n_out + a.m, [&](auto cap) {
+        with_flags([&](auto co, auto ta, auto pl) {
+            hipLaunchKernelGGL((sampler_step_kernel<cap, co, !co, ta, pl>), dim3(a.N), dim3(64), 0, st, a);
+        }, coarse, tail, plain);
+    });
     return check_launch("sampler_step");
 }
 
@@ -654,20 +668,25 @@ int launch_coarse(const float* near, const float* far, const float* t_rand, int 
     return check_launch("coarse_z");
 }
 
+// the render scalars CompositeArgs and CompositeBwdArgs share, from the entry point's EmapRenderParams
+template <class A>
+static void copy_render_scalars(const EmapRenderParams& p, A& a) {
+    a.inv_s = p.inv_s; a.beta = p.beta; a.gamma = p.gamma; a.car = p.cos_anneal_ratio; a.anneal = p.has_cos_anneal;
+    a.flip_sat = p.flip_saturation; a.near_surface = p.near_surface; a.background = p.background; a.has_bg = p.has_background;
+    a.var_p = p.variance_dev; a.beta_p = p.beta_dev; a.gamma_p = p.gamma_dev; a.beta_min = p.beta_min;
+}
+
 int fill_composite_args(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
-                        const float* depth_scale, int N, int S, const float* sample_dist, float inv_s, float beta,
-                        float gamma, float car, int anneal, float flip_sat, float near_surface, float sparse_scale,
-                        float background, int has_bg, const float* var_p, const float* beta_p, const float* gamma_p,
-                        float beta_min, const EmapCompositeOut* out, float* partials, CompositeArgs* pa) {
+                        const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
+                        const EmapCompositeOut* out, float* partials, CompositeArgs* pa) {
     if (S < 1 || S > MAXS_WIDE) { set_error("composite: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (!out || !partials) { set_error("composite: out/partials must not be null"); return EMAP_E_INVALID; }
-    if (var_p && (!beta_p || !gamma_p)) { set_error("composite: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
+    if (p.variance_dev && (!p.beta_dev || !p.gamma_dev)) { set_error("composite: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
     CompositeArgs& a = *pa;
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
-    a.sample_dist = sample_dist; a.N = N; a.S = S; a.inv_s = inv_s; a.beta = beta; a.gamma = gamma; a.car = car;
-    a.anneal = anneal; a.flip_sat = flip_sat; a.near_surface = near_surface; a.sparse_scale = sparse_scale;
-    a.background = background; a.has_bg = has_bg; a.out = *out; a.partials = partials;
-    a.var_p = var_p; a.beta_p = beta_p; a.gamma_p = gamma_p; a.beta_min = beta_min;
+    a.sample_dist = sample_dist; a.N = N; a.S = S;
+    copy_render_scalars(p, a);
+    a.sparse_scale = p.sparse_scale; a.out = *out; a.partials = partials;
     return EMAP_OK;
 }
 
@@ -678,32 +697,15 @@ int launch_composite_reduce(const CompositeArgs& a, int32_t* err, hipStream_t st
 }
 
 int launch_composite(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
-                     const float* depth_scale, int N, int S, const float* sample_dist, float inv_s, float beta,
-                     float gamma, float car, int anneal, float flip_sat, float near_surface, float sparse_scale,
-                     float background, int has_bg, const float* var_p, const float* beta_p, const float* gamma_p,
-                     float beta_min, const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st, int mode) {
+                     const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
+                     const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st) {
     CompositeArgs a;
-    const int rc = fill_composite_args(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, inv_s, beta, gamma, car, anneal, flip_sat,
-                                       near_surface, sparse_scale, background, has_bg, var_p, beta_p, gamma_p, beta_min, out, partials, &a);
+    const int rc = fill_composite_args(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, p, out, partials, &a);
     if (rc) return rc;
     if (N <= 0) return EMAP_OK;
-    if (mode == EMAP_RENDER_PLAIN) {
-        if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 256) hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 512) hipLaunchKernelGGL((composite_kernel<8, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_kernel<16, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-    } else if (mode == EMAP_RENDER_UNBIASED_NORMCOS) {
-        if (S <= 64) hipLaunchKernelGGL((composite_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 128) hipLaunchKernelGGL((composite_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 256) hipLaunchKernelGGL((composite_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 512) hipLaunchKernelGGL((composite_kernel<8, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_kernel<16, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-    } else if (S <= 64) hipLaunchKernelGGL(composite_kernel<1>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 128) hipLaunchKernelGGL(composite_kernel<2>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 256) hipLaunchKernelGGL(composite_kernel<4>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 512) hipLaunchKernelGGL(composite_kernel<8>, dim3(N), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(composite_kernel<16>, dim3(N), dim3(64), 0, st, a);
+    with_render_mode(p.render_mode, [&](auto mode) {
+        with_chunk(S, [&](auto c) { hipLaunchKernelGGL((composite_kernel<c, mode>), dim3(N), dim3(64), 0, st, a); });
+    });
     if (out->scalars) hipLaunchKernelGGL(composite_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, out->scalars, err, a);
     return check_launch("composite");
 }
@@ -714,35 +716,19 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
                          hipStream_t st) {
     if (S < 1 || S > MAXS_WIDE) { set_error("composite_bwd: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
+    if (p->variance_dev && (!p->beta_dev || !p->gamma_dev)) { set_error("composite_bwd: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
     CompositeBwdArgs a;
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
-    a.sample_dist = sample_dist; a.N = N; a.S = S; a.inv_s = p->inv_s; a.beta = p->beta; a.gamma = p->gamma; a.car = p->cos_anneal_ratio;
-    a.anneal = p->has_cos_anneal; a.flip_sat = p->flip_saturation; a.near_surface = p->near_surface;
-    a.background = p->background; a.has_bg = p->has_background;
-    a.var_p = p->variance_dev; a.beta_p = p->beta_dev; a.gamma_p = p->gamma_dev; a.beta_min = p->beta_min;
-    if (a.var_p && (!a.beta_p || !a.gamma_p)) { set_error("composite_bwd: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
+    a.sample_dist = sample_dist; a.N = N; a.S = S;
+    copy_render_scalars(*p, a);
     a.d_edge = gr->d_edge; a.d_depth = gr->d_depth; a.d_ge = gr->d_gradient_error; a.d_ge_ns = gr->d_gradient_error_near_surface;
     a.scalars = gr->scalars; a.d_udf = d_udf; a.d_grad = d_grad3; a.partials = partials; a.absmax = absmax;
     a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail;
     a.raymax = absmax ? partials + (size_t)N * 4 : nullptr;     // internal callers (emap_render_bwd) size `partials` as (N,4) + (N,2)
     if ((a.d_ge || a.d_ge_ns) && !a.scalars) { set_error("composite_bwd: the eikonal gradients need the forward's scalars"); return EMAP_E_INVALID; }
-    if (p->render_mode == EMAP_RENDER_PLAIN) {
-        if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 256) hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 512) hipLaunchKernelGGL((composite_bwd_kernel<8, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_bwd_kernel<16, EMAP_RENDER_PLAIN>), dim3(N), dim3(64), 0, st, a);
-    } else if (p->render_mode == EMAP_RENDER_UNBIASED_NORMCOS) {
-        if (S <= 64) hipLaunchKernelGGL((composite_bwd_kernel<1, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 128) hipLaunchKernelGGL((composite_bwd_kernel<2, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 256) hipLaunchKernelGGL((composite_bwd_kernel<4, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else if (S <= 512) hipLaunchKernelGGL((composite_bwd_kernel<8, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((composite_bwd_kernel<16, EMAP_RENDER_UNBIASED_NORMCOS>), dim3(N), dim3(64), 0, st, a);
-    } else if (S <= 64) hipLaunchKernelGGL(composite_bwd_kernel<1>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 128) hipLaunchKernelGGL(composite_bwd_kernel<2>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 256) hipLaunchKernelGGL(composite_bwd_kernel<4>, dim3(N), dim3(64), 0, st, a);
-    else if (S <= 512) hipLaunchKernelGGL(composite_bwd_kernel<8>, dim3(N), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(composite_bwd_kernel<16>, dim3(N), dim3(64), 0, st, a);
+    with_render_mode(p->render_mode, [&](auto mode) {
+        with_chunk(S, [&](auto c) { hipLaunchKernelGGL((composite_bwd_kernel<c, mode>), dim3(N), dim3(64), 0, st, a); });
+    });
     hipLaunchKernelGGL(composite_bwd_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, a, gr->d_variance, gr->d_beta,
                        gr->d_gamma, gr->grad_scale, gr->accumulate);
     return check_launch("composite_bwd");

@@ -589,10 +589,18 @@ int launch_pack(const NetLayout& L, const float* const* g, const float* const* v
     return check_launch("pack_weights");
 }
 
-int launch_mlp_bf16(const NetLayout&, const void*, const PointSource&, int64_t, float*, float*, hipStream_t, int, int32_t*, void*, const CompositeFuse*);
-int launch_mlp_bf16x3(const NetLayout&, const void*, const PointSource&, int64_t, float*, float*, hipStream_t, int, int32_t*, void*, const CompositeFuse*);
-int launch_mlp_f16(const NetLayout&, const void*, const PointSource&, int64_t, float*, float*, hipStream_t, int, int32_t*, void*, const CompositeFuse*);
-int launch_mlp_f16x3(const NetLayout&, const void*, const PointSource&, int64_t, float*, float*, hipStream_t, int, int32_t*, void*, const CompositeFuse*);
+const MlpUnit* mlp_unit(int prec) {
+    switch (prec) {
+        case EMAP_PREC_BF16: return mlp_unit_bf16();
+        case EMAP_PREC_BF16X3: return mlp_unit_bf16x3();
+        case EMAP_PREC_F16: return mlp_unit_f16();
+        case EMAP_PREC_F16X3:
+        case EMAP_PREC_F16X3E:
+        case EMAP_PREC_F16X3M: return mlp_unit_f16x3();   // L.mx_fwd / mx_bwd / sweep_mx select the kernels
+    }
+    set_error("unknown precision mode %d", prec);
+    return nullptr;
+}
 
 // kernel variant: 2 = "fs2" (udf_mlp_fs2_kernel: every value launch, forward-mode tangents for small grad launches),
 // 3 = "rev" (grad launches only: forward + reverse sweep on 32x32 MFMA tiles, udf_mlp_rev32.inc).
@@ -622,22 +630,9 @@ int launch_mlp(const NetLayout& L, const void* packed, int prec, const PointSour
                float* grad3, hipStream_t st, int32_t* err_flags, void* scratch, const CompositeFuse* fuse) {
     const int v = mlp_variant(L, prec, P, grad3 != nullptr);
     if (fuse && v != 3) { set_error("launch_mlp: the fused compositing tail needs the reverse-sweep kernel (mlp_uses_rev)"); return EMAP_E_INVALID; }
-    switch (prec) {
-        case EMAP_PREC_BF16: return launch_mlp_bf16(L, packed, src, P, udf, grad3, st, v, err_flags, scratch, fuse);
-        case EMAP_PREC_BF16X3: return launch_mlp_bf16x3(L, packed, src, P, udf, grad3, st, v, err_flags, scratch, fuse);
-        case EMAP_PREC_F16: return launch_mlp_f16(L, packed, src, P, udf, grad3, st, v, err_flags, scratch, fuse);
-        case EMAP_PREC_F16X3:
-        case EMAP_PREC_F16X3E:
-        case EMAP_PREC_F16X3M: return launch_mlp_f16x3(L, packed, src, P, udf, grad3, st, v, err_flags, scratch, fuse);   // L.mx_fwd selects the kernel
-    }
-    set_error("unknown precision mode %d", prec);
-    return EMAP_E_INVALID;
+    const MlpUnit* unit = mlp_unit(prec);
+    return unit ? unit->mlp(L, packed, src, P, udf, grad3, st, v, err_flags, scratch, fuse) : EMAP_E_INVALID;
 }
-
-int launch_is_bf16(const NetLayout&, const void*, const IsLaunch&, hipStream_t, int32_t*);
-int launch_is_bf16x3(const NetLayout&, const void*, const IsLaunch&, hipStream_t, int32_t*);
-int launch_is_f16(const NetLayout&, const void*, const IsLaunch&, hipStream_t, int32_t*);
-int launch_is_f16x3(const NetLayout&, const void*, const IsLaunch&, hipStream_t, int32_t*);
 
 static int fused_sampling_from_env() {      // EMAP_FUSED_SAMPLING=0: the launch chain; 2: fused whatever the launch size (A/B) (read ONCE at load, like EMAP_GRAD_MODE; at run time: emap_set_fused_sampling)
     const char* e = getenv("EMAP_FUSED_SAMPLING");
@@ -649,16 +644,8 @@ int fused_sampling_mode() { return g_fused_sampling.load(std::memory_order_relax
 
 int launch_importance(const NetLayout& L, const void* packed, int prec, const IsLaunch& q, hipStream_t st, int32_t* err_flags) {
     if (!g_fused_sampling.load(std::memory_order_relaxed)) return IS_NOT_FUSED;
-    switch (prec) {
-        case EMAP_PREC_BF16: return launch_is_bf16(L, packed, q, st, err_flags);
-        case EMAP_PREC_BF16X3: return launch_is_bf16x3(L, packed, q, st, err_flags);
-        case EMAP_PREC_F16: return launch_is_f16(L, packed, q, st, err_flags);
-        case EMAP_PREC_F16X3:
-        case EMAP_PREC_F16X3E:
-        case EMAP_PREC_F16X3M: return launch_is_f16x3(L, packed, q, st, err_flags);
-    }
-    set_error("unknown precision mode %d", prec);
-    return EMAP_E_INVALID;
+    const MlpUnit* unit = mlp_unit(prec);
+    return unit ? unit->importance(L, packed, q, st, err_flags) : EMAP_E_INVALID;
 }
 
 }  // namespace emap

@@ -865,5 +865,19 @@ int launch_is_mode(const NetLayout& L, const void* packed, const IsLaunch& q, hi
 #include "udf_mlp_rev32.inc"
 #include "udf_mlp_vjp.inc"
 
-// one precision mode per translation unit (udf_mlp_<mode>.hip) so that the modes compile in parallel
+// the value / grad_x launch of mlp_variant's choice (udf_mlp.hip): 3 = the reverse sweep, else fs2
+template <int MODE>
+int launch_mlp_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, float* grad3, hipStream_t st,
+                    int variant, int32_t* err, void* scratch, const CompositeFuse* fuse) {
+    if (variant == 3) return launch_mlp_rev32_mode<MODE>(L, packed, src, P, udf, grad3, st, err, scratch, fuse);
+    return launch_mlp_fs2_mode<MODE>(L, packed, src, P, udf, grad3, st, err);
+}
+
+// one precision mode per translation unit (udf_mlp_<mode>.hip: mlp_unit_<mode>() returns mlp_unit_of<MODE>()) so that the modes compile in parallel.
+// A function, not a const table at namespace scope: HIP would make that a device variable too, which cannot refer to host functions.
+template <int MODE>
+const MlpUnit* mlp_unit_of() {
+    static const MlpUnit u = {launch_mlp_mode<MODE>, launch_is_mode<MODE>, launch_vjp_sweep_mode<MODE>};
+    return &u;
+}
 }  // namespace emap

@@ -1128,7 +1128,8 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
         return EMAP_E_INVALID;
     }
     if (a.n_tiles <= 0) return EMAP_OK;
-    const int wg_cap = (NW == 8) ? REV_MAX_WG / 3 : (REV_MAX_WG * 2) / 3;   // resident workgroups: one (8 waves, 128 points) or two per CU
+    constexpr int wg_cap = (NW == 8) ? REV_MAX_WG / 3 : (REV_MAX_WG * 2) / 3;   // resident workgroups: one (8 waves, 128 points) or two per CU
+    static_assert(NW != 4 || wg_cap == REV_WG_CAP_4W, "comp_list_entries bounds the fused tail's ray list with this grid cap");
     const int grid = a.n_tiles < wg_cap ? a.n_tiles : wg_cap;
     // sigma' slabs: caller-provided (emap_render_workspace_bytes / emap_udf_scratch_bytes include them) - no allocation here
     if (!scratch) { set_error("udf_mlp_rev32: no scratch buffer (pass the buffer sized by emap_udf_scratch_bytes)"); return EMAP_E_WORKSPACE; }
