@@ -84,6 +84,13 @@ struct NetLayout {
 // unit layout: fp6 registers q0..q3 of block (t, part6) at (2 t + part6) KiB + 16 lane; q4..q5 at 4 KiB + (2 t + part6) 512 + 8 lane;
 // scale bytes at 6 KiB + 4 lane + (2 t + part6)      (part6: 0 = W_hi6, 1 = W_lo6, whose byte already undoes the x 2^11 of the lo parts)
 constexpr int SWM_UNIT_BYTES = 6656;
+// Section sizes: build_layout places the blocks with them, the pack bodies (udf_mlp.hip) find their block with them.
+// fragments of layer l's transposed hidden-row block (t_off[l]) and of a transposed PE block (tpe_off[l])
+__host__ __device__ inline int t_hidden_frags(const NetLayout& L, int l) { return ((L.layer[l].in_prev + 31) / 32) * (L.H / 32) * 2 * L.nparts; }
+__host__ __device__ inline int t_pe_frags(const NetLayout& L) { return 2 * (L.H / 32) * 2 * L.nparts; }
+// swm units of forward layer l (swm_unit[l]) and of reverse step l (swm_t_unit[l])
+__host__ __device__ inline int swm_fwd_units(const NetLayout& L, int l) { return L.layer[l].n_pairs * (L.H / 128); }
+__host__ __device__ inline int swm_rev_units(const NetLayout& L, int l) { return ((L.layer[l].in_prev + 31) / 32) * (L.H / 128); }
 
 // The transposed 32x32 section in the MIXED layout of the MX-fp6 reverse sweep (udf_mlp.hip:pack32_t_body, udf_mlp_rev32.inc):
 // split-fp16 at d_hidden = 256 (a sweep wave owns two row tiles = one 32-value MX block per lane)

@@ -20,6 +20,10 @@ long long* prof_clk_here() {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x6 __attribute__((ext_vector_type(6)));
 __host__ __device__ constexpr bool prec_is_f16(int mode) { return mode == EMAP_PREC_F16 || mode == EMAP_PREC_F16X3 || mode == EMAP_PREC_F16X3M || mode == EMAP_PREC_F16X3E; }
 __host__ __device__ constexpr int prec_nparts(int mode) { return (mode == EMAP_PREC_BF16 || mode == EMAP_PREC_F16) ? 1 : 2; }
 
@@ -60,147 +64,23 @@ __global__ __launch_bounds__(256) void rowscale_kernel(const PackArgs a) {
     }
 }
 
-// W_l[o][col] * rowscale * mult, or 0 outside the matrix - the two loads are UNCONDITIONAL on clamped indices (a branch per element kept
-// the compiler from batching the 8 / 32 independent gathers of a thread: each waited for its own round trip)
-__device__ __forceinline__ float packed_weight(const PackArgs& a, const float* rs, int l, int H, int o, int col, int out_dim, int n_in, float mult) {
+// W_l[o][col] = rowscale * v * mult (1/sqrt(2) on the skip layer: cat([x, PE]) / sqrt(2), udf_model.py:100), or 0 outside the matrix - the two
+// loads are UNCONDITIONAL on clamped indices (a branch per element kept the compiler from batching the 8 / 32 independent gathers of a thread:
+// each waited for its own round trip)
+__device__ __forceinline__ float layer_weight(const PackArgs& a, int l, int o, int col) {
+    const int out_dim = a.L.layer[l].out_dim, n_in = a.in_dim[l];
+    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
+    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;
     const bool ok = (o < out_dim) & (col >= 0) & (col < n_in);
     const int oc = min(max(o, 0), out_dim - 1), cc = min(max(col, 0), n_in - 1);
-    const float w = rs[l * H + oc] * a.v[l][(size_t)oc * n_in + cc] * mult;
+    const float w = rs[l * a.L.H + oc] * a.v[l][(size_t)oc * n_in + cc] * mult;
     return ok ? w : 0.f;
 }
 
-__device__ __forceinline__ void pack_body(const PackArgs& a, unsigned block) {
-    const long long gid = (long long)block * 256 + threadIdx.x;  // one thread per (fragment, lane)
-    const long long F = gid >> 6;
-    const int lane = (int)(gid & 63);
-    if (F >= a.L.total_frags) return;
-    int l = 0;
-    while (l + 1 < a.L.n_lin && F >= a.L.layer[l + 1].frag_off) ++l;
-    const LayerDesc Ld = a.L.layer[l];
-    const int H = a.L.H, NP = a.L.nparts, d0 = a.L.d0, M = a.L.multires;
-    int idx = (int)(F - Ld.frag_off);
-    const int part = idx % NP; idx /= NP;
-    const int t = idx & 1; idx >>= 1;
-    const int n_ks = Ld.pe_ks + Ld.h_ks;
-    const int s = idx % n_ks;
-    const int p = idx / n_ks;
-    const int i = lane & 15, g = lane >> 4;
-    const int o = 32 * p + 16 * t + i;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;  // cat([x, PE]) / sqrt(2), udf_model.py:100
-    const int n_in = a.in_dim[l];
-    const bool f16 = a.L.is_f16 != 0;
-    bf16x8 outv;
-    f16x8 outh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        int col = -1;
-        if (s < Ld.pe_ks) {
-            // PE block slot (sp, g, e): pair q = 4*sp + e/2 -> angle a = 8*g + q; kind = e&1 (sin|cos)
-            const int q = 4 * s + (e >> 1), ang = 8 * g + q, kind = e & 1;
-            int pcol = -1;
-            if (ang < 3 * M) {
-                const int k = ang / 3, c = ang - 3 * k;
-                pcol = 3 + 6 * k + (kind ? 3 + c : c);
-            } else if (ang == 3 * M) {
-                pcol = kind ? 1 : 0;
-            } else if (ang == 3 * M + 1) {
-                pcol = kind ? -1 : 2;
-            }
-            if (pcol >= 0 && pcol < d0) col = (l == 0) ? pcol : Ld.in_prev + pcol;
-        } else {
-            const int sh = s - Ld.pe_ks;
-            const int f = 16 * (2 * sh + (e >> 2)) + 4 * g + (e & 3);
-            if (f < Ld.in_prev) col = f;
-        }
-        const float w = packed_weight(a, rs, l, H, o, col, Ld.out_dim, n_in, mult);
-        const __bf16 hi = (__bf16)w;
-        outv[e] = (part == 0) ? hi : (__bf16)(w - (float)hi);
-        const _Float16 hh = (_Float16)w;
-        outh[e] = (part == 0) ? hh : (_Float16)((w - (float)hh) * 2048.0f);  // lo parts scaled by 2^11 (split-fp16)
-    }
-    char* dst = a.packed + a.L.frag_off_bytes + F * FRAG_BYTES + lane * 16;
-    if (f16) *reinterpret_cast<f16x8*>(dst) = outh;
-    else *reinterpret_cast<bf16x8*>(dst) = outv;
-}
-
-// Transposed fragments for the reverse sweep: A operand of  delta_in = W_l^T * delta_z_l.
-//   hidden rows: row f = 32*p + 16*t + i is input feature f of layer l (natural order, = the C-fragment row of the
-//                forward output a_{l-1}, so sigma' stashed by the forward sweep lines up lane for lane);
-//   PE rows:     row (tile tau = 2*pp + t, i = 4*gc + r) is PE slot (sp = pp, gc, e = 4*t + r) - the slot lane group gc
-//                itself produced in the forward PE block;
-//   k element (s, g, e) is output feature 16*(2s + e/4) + 4g + e%4 of layer l (the usual permutation).
-__device__ __forceinline__ void pack_t_body(const PackArgs& a, unsigned block) {
-    const long long gid = (long long)block * 256 + threadIdx.x;
-    const long long F = gid >> 6;
-    const int lane = (int)(gid & 63);
-    if (F >= a.L.t_total_frags) return;
-    const int H = a.L.H, NP = a.L.nparts, d0 = a.L.d0, M = a.L.multires, NKS = H / 32;
-    // locate the block
-    int l = -1; bool pe = false; int base = 0;
-    for (int q = 0; q < a.L.n_lin; ++q) {
-        if (q >= 1 && q < a.L.n_lin - 1) {
-            const int n = ((a.L.layer[q].in_prev + 31) / 32) * NKS * 2 * NP;
-            if (F >= a.L.t_off[q] && F < a.L.t_off[q] + n) { l = q; pe = false; base = a.L.t_off[q]; }
-        }
-        if (q == 0 || q == a.L.skip_l) {
-            const int n = 2 * NKS * 2 * NP;
-            if (F >= a.L.tpe_off[q] && F < a.L.tpe_off[q] + n) { l = q; pe = true; base = a.L.tpe_off[q]; }
-        }
-    }
-    if (l < 0) return;
-    const LayerDesc Ld = a.L.layer[l];
-    int idx = (int)(F - base);
-    const int part = idx % NP; idx /= NP;
-    const int t = idx & 1; idx >>= 1;
-    const int s = idx % NKS;
-    const int p = idx / NKS;
-    const int i = lane & 15, g = lane >> 4;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;
-    const int n_in = a.in_dim[l];
-    int col = -1;   // column of W_l this row stands for
-    if (!pe) {
-        const int f = 32 * p + 16 * t + i;
-        if (f < Ld.in_prev) col = f;
-    } else {
-        const int gc = i >> 2, r = i & 3, e_pe = 4 * t + r;
-        const int q = 4 * p + (e_pe >> 1), ang = 8 * gc + q, kind = e_pe & 1;
-        int pcol = -1;
-        if (ang < 3 * M) {
-            const int k = ang / 3, c = ang - 3 * k;
-            pcol = 3 + 6 * k + (kind ? 3 + c : c);
-        } else if (ang == 3 * M) {
-            pcol = kind ? 1 : 0;
-        } else if (ang == 3 * M + 1) {
-            pcol = kind ? -1 : 2;
-        }
-        if (pcol >= 0 && pcol < d0) col = (l == 0) ? pcol : Ld.in_prev + pcol;
-    }
-    const bool f16 = a.L.is_f16 != 0;
-    bf16x8 outv;
-    f16x8 outh;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int o = 16 * (2 * s + (e >> 2)) + 4 * g + (e & 3);
-        const float w = packed_weight(a, rs, l, H, o, col, Ld.out_dim, n_in, mult);
-        const __bf16 hi = (__bf16)w;
-        outv[e] = (part == 0) ? hi : (__bf16)(w - (float)hi);
-        const _Float16 hh = (_Float16)w;
-        outh[e] = (part == 0) ? hh : (_Float16)((w - (float)hh) * 2048.0f);
-    }
-    char* dst = a.packed + a.L.t_frag_off_bytes + F * FRAG_BYTES + lane * 16;
-    if (f16) *reinterpret_cast<f16x8*>(dst) = outh;
-    else *reinterpret_cast<bf16x8*>(dst) = outv;
-}
-
-
-// ---- fragments in the K order of the 32x32x16 kernels (udf_mlp_rev32.inc) -------------------------------------------------
-// A operand of v_mfma_f32_32x32x16: lane (hh = lane>>5, i = lane&31) holds row i, k = 8*hh + e.  One fragment = 32 output
-// features x 16 k; fragment order = layer, row tile p, K32-step S (PE block first), u (K16 half), part (hi, lo).
-//   hidden k-slot (S, u, hh, e) = feature 32S + (e&3) + 8(2u + (e>>2)) + 4hh  (register r = 8u + e of the lane's C fragment)
-//   PE k-slot (S, u, hh, e): angle index 16hh + 8S + 4u + (e>>1), kind (sin|cos) = e&1
-__device__ __forceinline__ int pe_col_of(int ang, int kind, int M, int d0) {
+// column of W_l that PE slot (angle index ang, kind 0 = sin | 1 = cos) stands for, -1 if none: angle ang = 3k + c is sin / cos of
+// frequency k of coordinate c, the two slots after the last angle hold the raw coordinates (x | y), (z | -)
+__device__ __forceinline__ int pe_col(const PackArgs& a, int l, int ang, int kind) {
+    const int M = a.L.multires;
     int pcol = -1;
     if (ang < 3 * M) {
         const int k = ang / 3, c = ang - 3 * k;
@@ -210,8 +90,28 @@ __device__ __forceinline__ int pe_col_of(int ang, int kind, int M, int d0) {
     } else if (ang == 3 * M + 1) {
         pcol = kind ? -1 : 2;
     }
-    return (pcol >= 0 && pcol < d0) ? pcol : -1;
+    return (pcol < 0) ? -1 : (l == 0) ? pcol : a.L.layer[l].in_prev + pcol;
 }
+
+// layer of forward fragment F
+__device__ __forceinline__ int frag_layer(const NetLayout& L, long long F) {
+    int l = 0;
+    while (l + 1 < L.n_lin && F >= L.layer[l + 1].frag_off) ++l;
+    return l;
+}
+
+// block of transposed fragment F: layer l (-1 if F is in none), PE rows or hidden rows, first fragment
+struct TBlock { int l; bool pe; int base; };
+__device__ __forceinline__ TBlock t_block(const NetLayout& L, long long F) {
+    TBlock b{-1, false, 0};
+    for (int q = 0; q < L.n_lin; ++q) {
+        if (q >= 1 && q < L.n_lin - 1 && F >= L.t_off[q] && F < L.t_off[q] + t_hidden_frags(L, q)) b = TBlock{q, false, L.t_off[q]};
+        if ((q == 0 || q == L.skip_l) && F >= L.tpe_off[q] && F < L.tpe_off[q] + t_pe_frags(L)) b = TBlock{q, true, L.tpe_off[q]};
+    }
+    return b;
+}
+
+// part 0 (hi) or 1 (lo) of the lane's 8 weights as one 16-byte lane slot of a fragment
 __device__ __forceinline__ void store_frag(const PackArgs& a, char* dst, const float (&w)[8], int part) {
     bf16x8 outv;
     f16x8 outh;
@@ -226,8 +126,90 @@ __device__ __forceinline__ void store_frag(const PackArgs& a, char* dst, const f
     else *reinterpret_cast<bf16x8*>(dst) = outv;
 }
 
-typedef _Float16 f16x32 __attribute__((ext_vector_type(32)));
-typedef uint32_t u32x6 __attribute__((ext_vector_type(6)));
+// One lane's MX block of 32 weights in split-fp16: the f16 hi parts, and the hi and lo parts (lo x 2^11) as e2m3 with their E8M0 bytes
+// (the lo byte undoes the x 2^11), through v_cvt_scalef32_pk32_fp6_f16 - the instruction the sweeps use for their B operands (probed:
+// natural element order, x / scale, RNE, saturating; profiles/r04_probe_fp6.txt)
+struct Mx6Block {
+    f16x32 hi16;
+    u32x6 qh, ql;
+    uint8_t bh, bl;
+};
+__device__ __forceinline__ Mx6Block quantise_mx6(const float (&w)[32]) {
+    Mx6Block r;
+    f16x32 vl;
+    float mh = 0.f, ml = 0.f;
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        const _Float16 h16 = (_Float16)w[e];
+        const _Float16 l16 = (_Float16)((w[e] - (float)h16) * 2048.0f);
+        r.hi16[e] = h16; vl[e] = l16;
+        mh = fmaxf(mh, fabsf((float)h16));
+        ml = fmaxf(ml, fabsf((float)l16));
+    }
+    const uint32_t sbh = mx6_scale_bits(mh), sbl = mx6_scale_bits(ml);
+    r.qh = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(r.hi16, __builtin_bit_cast(float, sbh));
+    r.ql = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vl, __builtin_bit_cast(float, sbl));
+    r.bh = (uint8_t)(sbh >> 23);
+    r.bl = (uint8_t)((sbl >> 23) - 11u);
+    return r;
+}
+
+__device__ __forceinline__ void pack_body(const PackArgs& a, unsigned block) {
+    const long long F = (long long)block * 4 + (threadIdx.x >> 6);  // one thread per (fragment, lane)
+    const int lane = threadIdx.x & 63;
+    if (F >= a.L.total_frags) return;
+    const int l = frag_layer(a.L, F);
+    const LayerDesc Ld = a.L.layer[l];
+    int idx = (int)(F - Ld.frag_off);
+    const int part = idx % a.L.nparts; idx /= a.L.nparts;
+    const int t = idx & 1; idx >>= 1;
+    const int n_ks = Ld.pe_ks + Ld.h_ks;
+    const int s = idx % n_ks, p = idx / n_ks;
+    const int i = lane & 15, g = lane >> 4;
+    float w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        // PE block slot (s, g, e): pair q = 4*s + e/2 -> angle 8*g + q, kind = e&1 (sin|cos); hidden k-slot: the usual permutation
+        const int f = 16 * (2 * (s - Ld.pe_ks) + (e >> 2)) + 4 * g + (e & 3);
+        const int col = (s < Ld.pe_ks) ? pe_col(a, l, 8 * g + 4 * s + (e >> 1), e & 1) : (f < Ld.in_prev) ? f : -1;
+        w[e] = layer_weight(a, l, 32 * p + 16 * t + i, col);
+    }
+    store_frag(a, a.packed + a.L.frag_off_bytes + F * FRAG_BYTES + lane * 16, w, part);
+}
+
+// Transposed fragments for the reverse sweep: A operand of  delta_in = W_l^T * delta_z_l.
+//   hidden rows: row f = 32*p + 16*t + i is input feature f of layer l (natural order, = the C-fragment row of the
+//                forward output a_{l-1}, so sigma' stashed by the forward sweep lines up lane for lane);
+//   PE rows:     row (tile tau = 2*pp + t, i = 4*gc + r) is PE slot (sp = pp, gc, e = 4*t + r) - the slot lane group gc
+//                itself produced in the forward PE block;
+//   k element (s, g, e) is output feature 16*(2s + e/4) + 4g + e%4 of layer l (the usual permutation).
+__device__ __forceinline__ void pack_t_body(const PackArgs& a, unsigned block) {
+    const long long F = (long long)block * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (F >= a.L.t_total_frags) return;
+    const TBlock b = t_block(a.L, F);
+    if (b.l < 0) return;
+    const int NKS = a.L.H / 32;
+    int idx = (int)(F - b.base);
+    const int part = idx % a.L.nparts; idx /= a.L.nparts;
+    const int t = idx & 1; idx >>= 1;
+    const int s = idx % NKS, p = idx / NKS;
+    const int i = lane & 15, g = lane >> 4;
+    // column of W_l this row stands for
+    const int f = 32 * p + 16 * t + i, e_pe = 4 * t + (i & 3);
+    const int col = b.pe ? pe_col(a, b.l, 8 * (i >> 2) + 4 * p + (e_pe >> 1), e_pe & 1) : (f < a.L.layer[b.l].in_prev) ? f : -1;
+    float w[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) w[e] = layer_weight(a, b.l, 16 * (2 * s + (e >> 2)) + 4 * g + (e & 3), col);
+    store_frag(a, a.packed + a.L.t_frag_off_bytes + F * FRAG_BYTES + lane * 16, w, part);
+}
+
+
+// ---- fragments in the K order of the 32x32x16 kernels (udf_mlp_rev32.inc) -------------------------------------------------
+// A operand of v_mfma_f32_32x32x16: lane (hh = lane>>5, i = lane&31) holds row i, k = 8*hh + e.  One fragment = 32 output
+// features x 16 k; fragment order = layer, row tile p, K32-step S (PE block first), u (K16 half), part (hi, lo).
+//   hidden k-slot (S, u, hh, e) = feature 32S + (e&3) + 8(2u + (e>>2)) + 4hh  (register r = 8u + e of the lane's C fragment)
+//   PE k-slot (S, u, hh, e): angle index 16hh + 8S + 4u + (e>>1), kind (sin|cos) = e&1
 
 // The 8 KiB block of one (row tile, K64-step Sg) in the MIXED layout of the MX-fp6 sweeps (layout: see pack32_t_body), written by thread f = 0 of
 // each lane - the fragment-granular grid of pack_all_kernel gives a block eight waves, seven of them exit: one thread evaluates the lane's 32
@@ -235,45 +217,32 @@ typedef uint32_t u32x6 __attribute__((ext_vector_type(6)));
 // maxima: 416 weight evaluations per lane and block instead of 32, and the re-pack of a training step took 154 us instead of 17).
 // weight(S, u, e) = the element of K32-step S, K16-step u, k-slot e of this lane's row.
 template <class WF>
-__device__ __forceinline__ void store_mixed_block(const PackArgs& a, char* blk, int lane, int f, int Sg, int NSG, WF&& weight) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void store_mixed_block(char* blk, int lane, int f, int Sg, int NSG, WF&& weight) {
     if (f != 0) return;
-    f16x32 vh, vl;
-    float mh = 0.f, ml = 0.f;
+    float w[32];
 #pragma unroll
-    for (int e = 0; e < 32; ++e) {       // element order of the lane's MX block: e = 16 t + 8 u + e'  <->  (S = 2 Sg + t, u, e')
-        const float w = weight(2 * Sg + (e >> 4), (e >> 3) & 1, e & 7);
-        const _Float16 h16 = (_Float16)w;
-        const _Float16 l16 = (_Float16)((w - (float)h16) * 2048.0f);
-        vh[e] = h16; vl[e] = l16;
-        mh = fmaxf(mh, fabsf((float)h16));
-        ml = fmaxf(ml, fabsf((float)l16));
-    }
+    for (int e = 0; e < 32; ++e)          // element order of the lane's MX block: e = 16 t + 8 u + e'  <->  (S = 2 Sg + t, u, e')
+        w[e] = weight(2 * Sg + (e >> 4), (e >> 3) & 1, e & 7);
+    const Mx6Block q = quantise_mx6(w);
     // @0..3 KiB: the four hi16 fragments (t, u)
-    typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        f16x8v o;
+    for (int k = 0; k < 4; ++k) {
+        f16x8 o;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = vh[8 * q + e];
-        *reinterpret_cast<f16x8v*>(blk + q * FRAG_BYTES + lane * 16) = o;
+        for (int e = 0; e < 8; ++e) o[e] = q.hi16[8 * k + e];
+        *reinterpret_cast<f16x8*>(blk + k * FRAG_BYTES + lane * 16) = o;
     }
-    // fp6 forms and their E8M0 bytes (lo parts are stored x 2^11: undone in the byte)
-    const uint32_t sbh = mx6_scale_bits(mh), sbl = mx6_scale_bits(ml);
-    const u32x6 qh = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vh, __builtin_bit_cast(float, sbh));
-    const u32x6 ql = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vl, __builtin_bit_cast(float, sbl));
-    *reinterpret_cast<u32x4*>(blk + 4 * FRAG_BYTES + lane * 16) = u32x4{qh[0], qh[1], qh[2], qh[3]};
-    *reinterpret_cast<u32x4*>(blk + 5 * FRAG_BYTES + lane * 16) = u32x4{ql[0], ql[1], ql[2], ql[3]};
-    *reinterpret_cast<u32x2*>(blk + 6 * FRAG_BYTES + lane * 8) = u32x2{qh[4], qh[5]};
-    *reinterpret_cast<u32x2*>(blk + 6 * FRAG_BYTES + 512 + lane * 8) = u32x2{ql[4], ql[5]};
+    // fp6 forms
+    *reinterpret_cast<u32x4*>(blk + 4 * FRAG_BYTES + lane * 16) = u32x4{q.qh[0], q.qh[1], q.qh[2], q.qh[3]};
+    *reinterpret_cast<u32x4*>(blk + 5 * FRAG_BYTES + lane * 16) = u32x4{q.ql[0], q.ql[1], q.ql[2], q.ql[3]};
+    *reinterpret_cast<u32x2*>(blk + 6 * FRAG_BYTES + lane * 8) = u32x2{q.qh[4], q.qh[5]};
+    *reinterpret_cast<u32x2*>(blk + 6 * FRAG_BYTES + 512 + lane * 8) = u32x2{q.ql[4], q.ql[5]};
     // @7 KiB of block Sg' (8 B / lane): bytes 2 j + (hi6 | lo6) = the scales of step Sg' + j, j = 0..3.  This thread owns the bytes of ITS step in
     // the slots of blocks Sg, Sg - 1, Sg - 2, Sg - 3 (byte stores) and zeroes the bytes of its own slot that belong to no step
-    const uint8_t bh = (uint8_t)(sbh >> 23), bl = (uint8_t)((sbl >> 23) - 11u);
     for (int j = 0; j < 4; ++j) {
         if (Sg - j >= 0) {
             uint8_t* slot = reinterpret_cast<uint8_t*>(blk - (ptrdiff_t)j * 8 * FRAG_BYTES + 7 * FRAG_BYTES + lane * 8);
-            slot[2 * j] = bh; slot[2 * j + 1] = bl;
+            slot[2 * j] = q.bh; slot[2 * j + 1] = q.bl;
         }
         if (Sg + j >= NSG) {
             uint8_t* own = reinterpret_cast<uint8_t*>(blk + 7 * FRAG_BYTES + lane * 8);
@@ -283,42 +252,30 @@ __device__ __forceinline__ void store_mixed_block(const PackArgs& a, char* blk, 
 }
 
 __device__ __forceinline__ void pack32_body(const PackArgs& a, unsigned block) {
-    const long long gid = (long long)block * 256 + threadIdx.x;  // one thread per (fragment, lane)
-    const long long F = gid >> 6;
-    const int lane = (int)(gid & 63);
+    const long long F = (long long)block * 4 + (threadIdx.x >> 6);  // one thread per (fragment, lane)
+    const int lane = threadIdx.x & 63;
     if (F >= a.L.total_frags) return;
-    int l = 0;
-    while (l + 1 < a.L.n_lin && F >= a.L.layer[l + 1].frag_off) ++l;
+    const int l = frag_layer(a.L, F);
     const LayerDesc Ld = a.L.layer[l];
-    const int H = a.L.H, NP = a.L.nparts, d0 = a.L.d0, M = a.L.multires;
     int idx = (int)(F - Ld.frag_off);
     const int n_ks = Ld.pe_ks + Ld.h_ks;
     const int i = lane & 31, hh = lane >> 5;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;  // cat([x, PE]) / sqrt(2), udf_model.py:100
-    const int n_in = a.in_dim[l];
     // element (K32-step S, K16-step u, k-slot e) of row o
     auto weight = [&](int o, int S, int u, int e) -> float {
-        int col = -1;
-        if (S < Ld.pe_ks) {
-            const int pcol = pe_col_of(16 * hh + 8 * S + 4 * u + (e >> 1), e & 1, M, d0);
-            if (pcol >= 0) col = (l == 0) ? pcol : Ld.in_prev + pcol;
-        } else {
-            const int f = 32 * (S - Ld.pe_ks) + (e & 3) + 8 * (2 * u + (e >> 2)) + 4 * hh;
-            if (f < Ld.in_prev) col = f;
-        }
-        return packed_weight(a, rs, l, H, o, col, Ld.out_dim, n_in, mult);
+        const int f = 32 * (S - Ld.pe_ks) + (e & 3) + 8 * (2 * u + (e >> 2)) + 4 * hh;
+        const int col = (S < Ld.pe_ks) ? pe_col(a, l, 16 * hh + 8 * S + 4 * u + (e >> 1), e & 1) : (f < Ld.in_prev) ? f : -1;
+        return layer_weight(a, l, o, col);
     };
     if (r32_mixed(a.L)) {      // MX-fp6 forward sweep: one 8 KiB block per (row tile, K64-step) - every layer has an even number of K32-steps
         const int f = idx & 7; idx >>= 3;
         const int NSG = n_ks / 2;
         const int Sg = idx % NSG;
         const int o = 32 * (idx / NSG) + i;
-        store_mixed_block(a, a.packed + a.L.r32_frag_off_bytes + (F - f) * FRAG_BYTES, lane, f, Sg, NSG,
+        store_mixed_block(a.packed + a.L.r32_frag_off_bytes + (F - f) * FRAG_BYTES, lane, f, Sg, NSG,
                           [&](int S, int u, int e) -> float { return weight(o, S, u, e); });
         return;
     }
-    const int part = idx % NP; idx /= NP;
+    const int part = idx % a.L.nparts; idx /= a.L.nparts;
     const int u = idx & 1; idx >>= 1;
     const int S = idx % n_ks;
     const int o = 32 * (idx / n_ks) + i;
@@ -335,54 +292,31 @@ __device__ __forceinline__ void pack32_body(const PackArgs& a, unsigned block) {
 //                lane half hc holds in register r of its C fragment and in its own PE fragment;
 //   k element (S, u, hh, e) is output feature 32S + (e&3) + 8(2u + (e>>2)) + 4hh of layer l.
 __device__ __forceinline__ void pack32_t_body(const PackArgs& a, unsigned block) {
-    const long long gid = (long long)block * 256 + threadIdx.x;
-    const long long F = gid >> 6;
-    const int lane = (int)(gid & 63);
+    const long long F = (long long)block * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
     if (F >= a.L.t_total_frags) return;
-    const int H = a.L.H, NP = a.L.nparts, d0 = a.L.d0, M = a.L.multires, NKS = H / 32;
-    int l = -1; bool pe = false; int base = 0;
-    for (int q = 0; q < a.L.n_lin; ++q) {
-        if (q >= 1 && q < a.L.n_lin - 1) {
-            const int n = ((a.L.layer[q].in_prev + 31) / 32) * NKS * 2 * NP;
-            if (F >= a.L.t_off[q] && F < a.L.t_off[q] + n) { l = q; pe = false; base = a.L.t_off[q]; }
-        }
-        if (q == 0 || q == a.L.skip_l) {
-            const int n = 2 * NKS * 2 * NP;
-            if (F >= a.L.tpe_off[q] && F < a.L.tpe_off[q] + n) { l = q; pe = true; base = a.L.tpe_off[q]; }
-        }
-    }
-    if (l < 0) return;
-    const LayerDesc Ld = a.L.layer[l];
-    int idx = (int)(F - base);
+    const TBlock b = t_block(a.L, F);
+    if (b.l < 0) return;
+    const int NKS = a.L.H / 32;
+    int idx = (int)(F - b.base);
     const int i = lane & 31, hh = lane >> 5;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;
-    const int n_in = a.in_dim[l];
     // row i of row tile p -> column `col` of W_l
     auto col_of = [&](int p) -> int {
-        if (!pe) {
-            const int f = 32 * p + i;
-            return (f < Ld.in_prev) ? f : -1;
-        }
-        const int hc = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3);
-        const int pcol = pe_col_of(16 * hc + 8 * p + 4 * (r >> 3) + ((r & 7) >> 1), r & 1, M, d0);
-        return (pcol >= 0) ? ((l == 0) ? pcol : Ld.in_prev + pcol) : -1;
+        const int f = 32 * p + i, hc = (i >> 2) & 1, r = (i & 3) + 4 * (i >> 3);
+        return b.pe ? pe_col(a, b.l, 16 * hc + 8 * p + 4 * (r >> 3) + ((r & 7) >> 1), r & 1) : (f < a.L.layer[b.l].in_prev) ? f : -1;
     };
     auto weight = [&](int col, int S, int u, int e) -> float {
-        const int o = 32 * S + (e & 3) + 8 * (2 * u + (e >> 2)) + 4 * hh;
-        return packed_weight(a, rs, l, H, o, col, Ld.out_dim, n_in, mult);
+        return layer_weight(a, b.l, 32 * S + (e & 3) + 8 * (2 * u + (e >> 2)) + 4 * hh, col);
     };
-    char* dst = a.packed + a.L.r32_t_frag_off_bytes + F * FRAG_BYTES + lane * 16;
     if (!r32_t_mixed(a.L)) {
-        const int part = idx % NP; idx /= NP;
+        const int part = idx % a.L.nparts; idx /= a.L.nparts;
         const int u = idx & 1; idx >>= 1;
         const int S = idx % NKS;
-        const int p = idx / NKS;
-        const int col = col_of(p);
+        const int col = col_of(idx / NKS);
         float w[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) w[e] = weight(col, S, u, e);
-        store_frag(a, dst, w, part);
+        store_frag(a, a.packed + a.L.r32_t_frag_off_bytes + F * FRAG_BYTES + lane * 16, w, part);
         return;
     }
     // ---- mixed layout (split-fp16, d_hidden = 256): one 8 KiB block per (row tile p, K64-step Sg):
@@ -393,14 +327,12 @@ __device__ __forceinline__ void pack32_t_body(const PackArgs& a, unsigned block)
     // The cross terms W_hi x_lo + W_lo x_hi of the reverse sweep run as MX-scaled fp6 (e2m3) MFMAs of K = 64
     // (v_mfma_scale_f32_32x32x64_f8f6f4, 4x the f16 rate; docs/DESIGN_LOG_r1-r4.md par. 6c): lane (hh, i) of an fp6 block holds the 32 k-slots
     // e = 16 pi + 8 u + e' <-> (S = 2Sg + pi, u, hh, e') of row i - the order in which a sweep lane holds its two row tiles' outputs -
-    // as six registers of e2m3.  hi6 quantises the f16 hi parts, lo6 the lo parts (x 2^11 in f16, undone in the scale byte); both
-    // through v_cvt_scalef32_pk32_fp6_f16, the instruction the sweep itself uses for its B operands (probed: natural element order,
-    // x / scale, RNE, saturating; profiles/r04_probe_fp6.txt).
+    // as six registers of e2m3.  hi6 quantises the f16 hi parts, lo6 the lo parts (quantise_mx6).
     const int f = idx & 7; idx >>= 3;
     const int NSG = NKS / 2;
     const int Sg = idx % NSG;
     const int col = col_of(idx / NSG);
-    store_mixed_block(a, a.packed + a.L.r32_t_frag_off_bytes + (F - f) * FRAG_BYTES, lane, f, Sg, NSG,
+    store_mixed_block(a.packed + a.L.r32_t_frag_off_bytes + (F - f) * FRAG_BYTES, lane, f, Sg, NSG,
                       [&](int S, int u, int e) -> float { return weight(col, S, u, e); });
 }
 
@@ -408,63 +340,45 @@ __device__ __forceinline__ void pack32_t_body(const PackArgs& a, unsigned block)
 // pair and the 32 k-values of K-step 4 S + kb in the element order idx = 8 g' + e  <->  feature 16 (2 s + (e >> 2)) + 4 g' + (e & 3): exactly what
 // the four lanes (g', i) of the f16 fragment (s, t) hold, and on the B side what the four lanes (g', column) of an output fragment hold.
 __device__ __forceinline__ void pack_swm_body(const PackArgs& a, unsigned block) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const long long gid = (long long)block * 256 + threadIdx.x;
     const int unit = (int)(gid >> 7), t = (int)((gid >> 6) & 1), lane = (int)(gid & 63);
     if (unit >= a.L.swm_units) return;
-    const int H = a.L.H, n128 = H / 128;
     int l = -1; bool tr = false;
     for (int q = 1; q < a.L.n_lin; ++q) {
-        if (a.L.swm_unit[q] >= 0 && unit >= a.L.swm_unit[q] && unit < a.L.swm_unit[q] + a.L.layer[q].n_pairs * n128) { l = q; tr = false; }
-        if (a.L.swm_t_unit[q] >= 0 && unit >= a.L.swm_t_unit[q] && unit < a.L.swm_t_unit[q] + ((a.L.layer[q].in_prev + 31) / 32) * n128) { l = q; tr = true; }
+        if (a.L.swm_unit[q] >= 0 && unit >= a.L.swm_unit[q] && unit < a.L.swm_unit[q] + swm_fwd_units(a.L, q)) { l = q; tr = false; }
+        if (a.L.swm_t_unit[q] >= 0 && unit >= a.L.swm_t_unit[q] && unit < a.L.swm_t_unit[q] + swm_rev_units(a.L, q)) { l = q; tr = true; }
     }
     if (l < 0) return;
-    const LayerDesc Ld = a.L.layer[l];
+    const int n128 = a.L.H / 128;
     const int u = unit - (tr ? a.L.swm_t_unit[l] : a.L.swm_unit[l]);
     const int p = u / n128, S = u % n128;
     const int i = lane & 15, kb = lane >> 4, s = 4 * S + kb;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;
-    const int n_in = a.in_dim[l];
     const int row = 32 * p + 16 * t + i;          // forward: output feature; transposed: input feature (a column of W_l)
-    f16x32 vh, vl;
-    float mh = 0.f, ml = 0.f;
+    float w[32];
 #pragma unroll
     for (int idx = 0; idx < 32; ++idx) {
         const int gq = idx >> 3, e = idx & 7;
         const int f = 16 * (2 * s + (e >> 2)) + 4 * gq + (e & 3);
         // forward: W[row][f], f < in_prev; transposed: W[f][row], row < in_prev
         const int wo = tr ? f : row, wc = tr ? row : f;
-        const float w = packed_weight(a, rs, l, H, wo, (wc < Ld.in_prev) ? wc : -1, Ld.out_dim, n_in, mult);
-        const _Float16 h16 = (_Float16)w;
-        const _Float16 l16 = (_Float16)((w - (float)h16) * 2048.0f);
-        vh[idx] = h16; vl[idx] = l16;
-        mh = fmaxf(mh, fabsf((float)h16));
-        ml = fmaxf(ml, fabsf((float)l16));
+        w[idx] = layer_weight(a, l, wo, (wc < a.L.layer[l].in_prev) ? wc : -1);
     }
-    const uint32_t sbh = mx6_scale_bits(mh), sbl = mx6_scale_bits(ml);
-    const u32x6 qh = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vh, __builtin_bit_cast(float, sbh));
-    const u32x6 ql = __builtin_amdgcn_cvt_scalef32_pk32_fp6_f16(vl, __builtin_bit_cast(float, sbl));
+    const Mx6Block q = quantise_mx6(w);
     char* ub = a.packed + a.L.swm_off_bytes + (size_t)unit * SWM_UNIT_BYTES;
-    *reinterpret_cast<u32x4*>(ub + (2 * t + 0) * 1024 + lane * 16) = u32x4{qh[0], qh[1], qh[2], qh[3]};
-    *reinterpret_cast<u32x4*>(ub + (2 * t + 1) * 1024 + lane * 16) = u32x4{ql[0], ql[1], ql[2], ql[3]};
-    *reinterpret_cast<u32x2*>(ub + 4096 + (2 * t + 0) * 512 + lane * 8) = u32x2{qh[4], qh[5]};
-    *reinterpret_cast<u32x2*>(ub + 4096 + (2 * t + 1) * 512 + lane * 8) = u32x2{ql[4], ql[5]};
+    *reinterpret_cast<u32x4*>(ub + (2 * t + 0) * 1024 + lane * 16) = u32x4{q.qh[0], q.qh[1], q.qh[2], q.qh[3]};
+    *reinterpret_cast<u32x4*>(ub + (2 * t + 1) * 1024 + lane * 16) = u32x4{q.ql[0], q.ql[1], q.ql[2], q.ql[3]};
+    *reinterpret_cast<u32x2*>(ub + 4096 + (2 * t + 0) * 512 + lane * 8) = u32x2{q.qh[4], q.qh[5]};
+    *reinterpret_cast<u32x2*>(ub + 4096 + (2 * t + 1) * 512 + lane * 8) = u32x2{q.ql[4], q.ql[5]};
     uint8_t* sc = reinterpret_cast<uint8_t*>(ub + 6144 + lane * 4);
-    sc[2 * t + 0] = (uint8_t)(sbh >> 23);
-    sc[2 * t + 1] = (uint8_t)((sbl >> 23) - 11u);
+    sc[2 * t + 0] = q.bh;
+    sc[2 * t + 1] = q.bl;
 }
 
 // fp32 copy of the last layer's real row (times its weight-norm scale): the seed of the reverse sweep
 __device__ __forceinline__ void pack_wlast_body(const PackArgs& a, unsigned block) {
-    const int f = block * 256 + threadIdx.x;
-    const int H = a.L.H, l = a.L.n_lin - 1;
-    if (f >= H) return;
-    const float* rs = reinterpret_cast<const float*>(a.packed + a.L.rowscale_off_bytes);
-    float* wl = reinterpret_cast<float*>(a.packed + a.L.wlast_off_bytes);
-    const float mult = (l == a.L.skip_l) ? 0.70710678118654752440f : 1.0f;   // skip layer == last layer (d4 networks)
-    wl[f] = (f < a.L.layer[l].in_prev) ? rs[l * H] * a.v[l][f] * mult : 0.f;
+    const int f = block * 256 + threadIdx.x, l = a.L.n_lin - 1;
+    if (f >= a.L.H) return;
+    reinterpret_cast<float*>(a.packed + a.L.wlast_off_bytes)[f] = layer_weight(a, l, 0, (f < a.L.layer[l].in_prev) ? f : -1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -517,8 +431,8 @@ int build_layout(const EmapNetConfig* cfg, int prec, NetLayout* L) {
     int tf = 0;
     for (int l = 0; l < cfg->n_lin; ++l) {
         L->t_off[l] = -1; L->tpe_off[l] = -1;
-        if (l >= 1 && l < cfg->n_lin - 1) { L->t_off[l] = tf; tf += ((L->layer[l].in_prev + 31) / 32) * (H / 32) * 2 * L->nparts; }
-        if (l == 0 || l == cfg->skip_l) { L->tpe_off[l] = tf; tf += 2 * (H / 32) * 2 * L->nparts; }
+        if (l >= 1 && l < cfg->n_lin - 1) { L->t_off[l] = tf; tf += t_hidden_frags(*L, l); }
+        if (l == 0 || l == cfg->skip_l) { L->tpe_off[l] = tf; tf += t_pe_frags(*L); }
     }
     L->t_total_frags = tf;   // always packed: the training backward (udf_mlp_vjp.inc) needs it for every topology
     L->r32_frag_off_bytes = L->t_frag_off_bytes + tf * FRAG_BYTES;
@@ -533,9 +447,8 @@ int build_layout(const EmapNetConfig* cfg, int prec, NetLayout* L) {
     L->swm_off_bytes = (int32_t)(((size_t)L->r32_t_frag_off_bytes + (size_t)tf * FRAG_BYTES + 255) & ~(size_t)255);
     for (int l = 0; l < cfg->n_lin; ++l) { L->swm_unit[l] = -1; L->swm_t_unit[l] = -1; }
     if (L->sweep_mx) {
-        const int n128 = H / 128;
-        for (int l = 1; l < cfg->n_lin; ++l) { L->swm_unit[l] = L->swm_units; L->swm_units += L->layer[l].n_pairs * n128; }
-        for (int l = 1; l < cfg->n_lin - 1; ++l) { L->swm_t_unit[l] = L->swm_units; L->swm_units += ((L->layer[l].in_prev + 31) / 32) * n128; }
+        for (int l = 1; l < cfg->n_lin; ++l) { L->swm_unit[l] = L->swm_units; L->swm_units += swm_fwd_units(*L, l); }
+        for (int l = 1; l < cfg->n_lin - 1; ++l) { L->swm_t_unit[l] = L->swm_units; L->swm_units += swm_rev_units(*L, l); }
     }
     return EMAP_OK;
 }
