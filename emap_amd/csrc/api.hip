@@ -57,36 +57,41 @@ static int device_cus() {
     return n;
 }
 
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 struct VjpPlan {
     VjpLayout V;
-    WgradJob jobs[WGRAD_MAX_JOBS];
-    int n_jobs, job_h[EMAP_MAX_LIN], job_pe[EMAP_MAX_LIN], wgrad_wg, sweep_grid, chunk_tiles;
+    WgradPlan wg;
+    int sweep_grid, chunk_tiles;
+    int64_t tiles;            // ceil(P / VJP_PT)
+    size_t tile_bytes;        // stash bytes per tile
     size_t off_absmax, off_slab, off_partial, off_ldot, off_a, off_z, total;
+    size_t min_bytes;         // the smallest workspace plan_vjp accepts for these points
 };
 
-// avail = 0: the preferred plan (chunks of up to VJP_CHUNK_TILES tiles); avail > 0: the largest chunk whose stash fits into a workspace of
-// `avail` bytes - the caller bounds the memory, the backward runs in more chunks (chunk_tiles = 0: not even VJP_MIN_CHUNK_TILES fit)
+// The plan for a workspace of `avail` bytes: chunks of up to VJP_CHUNK_TILES tiles (the preferred plan, what an unbounded workspace gets), or
+// the largest chunk whose stash fits - the caller bounds the memory, the backward runs in more chunks (chunk_tiles = 0: not even
+// VJP_MIN_CHUNK_TILES fit)
 constexpr int VJP_MIN_CHUNK_TILES = 256;
-static VjpPlan plan_vjp(const NetLayout& L, int64_t P, size_t avail = 0) {
+static VjpPlan plan_vjp(const NetLayout& L, int64_t P, size_t avail = SIZE_MAX) {
     VjpPlan pl;
     build_vjp_layout(L, &pl.V);
     const int cus = device_cus();
     pl.sweep_grid = L.H == 256 ? cus : 2 * cus;          // d_hidden 256: 8 waves, one workgroup per CU; 128: two
-    const int64_t tiles = (P + VJP_PT - 1) / VJP_PT;
-    pl.chunk_tiles = (int)std::min<int64_t>(std::max<int64_t>(tiles, 1), VJP_CHUNK_TILES);
-    const size_t pfl = plan_wgrad(L, pl.V, cus, pl.jobs, &pl.n_jobs, pl.job_h, pl.job_pe, &pl.wgrad_wg);
+    pl.tiles = (P + VJP_PT - 1) / VJP_PT;
+    const int64_t tiles1 = std::max<int64_t>(pl.tiles, 1);
+    pl.wg = plan_wgrad(L, pl.V, cus);
     size_t off = 0;
     pl.off_absmax = off; off += 256;
     pl.off_slab = off; off += (size_t)pl.sweep_grid * pl.V.s_slab_kb * 1024;
-    pl.off_partial = off; off += ((pfl * 4 + 255) & ~(size_t)255);
-    pl.off_ldot = off; off += (((size_t)std::max<int64_t>(tiles, 1) * 4 + 255) & ~(size_t)255);
+    pl.off_partial = off; off += align256(pl.wg.partial_floats * 4);
+    pl.off_ldot = off; off += align256((size_t)tiles1 * 4);
     // precise weight gradients (L.wgrad_lo): a second pair of stashes for the lo parts of both operand sets
-    const size_t per_tile = ((size_t)pl.V.a_tile_kb + (size_t)pl.V.z_tile_kb) * 1024 * (L.wgrad_lo ? 2 : 1);
-    if (avail > 0) {
-        const size_t fit = avail > off ? (avail - off) / per_tile : 0;
-        const int64_t need = std::min<int64_t>(std::max<int64_t>(tiles, 1), VJP_MIN_CHUNK_TILES);
-        pl.chunk_tiles = (int64_t)fit < need ? 0 : (int)std::min<size_t>(fit, (size_t)pl.chunk_tiles);
-    }
+    pl.tile_bytes = ((size_t)pl.V.a_tile_kb + (size_t)pl.V.z_tile_kb) * 1024 * (L.wgrad_lo ? 2 : 1);
+    const int64_t need = std::min<int64_t>(tiles1, VJP_MIN_CHUNK_TILES);
+    pl.min_bytes = off + (size_t)need * pl.tile_bytes;
+    const size_t fit = avail > off ? (avail - off) / pl.tile_bytes : 0;
+    pl.chunk_tiles = (int64_t)fit < need ? 0 : (int)std::min<size_t>(fit, (size_t)std::min<int64_t>(tiles1, VJP_CHUNK_TILES));
     pl.off_a = off; off += (size_t)pl.chunk_tiles * pl.V.a_tile_kb * 1024;
     pl.off_z = off; off += (size_t)pl.chunk_tiles * pl.V.z_tile_kb * 1024;
     pl.V.lo_a_delta = pl.V.lo_z_delta = 0;
@@ -97,13 +102,6 @@ static VjpPlan plan_vjp(const NetLayout& L, int64_t P, size_t avail = 0) {
     pl.total = off;
     return pl;
 }
-// bytes of the smallest workspace plan_vjp accepts for P points
-static size_t vjp_min_bytes(const NetLayout& L, int64_t P) {
-    const VjpPlan pl = plan_vjp(L, P);
-    const int64_t tiles = (P + VJP_PT - 1) / VJP_PT;
-    const size_t per_tile = ((size_t)pl.V.a_tile_kb + (size_t)pl.V.z_tile_kb) * 1024 * (L.wgrad_lo ? 2 : 1);
-    return pl.off_a + (size_t)std::min<int64_t>(std::max<int64_t>(tiles, 1), VJP_MIN_CHUNK_TILES) * per_tile;
-}
 
 // d/dtheta of sum_p du[p] udf(x_p) + dg[p] . grad udf(x_p); absmax must already hold max|du|, max|dg| of the launch
 static int run_vjp(const NetLayout& L, const void* packed, int prec, const PointSource& src, int64_t P, const float* d_udf,
@@ -111,35 +109,39 @@ static int run_vjp(const NetLayout& L, const void* packed, int prec, const Point
     uint32_t* absmax = reinterpret_cast<uint32_t*>(ws + pl.off_absmax);
     float* partial = reinterpret_cast<float*>(ws + pl.off_partial);
     float* ldot = reinterpret_cast<float*>(ws + pl.off_ldot);
-    const int64_t tiles = (P + VJP_PT - 1) / VJP_PT;
+    const int64_t tiles = pl.tiles;
     const MlpUnit* unit = mlp_unit(prec);
     if (!unit) return EMAP_E_INVALID;
+    // the weight-gradient passes of a chunk, in this order (the partial sums depend on it).  Precise weight gradients (L.wgrad_lo):
+    // dW = Z_hi A_hi^T + (Z_hi A_lo^T + Z_lo A_hi^T) / LO_SCALE - the two cross terms from the lo stashes, added to the same K-slice partials
+    // (the lo x lo term is below 2^-22 of the product)
+    const float inv_lo = 1.0f / F16_LO_SCALE;
+    const struct { long long a_delta, z_delta; float scale; int no_bias; } pass[3] = {
+        {0, 0, 1.0f, 0}, {pl.V.lo_a_delta, 0, inv_lo, 1}, {0, pl.V.lo_z_delta, inv_lo, 0}};
+    const int n_pass = (L.wgrad_lo && pl.V.lo_a_delta) ? 3 : 1;
+    VjpSweep s;
+    s.src = src; s.P = P; s.d_udf = d_udf; s.d_grad = d_grad; s.V = &pl.V;
+    s.stash_a = ws + pl.off_a; s.stash_z = ws + pl.off_z; s.stash_s = ws + pl.off_slab;
+    s.grid = pl.sweep_grid; s.absmax = absmax; s.ldot = ldot;
     int chunk = 0;
     for (int64_t t0 = 0; t0 < tiles || chunk == 0; t0 += pl.chunk_tiles, ++chunk) {
-        const int nt = (int)std::min<int64_t>(pl.chunk_tiles, std::max<int64_t>(tiles - t0, 0));
+        s.tile0 = (int)t0;
+        s.n_tiles = (int)std::min<int64_t>(pl.chunk_tiles, std::max<int64_t>(tiles - t0, 0));
         int rc = EMAP_OK;
         {
         ProfScope ps(1, st);
-        rc = unit->vjp_sweep(L, packed, src, P, (int)t0, nt, d_udf, d_grad, pl.V, ws + pl.off_a, ws + pl.off_z, ws + pl.off_slab, pl.sweep_grid, absmax,
-                             ldot, st, err);
+        rc = unit->vjp_sweep(L, packed, s, st, err);
         }
         if (rc) return rc;
         ProfScope pw(2, st);
-        rc = launch_wgrad(L, pl.V, pl.jobs, pl.n_jobs, pl.wgrad_wg, ws + pl.off_a, ws + pl.off_z, partial, nt, chunk > 0 ? 1 : 0, st);
-        if (rc) return rc;
-        if (L.wgrad_lo && pl.V.lo_a_delta) {
-            // precise weight gradients: dW = Z_hi A_hi^T + (Z_hi A_lo^T + Z_lo A_hi^T) / LO_SCALE - the two cross terms from the lo stashes, added
-            // to the same K-slice partials (the lo x lo term is below 2^-22 of the product)
-            const float inv_lo = 1.0f / 2048.0f;      // LO_SCALE of the split-fp16 modes (udf_mlp_vjp.inc)
-            rc = launch_wgrad(L, pl.V, pl.jobs, pl.n_jobs, pl.wgrad_wg, ws + pl.off_a + pl.V.lo_a_delta, ws + pl.off_z, partial, nt, 1, st, inv_lo, 1);
-            if (rc) return rc;
-            rc = launch_wgrad(L, pl.V, pl.jobs, pl.n_jobs, pl.wgrad_wg, ws + pl.off_a, ws + pl.off_z + pl.V.lo_z_delta, partial, nt, 1, st, inv_lo, 0);
+        for (int i = 0; i < n_pass; ++i) {
+            rc = launch_wgrad(L, pl.V, pl.wg, s.stash_a + pass[i].a_delta, s.stash_z + pass[i].z_delta, partial, s.n_tiles,
+                              (chunk > 0 || i > 0) ? 1 : 0, st, pass[i].scale, pass[i].no_bias);
             if (rc) return rc;
         }
         if (tiles == 0) break;
     }
-    return launch_wgrad_reduce(L, pl.jobs, pl.n_jobs, pl.job_h, pl.job_pe, partial, absmax, ldot, (int)tiles, out->g_host, out->v_host, out->dg_host,
-                               out->dv_host, out->db_host, out->weight_norm, out->accumulate, out->grad_scale, st);
+    return launch_wgrad_reduce(L, pl.wg, partial, absmax, ldot, (int)tiles, *out, st);
 }
 
 static int check_param_grads(const NetLayout& L, const EmapParamGrads* o, const char* who) {
@@ -153,8 +155,6 @@ static int check_param_grads(const NetLayout& L, const EmapParamGrads* o, const 
     }
     return EMAP_OK;
 }
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // EmapRenderParams.render_mode (ABI 11; the field was `reserved`, always 0, before)
 static int check_render_mode(const EmapRenderParams* p, const char* what) {
@@ -505,8 +505,8 @@ int emap_udf_vjp(const EmapNetConfig* cfg, const void* packed, int prec, const f
     if (P < 0 || !packed || !workspace || (P > 0 && (!x || !d_udf || !d_grad3))) { set_error("udf_vjp: null pointer"); return EMAP_E_INVALID; }
     rc = check_param_grads(L, out, "udf_vjp");
     if (rc) return rc;
-    const VjpPlan pl = plan_vjp(L, P, workspace_bytes ? workspace_bytes : 1);
-    if (pl.chunk_tiles <= 0) { set_error("udf_vjp: workspace %zu < %zu bytes (minimum; emap_udf_vjp_workspace_bytes is the preferred size)", workspace_bytes, vjp_min_bytes(L, P)); return EMAP_E_WORKSPACE; }
+    const VjpPlan pl = plan_vjp(L, P, workspace_bytes);
+    if (pl.chunk_tiles <= 0) { set_error("udf_vjp: workspace %zu < %zu bytes (minimum; emap_udf_vjp_workspace_bytes is the preferred size)", workspace_bytes, pl.min_bytes); return EMAP_E_WORKSPACE; }
     char* ws = static_cast<char*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = launch_absmax(d_udf, d_grad3, P, reinterpret_cast<uint32_t*>(ws + pl.off_absmax), st);
@@ -517,36 +517,51 @@ int emap_udf_vjp(const EmapNetConfig* cfg, const void* packed, int prec, const f
     return run_vjp(L, packed, prec, src, P, d_udf, d_grad3, out, pl, ws, err_flags, st);
 }
 
-static size_t render_bwd_extra(const RenderShape& r, size_t* off_du, size_t* off_dg, size_t* off_part) {
+// The workspace of a render backward: d_udf, d_grad and composite_bwd's scratch in the first `extra` bytes, the MLP backward's workspace behind them
+struct RenderBwdPlan {
+    size_t off_du, off_dg, off_part, extra;
+    VjpPlan vjp;
+};
+static RenderBwdPlan plan_render_bwd(const NetLayout& L, const RenderShape& r, size_t avail = SIZE_MAX) {
     const size_t N = (size_t)r.N, S = (size_t)r.S;
+    RenderBwdPlan b;
     size_t off = 0;
-    *off_du = off; off += align256(N * S * 4);
-    *off_dg = off; off += align256(N * S * 12);
-    *off_part = off; off += align256(N * 16 + N * 8);      // composite_bwd's (N,4) partial sums + (N,2) per-ray maxima
-    return off;
+    b.off_du = off; off += align256(N * S * 4);
+    b.off_dg = off; off += align256(N * S * 12);
+    b.off_part = off; off += align256(N * 16 + N * 8);      // composite_bwd's (N,4) partial sums + (N,2) per-ray maxima
+    b.extra = off;
+    b.vjp = plan_vjp(L, (int64_t)r.N * r.S, avail > off ? avail - off : 0);
+    return b;
+}
+// the head of the emap_render_bwd_* entry points: the layout, the null check (args_ok: the caller's other pointers), the render mode, the shape
+static int render_bwd_begin(const EmapNetConfig* cfg, int prec, const EmapRenderParams* p, bool args_ok, const char* who, NetLayout* L,
+                            RenderShape* r) {
+    int rc = build_layout(cfg, prec, L);
+    if (rc) return rc;
+    if (!p || !args_ok) { set_error("%s: null pointer", who); return EMAP_E_INVALID; }
+    rc = check_render_mode(p, who);
+    if (rc) return rc;
+    *r = render_shape(*p);
+    return EMAP_OK;
 }
 
 int emap_render_bwd_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRenderParams* p, size_t* bytes) {
     NetLayout L;
-    const int rc = build_layout(cfg, prec, &L);
+    RenderShape r;
+    const int rc = render_bwd_begin(cfg, prec, p, bytes != nullptr, "render_bwd_workspace_bytes", &L, &r);
     if (rc) return rc;
-    if (!p || !bytes) { set_error("render_bwd_workspace_bytes: null pointer"); return EMAP_E_INVALID; }
-    if (check_render_mode(p, "render_bwd_workspace_bytes")) return EMAP_E_INVALID;
-    const RenderShape r = render_shape(*p);
-    size_t a, b, c;
-    *bytes = render_bwd_extra(r, &a, &b, &c) + plan_vjp(L, (int64_t)r.N * r.S).total;
+    const RenderBwdPlan b = plan_render_bwd(L, r);
+    *bytes = b.extra + b.vjp.total;
     return EMAP_OK;
 }
 
 int emap_render_bwd_absmax_offset(const EmapNetConfig* cfg, int prec, const EmapRenderParams* p, size_t* offset) {
     NetLayout L;
-    const int rc = build_layout(cfg, prec, &L);
+    RenderShape r;
+    const int rc = render_bwd_begin(cfg, prec, p, offset != nullptr, "render_bwd_absmax_offset", &L, &r);
     if (rc) return rc;
-    if (!p || !offset) { set_error("render_bwd_absmax_offset: null pointer"); return EMAP_E_INVALID; }
-    if (check_render_mode(p, "render_bwd_absmax_offset")) return EMAP_E_INVALID;
-    const RenderShape r = render_shape(*p);
-    size_t a, b, c;
-    *offset = render_bwd_extra(r, &a, &b, &c) + plan_vjp(L, (int64_t)r.N * r.S).off_absmax;
+    const RenderBwdPlan b = plan_render_bwd(L, r);
+    *offset = b.extra + b.vjp.off_absmax;
     return EMAP_OK;
 }
 
@@ -563,34 +578,27 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
                            const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
                            size_t workspace_bytes, int32_t* err_flags, void* stream, int stages) {
     NetLayout L;
-    int rc = build_layout(cfg, prec, &L);
-    if (rc) return rc;
-    if (!p || !g || !packed || !rays_o || !rays_d || !z_vals || !udf || !grad3 || !sample_dist_dev || !workspace) {
-        set_error("render_bwd: null pointer");
-        return EMAP_E_INVALID;
-    }
-    rc = check_render_mode(p, "render_bwd");
+    RenderShape r;
+    int rc = render_bwd_begin(cfg, prec, p, g && packed && rays_o && rays_d && z_vals && udf && grad3 && sample_dist_dev && workspace, "render_bwd", &L, &r);
     if (rc) return rc;
     rc = check_param_grads(L, out, "render_bwd");
     if (rc) return rc;
-    const RenderShape r = render_shape(*p);
     const int N = r.N, S = r.S;
     if (N <= 0) return EMAP_OK;
     if (S > EMAP_MAX_SAMPLES_PER_RAY) { set_error("render_bwd: %d samples per ray exceed the kernel limit of %d", S, EMAP_MAX_SAMPLES_PER_RAY); return EMAP_E_INVALID; }
-    size_t o_du, o_dg, o_part;
-    const size_t extra = render_bwd_extra(r, &o_du, &o_dg, &o_part);
-    const VjpPlan pl = plan_vjp(L, (int64_t)N * S, workspace_bytes > extra ? workspace_bytes - extra : 1);
-    if (pl.chunk_tiles <= 0) { set_error("render_bwd: workspace %zu < %zu bytes (minimum; emap_render_bwd_workspace_bytes is the preferred size)", workspace_bytes, extra + vjp_min_bytes(L, (int64_t)N * S)); return EMAP_E_WORKSPACE; }
+    const RenderBwdPlan b = plan_render_bwd(L, r, workspace_bytes);
+    const VjpPlan& pl = b.vjp;
+    if (pl.chunk_tiles <= 0) { set_error("render_bwd: workspace %zu < %zu bytes (minimum; emap_render_bwd_workspace_bytes is the preferred size)", workspace_bytes, b.extra + pl.min_bytes); return EMAP_E_WORKSPACE; }
     char* ws = static_cast<char*>(workspace);
-    char* vws = ws + extra;
+    char* vws = ws + b.extra;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float* d_udf = reinterpret_cast<float*>(ws + o_du);
-    float* d_grad = reinterpret_cast<float*>(ws + o_dg);
+    float* d_udf = reinterpret_cast<float*>(ws + b.off_du);
+    float* d_grad = reinterpret_cast<float*>(ws + b.off_dg);
     if ((stages & 3) == 0) { set_error("render_bwd_staged: stages must have bit 0 and / or bit 1 set"); return EMAP_E_INVALID; }
     if (stages & 1) {
         // render_core's tail in reverse; it also leaves max|d_udf|, max|d_grad| for the sweep's range scale
         rc = launch_composite_bwd(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist_dev, p, g, d_udf, d_grad,
-                                  reinterpret_cast<float*>(ws + o_part), reinterpret_cast<uint32_t*>(vws + pl.off_absmax), st);
+                                  reinterpret_cast<float*>(ws + b.off_part), reinterpret_cast<uint32_t*>(vws + pl.off_absmax), st);
         if (rc) return rc;
     }
     if (!(stages & 2)) return EMAP_OK;

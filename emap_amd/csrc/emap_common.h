@@ -15,6 +15,9 @@
 
 namespace emap {
 constexpr float F16X3_WS = 8192.0f;
+// the split-fp16 modes keep the lo part of every operand x 2^11: an f16 subnormal is flushed by the MFMA.  The kernels' LO_SCALE, and what the
+// host divides the lo passes of the precise weight gradients by (api.hip:run_vjp)
+constexpr float F16_LO_SCALE = 2048.0f;
 
 // ---- error plumbing (host) ------------------------------------------------------------------
 void set_error(const char* fmt, ...);
@@ -27,6 +30,14 @@ inline bool attr_needed(uint64_t& mask) {
     if (mask & (1ull << d)) return false;
     mask |= 1ull << d;
     return true;
+}
+// raises the dynamic-LDS limit of kernel `fn` the first time it is about to be launched on the current device (mask: one per kernel)
+inline int raise_lds_limit(uint64_t& mask, const void* fn, int bytes = 160 * 1024) {
+    if (attr_needed(mask) && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+        return EMAP_E_LAUNCH;
+    }
+    return EMAP_OK;
 }
 
 // ---- packed-weight layout -------------------------------------------------------------------
@@ -227,6 +238,17 @@ constexpr int VJP_CHUNK_TILES = EMAP_VJP_CHUNK_TILES;   // tiles per sweep launc
 // build_vjp_layout): a' (hi part) and sigma' (unorm16) in 4; the f16 sweep of the split-fp16 modes (no MX-fp6 cross terms) adds 2 with the
 // lo parts of a' (SLABLO)
 constexpr __host__ __device__ int vjp_slab_planes(bool split_f16, bool sweep_mx) { return split_f16 && !sweep_mx ? 6 : 4; }
+// The range scale K of a backward launch (udf_mlp_vjp.inc, header): the sweep evaluates its linear quantities for K (du, dg) and wgrad_reduce_kernel
+// divides by K, so both take it from here.  K = 2^k with K max|dg| in [0.5, 1) and K max|du| <= 64; 1 if both maxima are zero / non-finite.
+// absmax: [0] = bits of max|du|, [1] = bits of max|dg| (absmax_kernel / composite_bwd)
+__device__ __forceinline__ float vjp_scale_from(const uint32_t* absmax) {
+    const float mu = __builtin_bit_cast(float, absmax[0]), mg = __builtin_bit_cast(float, absmax[1]);
+    const float m = fmaxf(mg, mu * (1.0f / 64.0f));
+    if (!(m > 1e-30f) || !(m < 1e30f)) return 1.0f;
+    int e;
+    (void)frexpf(m, &e);           // m = f * 2^e, f in [0.5,1)
+    return ldexpf(1.0f, -e);
+}
 constexpr int WGRAD_MAX_JOBS = 2 * EMAP_MAX_LIN;
 struct VjpLayout {
     int32_t a_rt[EMAP_MAX_LIN + 1], a_off[EMAP_MAX_LIN + 1];   // row tiles / KiB offset inside a tile's A block
@@ -247,7 +269,25 @@ struct WgradJob {
     int32_t part_off;           // offset of the job's partial block in floats: [slice][16 row tiles][a_ct][256]
     int32_t bias_off;           // offset of the job's bias partials in floats: [slice][256] (part 0 jobs and layer 0 only, else -1)
 };
-
+// the jobs of one backward and their K-slices (plan_wgrad)
+struct WgradPlan {
+    WgradJob jobs[WGRAD_MAX_JOBS];
+    int n_jobs, total_wg;                             // total_wg: the grid of wgrad_kernel, one workgroup per slice
+    int job_h[EMAP_MAX_LIN], job_pe[EMAP_MAX_LIN];    // layer l's job over the hidden columns / over the PE columns (index into jobs), or -1
+    size_t partial_floats;                            // floats of the partial buffer
+};
+// one launch of the training backward's per-point sweep (udf_mlp_vjp.inc): points [32 tile0, min(P, 32 (tile0 + n_tiles)))
+struct VjpSweep {
+    PointSource src;
+    int64_t P;
+    int tile0, n_tiles;
+    const float *d_udf, *d_grad;                      // (P), (P,3)
+    const VjpLayout* V;
+    char *stash_a, *stash_z, *stash_s;                // VjpArgs
+    int grid;                                         // workgroups (at most one per tile is launched)
+    const uint32_t* absmax;
+    float* ldot;
+};
 
 bool mlp_uses_rev(const NetLayout& L, int prec, int64_t P);
 int set_grad_mode(int mode);   // -1 by launch size, 0 forward-mode tangents, 1 reverse sweep; returns the previous setting (udf_mlp.hip)
@@ -296,23 +336,20 @@ int launch_train_loss(const float* stats, float w_over_n, float igr, float igr_n
 int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64_t n, int64_t n_geo, float lr_geo, float lr, double b1,
                 double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st);
 // wgrad.hip: the training backward's weight-gradient GEMMs
-size_t plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget, WgradJob* jobs, int* n_jobs, int* job_h, int* job_pe, int* total_wg);
+WgradPlan plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget);
 int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hipStream_t st);
-int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradJob* jobs, int n_jobs, int total_wg, const char* stash_a,
-                 const char* stash_z, float* partial, int n_tiles, int accumulate, hipStream_t st, float scale = 1.0f, int no_bias = 0);
-int launch_wgrad_reduce(const NetLayout& L, const WgradJob* jobs, int n_jobs, const int* job_h, const int* job_pe, const float* partial,
-                        const uint32_t* absmax, const float* ldot, int n_tiles, const float* const* g, const float* const* v, float* const* dg,
-                        float* const* dv, float* const* db, int weight_norm, int accumulate, float grad_scale, hipStream_t st);
+// one GEMM pass over the n_tiles tiles of the two stashes; scale / no_bias: WgradArgs
+int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradPlan& plan, const char* stash_a, const char* stash_z, float* partial,
+                 int n_tiles, int accumulate, hipStream_t st, float scale, int no_bias);
+int launch_wgrad_reduce(const NetLayout& L, const WgradPlan& plan, const float* partial, const uint32_t* absmax, const float* ldot, int n_tiles,
+                        const EmapParamGrads& out, hipStream_t st);
 
 // The entry points of one precision unit (udf_mlp_<mode>.hip, one instantiation of udf_mlp_kernel.inc each).  variant: mlp_variant (udf_mlp.hip)
 struct MlpUnit {
     int (*mlp)(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf, float* grad3, hipStream_t st,
                int variant, int32_t* err, void* scratch, const CompositeFuse* fuse);
     int (*importance)(const NetLayout& L, const void* packed, const IsLaunch& q, hipStream_t st, int32_t* err);
-    // the training backward's per-point sweep over tiles [tile0, tile0 + n_tiles) (udf_mlp_vjp.inc)
-    int (*vjp_sweep)(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, int tile0, int n_tiles, const float* d_udf,
-                     const float* d_grad, const VjpLayout& V, char* stash_a, char* stash_z, char* stash_s, int grid, const uint32_t* absmax,
-                     float* ldot, hipStream_t st, int32_t* err);
+    int (*vjp_sweep)(const NetLayout& L, const void* packed, const VjpSweep& s, hipStream_t st, int32_t* err);
 };
 const MlpUnit* mlp_unit_bf16();
 const MlpUnit* mlp_unit_bf16x3();

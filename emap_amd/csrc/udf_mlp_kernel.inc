@@ -323,7 +323,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
     using V8 = typename Prec<MODE>::V;
     constexpr int NPART = Prec<MODE>::NPART;
     constexpr bool SCALED = (MODE == EMAP_PREC_F16X3);  // lo parts x2^11, second accumulator
-    constexpr float LO_SCALE = SCALED ? 2048.0f : 1.0f;
+    constexpr float LO_SCALE = SCALED ? F16_LO_SCALE : 1.0f;
     constexpr int NKS = H / 32;
     constexpr int NPAIR = H / 32;
     constexpr int PPW = NPAIR / NW;                // output pairs per wave per layer (NW = 4 or 8 waves per workgroup)
@@ -705,28 +705,36 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
     }
 }
 
+// What every MLP launch takes from the layout and its caller (every other field zero).  frag_off_bytes / t_frag_off_bytes: the forward and the
+// transposed fragment section in the K order of the kernel that is launched
+static MlpArgs fill_mlp_args(const NetLayout& L, const void* packed, int frag_off_bytes, int t_frag_off_bytes, const PointSource& src, int64_t P,
+                             int32_t* err) {
+    MlpArgs a;
+    memset(&a, 0, sizeof(a));
+    const char* pk = static_cast<const char*>(packed);
+    a.frags = pk + frag_off_bytes;
+    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
+    a.tfrags = pk + t_frag_off_bytes;
+    a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
+    a.src = src; a.P = P; a.err = err;
+    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
+    for (int l = 0; l < L.n_lin; ++l) { a.layer[l] = L.layer[l]; a.t_off[l] = L.t_off[l]; a.tpe_off[l] = L.tpe_off[l]; }
+    return a;
+}
+
 template <int H, int MODE, int NCT, bool GRAD, int NW = 4>
 static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, float* udf,
                             float* grad3, hipStream_t st, int32_t* err) {
     constexpr int NPART = Prec<MODE>::NPART;
     constexpr int PT = GRAD ? 16 : 16 * NCT;
-    MlpArgs a;
-    const char* pk = static_cast<const char*>(packed);
-    a.frags = pk + L.frag_off_bytes;
-    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
-    a.src = src; a.P = P; a.udf = udf; a.grad = grad3; a.err = err;
+    MlpArgs a = fill_mlp_args(L, packed, L.frag_off_bytes, L.t_frag_off_bytes, src, P, err);
+    a.udf = udf; a.grad = grad3;
     a.n_tiles = (int)((P + PT - 1) / PT);
-    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
-    for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
     const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES;   // <= 80 KiB: two workgroups per CU (8 waves: one, two exchange buffers)
     static uint64_t attr_mask = 0;   // per device: the LDS-size attribute is a property of (function, device)
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, GRAD, NW>;
-    if (attr_needed(attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-            return EMAP_E_LAUNCH;
-        }
-    }
+    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
+    if (rc) return rc;
     if (a.n_tiles <= 0) return EMAP_OK;
     const int grid = a.n_tiles < 4096 ? a.n_tiles : 4096;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
@@ -804,28 +812,19 @@ int launch_mlp_fs2_mode(const NetLayout& L, const void* packed, const PointSourc
 template <int H, int MODE, int NCT, int NW>
 static int launch_is_t(const NetLayout& L, const void* packed, const IsLaunch& q, hipStream_t st, int32_t* err) {
     constexpr int NPART = Prec<MODE>::NPART;
-    MlpArgs a;
-    memset(&a, 0, sizeof(a));
-    const char* pk = static_cast<const char*>(packed);
-    a.frags = pk + L.frag_off_bytes;
-    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
-    a.src.rays_o = q.rays_o; a.src.rays_d = q.rays_d; a.src.near = q.near; a.src.far = q.far; a.src.t_rand = q.t_rand;
-    a.src.sample_dist = q.sample_dist; a.src.n_per_ray = q.m;
-    a.P = (int64_t)q.N * q.m; a.err = err;
+    PointSource src;
+    memset(&src, 0, sizeof(src));
+    src.rays_o = q.rays_o; src.rays_d = q.rays_d; src.near = q.near; src.far = q.far; src.t_rand = q.t_rand;
+    src.sample_dist = q.sample_dist; src.n_per_ray = q.m;
+    MlpArgs a = fill_mlp_args(L, packed, L.frag_off_bytes, L.t_frag_off_bytes, src, (int64_t)q.N * q.m, err);
     const int grid = (q.N + NCT - 1) / NCT;
     a.n_tiles = grid;
-    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
-    for (int l = 0; l < L.n_lin; ++l) a.layer[l] = L.layer[l];
     a.is_udf_coarse = q.udf_coarse; a.is_z_final = q.z_final; a.is_n_rays = q.N; a.is_sc = q.Sc; a.is_m = q.m; a.is_steps = q.steps;
     const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15);
     static uint64_t attr_mask = 0;
     auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, false, NW, true>;
-    if (attr_needed(attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-            return EMAP_E_LAUNCH;
-        }
-    }
+    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
+    if (rc) return rc;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
     return check_launch("importance_sample");
 }

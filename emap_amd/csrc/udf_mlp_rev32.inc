@@ -93,7 +93,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
     using V8 = typename Prec<MODE>::V;
     constexpr int NPART = Prec<MODE>::NPART;
     constexpr bool SPLIT = (NPART == 2);                                   // lo x hi and hi x lo products go to a second accumulator set
-    constexpr float LO_SCALE = (MODE == EMAP_PREC_F16X3) ? 2048.0f : 1.0f;   // fp16 lo parts x2^11 (subnormals flush in the MFMA)
+    constexpr float LO_SCALE = (MODE == EMAP_PREC_F16X3) ? F16_LO_SCALE : 1.0f;   // fp16 lo parts x2^11 (subnormals flush in the MFMA)
     constexpr bool ASM_SPLIT = (MODE == EMAP_PREC_F16X3);   // v_cvt_pkrtz / v_fma_mix hi-lo split (f16 only)
     // NW waves, NC column tiles of 32 points.  <4, 2>: 64-point tile, two workgroups per CU.  <8, 4>: 128-point tile, ONE
     // workgroup per CU whose 8 waves own one row tile each - every weight fragment is fetched once per CU and 128 points
@@ -1098,27 +1098,15 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
                               float* grad3, hipStream_t st, int32_t* err, void* scratch, const CompositeFuse* fuse) {
     constexpr int NPART = Prec<MODE>::NPART;
     constexpr int PT = 32 * NC;
-    MlpArgs a;
-    const char* pk = static_cast<const char*>(packed);
-    a.frags = pk + L.r32_frag_off_bytes;
-    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
-    a.tfrags = pk + L.r32_t_frag_off_bytes;
-    a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
-    a.src = src; a.P = P; a.udf = udf; a.grad = grad3; a.err = err;
+    MlpArgs a = fill_mlp_args(L, packed, L.r32_frag_off_bytes, L.r32_t_frag_off_bytes, src, P, err);
+    a.udf = udf; a.grad = grad3;
     a.n_tiles = (int)((P + PT - 1) / PT);
-    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
-    for (int l = 0; l < L.n_lin; ++l) { a.layer[l] = L.layer[l]; a.t_off[l] = L.t_off[l]; a.tpe_off[l] = L.tpe_off[l]; }
     const size_t lds = (size_t)((H / 32) + PE_KS) * 2 * NC * NPART * FRAG_BYTES;
     static uint64_t attr_mask = 0, attr_mask_c = 0;   // per device: the LDS-size attribute is a property of (function, device)
     auto kern = udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, false>;
     auto kern_c = udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, true>;
-    if (attr_needed(fuse ? attr_mask_c : attr_mask)) {
-        if (hipFuncSetAttribute(fuse ? reinterpret_cast<const void*>(kern_c) : reinterpret_cast<const void*>(kern),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-            return EMAP_E_LAUNCH;
-        }
-    }
+    const int rc = raise_lds_limit(fuse ? attr_mask_c : attr_mask, fuse ? reinterpret_cast<const void*>(kern_c) : reinterpret_cast<const void*>(kern));
+    if (rc) return rc;
     if (fuse && (!fuse->ray_cnt || comp_list_entries(P, fuse->c.S) > COMP_LIST_MAX || fuse->c.S < 1 || (int64_t)fuse->c.N * fuse->c.S != P || fuse->c.udf != udf || fuse->c.grad != grad3)) {
         set_error("udf_mlp_rev32: the fused compositing tail needs P = N * S points written to the buffers it composites from");
         return EMAP_E_INVALID;

@@ -70,16 +70,6 @@ struct VjpArgs {
     int32_t swm_unit[EMAP_MAX_LIN], swm_t_unit[EMAP_MAX_LIN];
 };
 
-__device__ __forceinline__ float vjp_scale_from(const uint32_t* absmax) {
-    // K = 2^k with K*max|dg| in [0.5,1) and K*max|du| <= 64  (see header); 1 if both are zero / non-finite
-    const float mu = __builtin_bit_cast(float, absmax[0]), mg = __builtin_bit_cast(float, absmax[1]);
-    const float m = fmaxf(mg, mu * (1.0f / 64.0f));
-    if (!(m > 1e-30f) || !(m < 1e30f)) return 1.0f;
-    int e;
-    (void)frexpf(m, &e);           // m = f * 2^e, f in [0.5,1)
-    return ldexpf(1.0f, -e);
-}
-
 // SMX (round 5; split-fp16, d_hidden = 256, 8 waves): the cross terms W_hi x_lo + W_lo x_hi of every hidden-K GEMM (forward layers 1.., the
 // last layer, reverse steps) run as v_mfma_scale_f32_16x16x128_f8f6f4 on e2m3 operands - the time of ONE 16x16x32 f16 MFMA for K = 128
 // (profiles/r04_probe_mx16.txt), i.e. 16 MX MFMAs instead of 64 f16 ones per K128-step and tile pair; the hi x hi pass stays f16.
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     const MlpArgs& a = va.m;
     constexpr int NPART = Prec<MODE>::NPART;
     constexpr bool SCALED = (NPART == 2);                // cross terms in a second accumulator set (see udf_mlp_rev.inc)
-    constexpr float LO_SCALE = (MODE == EMAP_PREC_F16X3) ? 2048.0f : 1.0f;   // fp16 lo parts x2^11 (subnormals flush)
+    constexpr float LO_SCALE = (MODE == EMAP_PREC_F16X3) ? F16_LO_SCALE : 1.0f;   // fp16 lo parts x2^11 (subnormals flush)
     constexpr int NCT = 4;
     constexpr int NKS = H / 32;
     constexpr int NPAIR = H / 32;
@@ -836,51 +826,35 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     clock_stamp(a.clk, 3);
 }
 
-// points [32*tile0, min(P, 32*(tile0 + n_tiles)))
 template <int H, int MODE, int NW, bool SMX_ = false>
-static int launch_vjp_sweep_t(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, int tile0, int n_tiles,
-                              const float* d_udf, const float* d_grad, const VjpLayout& V, char* stash_a, char* stash_z,
-                              char* stash_s, int grid, const uint32_t* absmax, float* ldot, hipStream_t st, int32_t* err) {
+static int launch_vjp_sweep_t(const NetLayout& L, const void* packed, const VjpSweep& s, hipStream_t st, int32_t* err) {
     constexpr int NPART = Prec<MODE>::NPART;
     VjpArgs va;
     memset(&va, 0, sizeof(va));
-    MlpArgs& a = va.m;
-    const char* pk = static_cast<const char*>(packed);
-    a.frags = pk + L.frag_off_bytes;
-    a.bias = reinterpret_cast<const float*>(pk + L.bias_off_bytes);
-    a.tfrags = pk + L.t_frag_off_bytes;
-    a.wlast = reinterpret_cast<const float*>(pk + L.wlast_off_bytes);
-    a.src = src; a.P = P; a.err = err;
-    a.n_tiles = n_tiles; va.tile0 = tile0;
-    a.n_lin = L.n_lin; a.multires = L.multires; a.udf_type = L.udf_type; a.scale = L.scale;
-    for (int l = 0; l < L.n_lin; ++l) { a.layer[l] = L.layer[l]; a.t_off[l] = L.t_off[l]; a.tpe_off[l] = L.tpe_off[l]; }
-    a.clk = prof_clk_here();
-    va.d_udf = d_udf; va.d_grad = d_grad; va.stash_a = stash_a; va.stash_z = stash_z; va.stash_s = stash_s; va.absmax = absmax; va.ldot = ldot; va.V = V;
-    va.swm = pk + L.swm_off_bytes;
+    va.m = fill_mlp_args(L, packed, L.frag_off_bytes, L.t_frag_off_bytes, s.src, s.P, err);
+    va.m.n_tiles = s.n_tiles; va.tile0 = s.tile0;
+    va.m.clk = prof_clk_here();
+    va.d_udf = s.d_udf; va.d_grad = s.d_grad; va.stash_a = s.stash_a; va.stash_z = s.stash_z; va.stash_s = s.stash_s; va.absmax = s.absmax; va.ldot = s.ldot; va.V = *s.V;
+    va.swm = static_cast<const char*>(packed) + L.swm_off_bytes;
     for (int l = 0; l < L.n_lin; ++l) { va.swm_unit[l] = L.swm_unit[l]; va.swm_t_unit[l] = L.swm_t_unit[l]; }
     const size_t lds = (NW == 8) ? (size_t)(2 * (H / 32) + PE_KS) * 4 * NPART * FRAG_BYTES + (size_t)NW * 4 * 16 * 4   // two exchange buffers + PE + red: 146 KiB at H = 256 in the split modes
                                  : (size_t)((H / 32) + PE_KS) * 4 * NPART * FRAG_BYTES;              // 80 KiB: two workgroups per CU
     auto kern = udf_mlp_vjp_kernel<H, MODE, NW, SMX_>;
     static uint64_t attr_mask = 0;
-    if (attr_needed(attr_mask) && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-        return EMAP_E_LAUNCH;
-    }
-    if (a.n_tiles <= 0) return EMAP_OK;
-    if (grid > a.n_tiles) grid = a.n_tiles;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, va);
+    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
+    if (rc) return rc;
+    if (s.n_tiles <= 0) return EMAP_OK;
+    hipLaunchKernelGGL(kern, dim3(s.grid < s.n_tiles ? s.grid : s.n_tiles), dim3(NW * 64), lds, st, va);
     return check_launch("udf_mlp_vjp");
 }
 
 template <int MODE>
-int launch_vjp_sweep_mode(const NetLayout& L, const void* packed, const PointSource& src, int64_t P, int tile0, int n_tiles,
-                          const float* d_udf, const float* d_grad, const VjpLayout& V, char* stash_a, char* stash_z,
-                          char* stash_s, int grid, const uint32_t* absmax, float* ldot, hipStream_t st, int32_t* err) {
+int launch_vjp_sweep_mode(const NetLayout& L, const void* packed, const VjpSweep& s, hipStream_t st, int32_t* err) {
     if constexpr (MODE == EMAP_PREC_F16X3) {
-        if (L.H == 256 && L.sweep_mx) return launch_vjp_sweep_t<256, MODE, 8, true>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
+        if (L.H == 256 && L.sweep_mx) return launch_vjp_sweep_t<256, MODE, 8, true>(L, packed, s, st, err);
     }
-    if (L.H == 256) return launch_vjp_sweep_t<256, MODE, 8>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
-    if (L.H == 128) return launch_vjp_sweep_t<128, MODE, 4>(L, packed, src, P, tile0, n_tiles, d_udf, d_grad, V, stash_a, stash_z, stash_s, grid, absmax, ldot, st, err);
+    if (L.H == 256) return launch_vjp_sweep_t<256, MODE, 8>(L, packed, s, st, err);
+    if (L.H == 128) return launch_vjp_sweep_t<128, MODE, 4>(L, packed, s, st, err);
     set_error("no training-backward kernel for d_hidden=%d", L.H);
     return EMAP_E_INVALID;
 }

@@ -12,10 +12,7 @@
 //                    skip concat, and applies the weight-norm VJP  W = g v/||v||  ->  dg, dv  (one wave per output row).
 //   absmax_kernel  : max|du|, max|dg| of a launch (the range scale K of the sweep).
 #include "emap_common.h"
-#include <stdlib.h>
 #include <string.h>
-#include <type_traits>
-#include <utility>
 
 namespace emap {
 
@@ -61,33 +58,8 @@ struct WgradArgs {
     WgradJob job[WGRAD_MAX_JOBS];
 };
 
-// The K loop is software-pipelined by hand with the same device the MLP kernels use (inline-asm loads retired by counted
-// s_waitcnt vmcnt(N) statements that name their destination registers; hipcc otherwise sinks every load to its first use and
-// the loop runs at one HBM latency per fragment: measured 1.8 ms instead of 0.3 ms for 65 536 points).  A step = one K-step
-// of one tile (2 Z fragments + CT A fragments).  Every A register is reloaded for the NEXT step right after the two MFMAs that
-// consumed it and the next step's Z fragments are issued at the top of the step, so CT + 2 coalesced 1 KiB loads per wave are in
-// flight at all times.  In-flight order at the top of a step: Z0, Z1, A[0..CT-1]  ->  vmcnt(CT-1) retires Z and A[0]; inside
-// the step A[c] has CT+1 younger loads behind it.  Column tiles beyond a_ct and a missing second row tile are clamped to valid
-// addresses: their accumulators are garbage and never stored.  scripts/isa_lint.py checks the register discipline.
-template <class V8>
-__device__ __forceinline__ void wg_load(V8& dst, int voff, const char* sbase) {
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(sbase) : "memory");   // s_nop: see asm_gload16
-}
-template <int N, class V8>
-__device__ __forceinline__ void wg_wait(V8& r0) { asm volatile("s_waitcnt vmcnt(%c1)" : "+v"(r0) : "i"(N) : "memory"); }
-template <int N, class V8>
-__device__ __forceinline__ void wg_wait3(V8& r0, V8& r1, V8& r2) { asm volatile("s_waitcnt vmcnt(%c3)" : "+v"(r0), "+v"(r1), "+v"(r2) : "i"(N) : "memory"); }
-__device__ __forceinline__ const char* wg_uniform(const char* p) {
-    const unsigned long long v = (unsigned long long)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<const char*>(((unsigned long long)hi << 32) | lo);
-}
-
-template <int... Is, class F>
-__device__ __forceinline__ void wg_static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void wg_static_for(F&& f) { wg_static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
-
+// wgrad_store: a workgroup's accumulators (x this pass's factor) to its slice of the job's partial block, and the bias sums of its Z rows.  Column
+// tiles beyond a_ct and a missing second row tile were fed clamped addresses by wgrad_lds_run: their accumulators are garbage and never stored.
 template <int CT>
 __device__ __forceinline__ void wgrad_store(const WgradArgs& a, const WgradJob& J, int slice, int wave, int lane, f32x4 (&acc)[2][CT], float (&bsum)[2]) {
     // partial block [slice][row tile 0..15][a_ct][64 lanes x 4]
@@ -123,6 +95,7 @@ __device__ __forceinline__ void wgrad_store(const WgradArgs& a, const WgradJob& 
 // ---------------------------------------------------------------------------------------------
 // weight-gradient GEMM, operands staged through LDS by DMA
 // ---------------------------------------------------------------------------------------------
+// wgrad_lds_run, the K loop of one workgroup.  A step = one K-step of one tile of its slice: the job's CT A fragments and its (<= 16) Z fragments.
 // If every one of the 8 waves pulled ALL column-tile fragments of a step itself (round 2's first version; they share them, only
 // the two Z fragments are a wave's own): 8 x 18 KiB per step through the CU's 64 B/clk vector-memory path = 2.3 k cycles against 1.0 k cycles
 // of MFMA per SIMD - L1-bandwidth bound by 2x, and every 1 KiB load costs its wave ~50 issue cycles.  Here each fragment of a
@@ -130,7 +103,9 @@ __device__ __forceinline__ void wgrad_store(const WgradArgs& a, const WgradJob& 
 // layout), 2 A + 2 Z fragments per wave and step, and read back with ds_read_b128 (256 B/clk).  Ring of NST = D + 1 stages, D
 // steps in flight (no registers are involved, so nothing the compiler could copy: loads stay in flight across the loop
 // back-edge); per step: s_waitcnt vmcnt (my fragments of this step have landed) -> s_barrier (everyone's have, and everyone
-// has finished reading the stage about to be refilled) -> issue step u + D -> 18 ds_read_b128 + 32 MFMAs.
+// has finished reading the stage about to be refilled) -> issue step u + D -> 18 ds_read_b128 + 32 MFMAs.  The load count per step is the
+// same in every wave and step (that is what the counted s_waitcnt relies on): fragments beyond a_ct / z_rt are clamped to valid ones, steps past the
+// end of the slice re-fetch the last one, and the loop drains with vmcnt(0) before the workgroup gives up its LDS.
 #ifndef EMAP_REDUCE_WAVES
 #define EMAP_REDUCE_WAVES 4
 #endif
@@ -259,15 +234,6 @@ struct ReduceArgs {
     float* db[EMAP_MAX_LIN];
 };
 
-__device__ __forceinline__ float vjp_scale_from_w(const uint32_t* absmax) {   // must equal udf_mlp_vjp.inc:vjp_scale_from
-    const float mu = __builtin_bit_cast(float, absmax[0]), mg = __builtin_bit_cast(float, absmax[1]);
-    const float m = fmaxf(mg, mu * (1.0f / 64.0f));
-    if (!(m > 1e-30f) || !(m < 1e30f)) return 1.0f;
-    int e;
-    (void)frexpf(m, &e);
-    return ldexpf(1.0f, -e);
-}
-
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -292,7 +258,7 @@ __global__ __launch_bounds__(RED_WAVES * 64) void wgrad_reduce_kernel(const Redu
     const int out_dim = a.out_dim[l];
     const int in_prev = a.in_prev[l];
     const int n_in = in_prev + (a.has_pe[l] ? a.d0 : 0);
-    const float inv_k = a.grad_scale / vjp_scale_from_w(a.absmax);
+    const float inv_k = a.grad_scale / vjp_scale_from(a.absmax);
     const float mult = (l == a.skip_l) ? 0.70710678118654752440f : 1.0f;
     const int rt = o0 >> 4, mq = (o0 & 15) >> 2;
     // the last layer's Z level holds its single real row twice: row 0 = hi part, row 1 = lo part of the seeds (udf_mlp_vjp.inc)
@@ -435,13 +401,14 @@ __global__ __launch_bounds__(RED_WAVES * 64) void wgrad_reduce_kernel(const Redu
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// jobs and their K-slices for a budget of `wg_budget` workgroups; returns the number of floats of the partial buffer
-size_t plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget, WgradJob* jobs, int* n_jobs, int* job_h, int* job_pe,
-                  int* total_wg) {
+// jobs and their K-slices for a budget of `wg_budget` workgroups
+WgradPlan plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget) {
+    WgradPlan pl;
+    WgradJob* jobs = pl.jobs;
     int n = 0;
     double cost[WGRAD_MAX_JOBS], tot = 0;
     for (int l = 0; l < L.n_lin; ++l) {
-        job_h[l] = job_pe[l] = -1;
+        pl.job_h[l] = pl.job_pe[l] = -1;
         const LayerDesc& d = L.layer[l];
         for (int part = 0; part < 2; ++part) {
             if (part == 0 && d.h_ks == 0) continue;
@@ -459,7 +426,7 @@ size_t plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget, WgradJo
             // count about half (measured: the one-row last layer ran 294 us with 15 slices, 188 us with 28, next to 240 us)
             cost[n] = (double)J.a_ct + (double)J.z_rt + 0.5 * (double)(16 - (J.z_rt < 16 ? J.z_rt : 16));
             tot += cost[n];
-            (part == 0 ? job_h : job_pe)[l] = n;
+            (part == 0 ? pl.job_h : pl.job_pe)[l] = n;
             ++n;
         }
     }
@@ -488,13 +455,14 @@ size_t plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget, WgradJo
         floats += (size_t)s * 16 * jobs[i].a_ct * 256;
     }
     for (int l = 0; l < L.n_lin; ++l) {   // the bias partials ride on one job per layer
-        WgradJob& J = jobs[(job_h[l] >= 0) ? job_h[l] : job_pe[l]];
+        WgradJob& J = jobs[(pl.job_h[l] >= 0) ? pl.job_h[l] : pl.job_pe[l]];
         J.bias_off = (int32_t)floats;
         floats += (size_t)J.n_slices * 256;
     }
-    *n_jobs = n;
-    *total_wg = wg;
-    return floats;
+    pl.n_jobs = n;
+    pl.total_wg = wg;
+    pl.partial_floats = floats;
+    return pl;
 }
 
 int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hipStream_t st) {
@@ -505,44 +473,43 @@ int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hi
     return check_launch("absmax");
 }
 
-int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradJob* jobs, int n_jobs, int total_wg, const char* stash_a,
-                 const char* stash_z, float* partial, int n_tiles, int accumulate, hipStream_t st, float scale, int no_bias) {
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.stash_a = stash_a; a.stash_z = stash_z; a.partial = partial; a.scale = scale; a.no_bias = no_bias;
-    a.n_tiles = n_tiles; a.n_jobs = n_jobs; a.a_tile_kb = V.a_tile_kb; a.z_tile_kb = V.z_tile_kb; a.accumulate = accumulate;
-    for (int i = 0; i < n_jobs; ++i) a.job[i] = jobs[i];
+template <class V8>
+static int launch_wgrad_t(const WgradArgs& a, int grid, hipStream_t st) {
     constexpr size_t lds = (size_t)(WGRAD_DEPTH + 1) * 32 * 1024;   // NST stages of (16 A + 16 Z) KiB
     static uint64_t attr_mask = 0;
-    if (attr_needed(attr_mask)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<f16x8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<bf16x8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-            return EMAP_E_LAUNCH;
-        }
-    }
-    if (L.is_f16) hipLaunchKernelGGL(wgrad_kernel<f16x8>, dim3(total_wg), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL(wgrad_kernel<bf16x8>, dim3(total_wg), dim3(512), lds, st, a);
+    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(wgrad_kernel<V8>), (int)lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(wgrad_kernel<V8>, dim3(grid), dim3(512), lds, st, a);
     return check_launch("wgrad");
 }
 
-int launch_wgrad_reduce(const NetLayout& L, const WgradJob* jobs, int n_jobs, const int* job_h, const int* job_pe,
-                        const float* partial, const uint32_t* absmax, const float* ldot, int n_tiles, const float* const* g, const float* const* v,
-                        float* const* dg, float* const* dv, float* const* db, int weight_norm, int accumulate, float grad_scale,
-                        hipStream_t st) {
+int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradPlan& plan, const char* stash_a, const char* stash_z, float* partial,
+                 int n_tiles, int accumulate, hipStream_t st, float scale, int no_bias) {
+    WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.stash_a = stash_a; a.stash_z = stash_z; a.partial = partial; a.scale = scale; a.no_bias = no_bias;
+    a.n_tiles = n_tiles; a.n_jobs = plan.n_jobs; a.a_tile_kb = V.a_tile_kb; a.z_tile_kb = V.z_tile_kb; a.accumulate = accumulate;
+    for (int i = 0; i < plan.n_jobs; ++i) a.job[i] = plan.jobs[i];
+    return L.is_f16 ? launch_wgrad_t<f16x8>(a, plan.total_wg, st) : launch_wgrad_t<bf16x8>(a, plan.total_wg, st);
+}
+
+int launch_wgrad_reduce(const NetLayout& L, const WgradPlan& plan, const float* partial, const uint32_t* absmax, const float* ldot, int n_tiles,
+                        const EmapParamGrads& out, hipStream_t st) {
     ReduceArgs a;
     memset(&a, 0, sizeof(a));
-    a.partial = partial; a.absmax = absmax; a.ldot = ldot; a.n_tiles = n_tiles; a.grad_scale = grad_scale; a.accumulate = accumulate; a.weight_norm = weight_norm;
+    a.partial = partial; a.absmax = absmax; a.ldot = ldot; a.n_tiles = n_tiles;
+    a.grad_scale = out.grad_scale; a.accumulate = out.accumulate; a.weight_norm = out.weight_norm;
     a.n_lin = L.n_lin; a.H = L.H; a.d0 = L.d0; a.multires = L.multires; a.skip_l = L.skip_l;
-    int rows = 0;   // counted in groups of 4 rows (one wave each)
+    int rows = 0;   // counted in groups of 4 rows (one workgroup each)
     for (int l = 0; l < L.n_lin; ++l) {
         a.row_off[l] = rows; rows += (L.layer[l].out_dim + 3) / 4;
         a.out_dim[l] = L.layer[l].out_dim; a.in_prev[l] = L.layer[l].in_prev; a.has_pe[l] = L.layer[l].pe_ks ? 1 : 0;
-        a.job_h[l] = job_h[l]; a.job_pe[l] = job_pe[l];
-        a.g[l] = g ? g[l] : nullptr; a.v[l] = v[l]; a.dg[l] = dg ? dg[l] : nullptr; a.dv[l] = dv[l]; a.db[l] = db[l];
+        a.job_h[l] = plan.job_h[l]; a.job_pe[l] = plan.job_pe[l];
+        a.g[l] = out.g_host ? out.g_host[l] : nullptr; a.v[l] = out.v_host[l];
+        a.dg[l] = out.dg_host ? out.dg_host[l] : nullptr; a.dv[l] = out.dv_host[l]; a.db[l] = out.db_host[l];
     }
     a.row_off[L.n_lin] = rows;
-    for (int i = 0; i < n_jobs; ++i) a.job[i] = jobs[i];
+    for (int i = 0; i < plan.n_jobs; ++i) a.job[i] = plan.jobs[i];
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rows), dim3(RED_WAVES * 64), 0, st, a);
     return check_launch("wgrad_reduce");
 }
