@@ -94,6 +94,11 @@ SYMBOLS = {
     "emap_udf_fwd_grad": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
     "emap_embed": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
     "emap_null_direction": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
+    "emap_lattice_points": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "emap_compact_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "emap_compact_append": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_int, _P, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "emap_jitter_points": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
+    "emap_shift_points": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "emap_sample_pdf": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_sample_pdf_u": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_upsample_step": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,

@@ -636,6 +636,48 @@ int emap_null_direction(const float* grads, int64_t n, int k, float* dir, void* 
     return launch_null_direction(grads, n, k, dir, static_cast<hipStream_t>(stream));
 }
 
+int emap_lattice_points(int N, int64_t first, int64_t count, float* xyz, void* stream) {
+    if (N < 2 || N > EMAP_LATTICE_MAX_N) { set_error("lattice_points: N must be in 2..%d (got %d)", EMAP_LATTICE_MAX_N, N); return EMAP_E_INVALID; }
+    if (first < 0 || count < 0) { set_error("lattice_points: negative first / count"); return EMAP_E_INVALID; }
+    if (count > EMAP_STAGE_MAX_POINTS) { set_error("lattice_points: count must be <= %lld per call (got %lld)", (long long)EMAP_STAGE_MAX_POINTS, (long long)count); return EMAP_E_INVALID; }
+    if (count > (int64_t)N * N * N - first) { set_error("lattice_points: [first, first + count) leaves the N^3 lattice"); return EMAP_E_INVALID; }
+    if (count > 0 && !xyz) { set_error("lattice_points: null pointer"); return EMAP_E_INVALID; }
+    return launch_lattice_points(N, first, count, xyz, static_cast<hipStream_t>(stream));
+}
+
+int emap_compact_workspace_bytes(int64_t n, size_t* bytes) {
+    if (!bytes || n < 0 || n > EMAP_COMPACT_MAX_N) { set_error("compact_workspace_bytes: bad argument"); return EMAP_E_INVALID; }
+    *bytes = compact_workspace_bytes(n);
+    return EMAP_OK;
+}
+
+int emap_compact_append(const float* df, const float* xyz, int64_t n, int64_t first_index, float threshold, int inclusive, float* out_xyz,
+                        float* out_df, int64_t* out_idx, int64_t capacity, int64_t* state, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    if (n < 0 || n > EMAP_COMPACT_MAX_N) { set_error("compact_append: n must be in 0..%lld (got %lld)", (long long)EMAP_COMPACT_MAX_N, (long long)n); return EMAP_E_INVALID; }
+    if (capacity <= 0) { set_error("compact_append: capacity must be > 0 (got %lld)", (long long)capacity); return EMAP_E_INVALID; }
+    if (!state || !workspace || (n > 0 && !df)) { set_error("compact_append: null pointer"); return EMAP_E_INVALID; }
+    if (out_xyz && !xyz) { set_error("compact_append: out_xyz given without xyz"); return EMAP_E_INVALID; }
+    if (workspace_bytes < compact_workspace_bytes(n)) { set_error("compact_append: workspace %zu < %zu bytes (emap_compact_workspace_bytes)", workspace_bytes, compact_workspace_bytes(n)); return EMAP_E_WORKSPACE; }
+    return launch_compact_append(df, xyz, n, first_index, threshold, inclusive != 0, out_xyz, out_df, out_idx, capacity, state, workspace,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int emap_jitter_points(const float* x, const float* noise, int64_t n, int k, float delta, float* out, void* stream) {
+    if (n < 0) { set_error("jitter_points: negative n"); return EMAP_E_INVALID; }
+    if (k < 1 || k > 128) { set_error("jitter_points: sampling_N must be in 1..128 (got %d)", k); return EMAP_E_INVALID; }
+    if (n > EMAP_STAGE_MAX_POINTS / k) { set_error("jitter_points: n * sampling_N must be <= %lld per call (got %lld x %d)", (long long)EMAP_STAGE_MAX_POINTS, (long long)n, k); return EMAP_E_INVALID; }
+    if (n > 0 && (!x || !noise || !out)) { set_error("jitter_points: null pointer"); return EMAP_E_INVALID; }
+    return launch_jitter_points(x, noise, n, k, delta, out, static_cast<hipStream_t>(stream));
+}
+
+int emap_shift_points(const float* x, const float* df, const float* normal, int64_t n, float* out, void* stream) {
+    if (n < 0) { set_error("shift_points: negative n"); return EMAP_E_INVALID; }
+    if (n > EMAP_STAGE_MAX_POINTS) { set_error("shift_points: n must be <= %lld per call (got %lld)", (long long)EMAP_STAGE_MAX_POINTS, (long long)n); return EMAP_E_INVALID; }
+    if (n > 0 && (!x || !df || !normal || !out)) { set_error("shift_points: null pointer"); return EMAP_E_INVALID; }
+    return launch_shift_points(x, df, normal, n, out, static_cast<hipStream_t>(stream));
+}
+
 int emap_profile_enable(int on) {
     if (on && !g_prof_init) {
         for (int k = 0; k < PROF_KERNELS; ++k)

@@ -223,6 +223,12 @@ int launch_mlp(const NetLayout& L, const void* packed, int prec, const PointSour
                float* udf, float* grad3, hipStream_t st, int32_t* err_flags = nullptr, void* scratch = nullptr,
                const CompositeFuse* fuse = nullptr);
 int launch_null_direction(const float* g, int64_t n, int k, float* dir, hipStream_t st);
+int launch_lattice_points(int N, int64_t first, int64_t count, float* xyz, hipStream_t st);
+size_t compact_workspace_bytes(int64_t n);
+int launch_compact_append(const float* df, const float* xyz, int64_t n, int64_t first_index, float thr, int inclusive, float* out_xyz,
+                          float* out_df, int64_t* out_idx, int64_t capacity, int64_t* state, void* workspace, hipStream_t st);
+int launch_jitter_points(const float* x, const float* noise, int64_t n, int k, float delta, float* out, hipStream_t st);
+int launch_shift_points(const float* x, const float* df, const float* normal, int64_t n, float* out, hipStream_t st);
 
 // ---- training backward (udf_mlp_vjp.inc, wgrad.hip) ---------------------------------------------------
 // The sweep kernel leaves the operands of the weight-gradient GEMM per tile of VJP_PT points in MFMA-fragment order

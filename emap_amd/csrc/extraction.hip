@@ -90,4 +90,201 @@ int launch_null_direction(const float* g, int64_t n, int k, float* dir, hipStrea
     return check_launch("null_direction");
 }
 
+// ---- get_pointcloud_from_udf (extract_pointcloud.py:212-293), streamed ------------------------------------------------------------
+// The point-cloud routine walks the N^3 lattice in chunks and keeps only the points below the threshold.  Four small kernels:
+// lattice coordinates of an index range, a stable stream compaction (count -> scan -> scatter: three launches in stream order,
+// no workgroup ever waits for another), the jitter neighbourhood x + delta * noise and the shift x + df * normal.  The last three
+// expressions are the reference's fp32 arithmetic: a multiply and an add, each rounded - no FMA contraction.
+//
+// Bound: HBM, all of them (a few bytes per point, no reuse).
+
+constexpr int CP_THREADS = 256;                       // compaction: threads per workgroup
+constexpr int CP_ITEMS = 8;                           //             consecutive points per thread
+constexpr int CP_TILE = CP_THREADS * CP_ITEMS;        //             points per workgroup
+constexpr int SCAN_THREADS = 1024;
+constexpr size_t CP_HEADER = 16;                      // workspace = [int64 base][int32 ok][int32 pad][int32 count per workgroup ...]
+
+__global__ __launch_bounds__(256) void lattice_points_kernel(int N, long long first, long long count, float vs, float* __restrict__ xyz) {
+#pragma clang fp contract(off)
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const long long i = first + t;
+    const long long iz = i % N, iy = (i / N) % N, ix = i / ((long long)N * N);
+    float* o = xyz + t * 3;
+    const float x = (float)ix * vs, y = (float)iy * vs, z = (float)iz * vs;       // arange(N) * (2/(N-1)) ...
+    o[0] = x + (-1.0f); o[1] = y + (-1.0f); o[2] = z + (-1.0f);                   // ... + (-1)
+}
+
+__device__ __forceinline__ bool cp_keep(float v, float thr, int inclusive) { return inclusive ? (v <= thr) : (v < thr); }
+
+// number of survivors among this thread's CP_ITEMS consecutive points, and their bit mask
+__device__ __forceinline__ int cp_thread_mask(const float* __restrict__ df, long long n, float thr, int inclusive, int vec, unsigned& mask) {
+    const long long i0 = ((long long)blockIdx.x * CP_THREADS + threadIdx.x) * CP_ITEMS;
+    mask = 0;
+    if (vec && i0 + CP_ITEMS <= n) {                    // vec: df is 16-byte aligned
+        const float4 a = *reinterpret_cast<const float4*>(df + i0), b = *reinterpret_cast<const float4*>(df + i0 + 4);
+        const float v[CP_ITEMS] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; ++j) mask |= cp_keep(v[j], thr, inclusive) ? (1u << j) : 0u;
+    } else {
+        for (int j = 0; j < CP_ITEMS; ++j)
+            if (i0 + j < n && cp_keep(df[i0 + j], thr, inclusive)) mask |= 1u << j;
+    }
+    return __popc(mask);
+}
+
+// exclusive prefix sum of one int per thread over the workgroup (CP_THREADS threads); `total` = the sum
+__device__ __forceinline__ int cp_block_scan(int v, int& total) {
+    __shared__ int wsum[CP_THREADS / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < CP_THREADS / 64; ++k) {
+        if (k < w) before += wsum[k];
+        total += wsum[k];
+    }
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(CP_THREADS) void compact_count_kernel(const float* __restrict__ df, long long n, float thr, int inclusive,
+                                                                   int vec, int* __restrict__ block_cnt) {
+    unsigned mask;
+    int total;
+    cp_block_scan(cp_thread_mask(df, n, thr, inclusive, vec, mask), total);
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = total;
+}
+
+// one workgroup: exclusive scan of the per-workgroup counts in place, then the decision for the whole call.
+// state = {survivors so far, error, calls appended, survivors this call needed when it set the error}
+__global__ __launch_bounds__(SCAN_THREADS) void compact_scan_kernel(int* __restrict__ block_cnt, int nb, long long capacity,
+                                                                    long long* __restrict__ state, long long* __restrict__ base_out,
+                                                                    int* __restrict__ ok_out) {
+    __shared__ int part[SCAN_THREADS];
+    __shared__ int carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += SCAN_THREADS) {
+        const int b = b0 + (int)threadIdx.x;
+        const int v = b < nb ? block_cnt[b] : 0;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (int d = 1; d < SCAN_THREADS; d <<= 1) {                 // Hillis-Steele inclusive scan
+            const int o = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+            __syncthreads();
+            part[threadIdx.x] += o;
+            __syncthreads();
+        }
+        if (b < nb) block_cnt[b] = carry + part[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == 0) carry += part[SCAN_THREADS - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const long long have = state[0], total = carry;
+        int ok = 0;
+        if (state[1] == 0) {                                          // a call after a failed one appends nothing: the order is kept
+            if (have + total > capacity) { state[1] = 1; state[3] = have + total; }
+            else { state[0] = have + total; state[2] += 1; ok = 1; }
+        }
+        *base_out = have;
+        *ok_out = ok;
+    }
+}
+
+__global__ __launch_bounds__(CP_THREADS) void compact_scatter_kernel(const float* __restrict__ df, const float* __restrict__ xyz, long long n,
+                                                                     long long first_index, float thr, int inclusive, int vec,
+                                                                     const int* __restrict__ block_off, const long long* __restrict__ base_in,
+                                                                     const int* __restrict__ ok_in, long long capacity,
+                                                                     float* __restrict__ out_xyz, float* __restrict__ out_df,
+                                                                     long long* __restrict__ out_idx) {
+    if (*ok_in == 0) return;                                          // uniform: the scan kernel refused the call
+    unsigned mask;
+    int total;
+    const int cnt = cp_thread_mask(df, n, thr, inclusive, vec, mask);
+    long long dst = *base_in + block_off[blockIdx.x] + cp_block_scan(cnt, total);
+    const long long i0 = ((long long)blockIdx.x * CP_THREADS + threadIdx.x) * CP_ITEMS;
+    for (int j = 0; j < CP_ITEMS; ++j) {
+        if (!(mask & (1u << j))) continue;
+        const long long i = i0 + j;
+        if (dst < capacity) {                                         // holds whenever ok is set; kept as the bound of every store
+            if (out_df) out_df[dst] = df[i];
+            if (out_idx) out_idx[dst] = first_index + i;
+            if (out_xyz) { out_xyz[dst * 3] = xyz[i * 3]; out_xyz[dst * 3 + 1] = xyz[i * 3 + 1]; out_xyz[dst * 3 + 2] = xyz[i * 3 + 2]; }
+        }
+        ++dst;
+    }
+}
+
+__global__ __launch_bounds__(256) void jitter_points_kernel(const float* __restrict__ x, const float* __restrict__ noise, long long total,
+                                                            int k3, float delta, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // one element of the (n, k, 3) neighbourhood
+    if (t >= total) return;
+    const long long p = t / k3;
+    const int c = (int)((t - p * k3) % 3);
+    const float d = delta * noise[t];
+    out[t] = x[p * 3 + c] + d;
+}
+
+__global__ __launch_bounds__(256) void shift_points_kernel(const float* __restrict__ x, const float* __restrict__ df, const float* __restrict__ normal,
+                                                           long long total, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // one coordinate
+    if (t >= total) return;
+    const float d = df[t / 3] * normal[t];
+    out[t] = x[t] + d;
+}
+
+static unsigned grid_for(long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+int launch_lattice_points(int N, int64_t first, int64_t count, float* xyz, hipStream_t st) {
+    if (count == 0) return EMAP_OK;
+    const float vs = (float)(2.0 / (double)(N - 1));
+    hipLaunchKernelGGL(lattice_points_kernel, dim3(grid_for(count, 256)), dim3(256), 0, st, N, (long long)first, (long long)count, vs, xyz);
+    return check_launch("lattice_points");
+}
+
+size_t compact_workspace_bytes(int64_t n) {
+    const int64_t nb = (n + CP_TILE - 1) / CP_TILE;
+    return CP_HEADER + (size_t)(nb > 0 ? nb : 1) * sizeof(int);
+}
+
+int launch_compact_append(const float* df, const float* xyz, int64_t n, int64_t first_index, float thr, int inclusive, float* out_xyz,
+                          float* out_df, int64_t* out_idx, int64_t capacity, int64_t* state, void* workspace, hipStream_t st) {
+    if (n == 0) return EMAP_OK;
+    const int nb = (int)((n + CP_TILE - 1) / CP_TILE);
+    long long* base = reinterpret_cast<long long*>(workspace);
+    int* ok = reinterpret_cast<int*>(static_cast<char*>(workspace) + 8);
+    int* block_cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + CP_HEADER);
+    const int vec = (reinterpret_cast<uintptr_t>(df) & 15) == 0;
+    hipLaunchKernelGGL(compact_count_kernel, dim3(nb), dim3(CP_THREADS), 0, st, df, (long long)n, thr, inclusive, vec, block_cnt);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, block_cnt, nb, (long long)capacity,
+                       reinterpret_cast<long long*>(state), base, ok);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(nb), dim3(CP_THREADS), 0, st, df, xyz, (long long)n, (long long)first_index, thr, inclusive,
+                       vec, block_cnt, base, ok, (long long)capacity, out_xyz, out_df, reinterpret_cast<long long*>(out_idx));
+    return check_launch("compact_append");
+}
+
+int launch_jitter_points(const float* x, const float* noise, int64_t n, int k, float delta, float* out, hipStream_t st) {
+    if (n == 0) return EMAP_OK;
+    const long long total = (long long)n * k * 3;
+    hipLaunchKernelGGL(jitter_points_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, x, noise, total, 3 * k, delta, out);
+    return check_launch("jitter_points");
+}
+
+int launch_shift_points(const float* x, const float* df, const float* normal, int64_t n, float* out, hipStream_t st) {
+    if (n == 0) return EMAP_OK;
+    hipLaunchKernelGGL(shift_points_kernel, dim3(grid_for((long long)n * 3, 256)), dim3(256), 0, st, x, df, normal, (long long)n * 3, out);
+    return check_launch("shift_points");
+}
+
 }  // namespace emap

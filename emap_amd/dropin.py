@@ -222,7 +222,7 @@ def install(force: bool = True, patch_dataset: bool = True):
     if patch_dataset:
         _patch_dataset()
     _patch_runner()
-    # extraction queries (SURVEY par. 8 f2): the reference module keeps its other functions; only the two query routines
+    # extraction queries (SURVEY par. 8 f2): the reference module keeps its other functions; only the query routines
     # are replaced, and only if the module can be imported at all (it needs nothing but torch)
     try:
         ep = importlib.import_module("src.edge_extraction.extract_pointcloud")
@@ -232,6 +232,12 @@ def install(force: bool = True, patch_dataset: bool = True):
         from . import extraction
         ep.get_udf_normals_grid = extraction.get_udf_normals_grid
         ep.get_udf_normals_slow = extraction.get_udf_normals_slow
+        # ... and the routine every shipped conf calls (runner_udf.py:528): the streamed point cloud.  The runner holds the name by
+        # `from ... import` (runner_udf.py:16), so it is re-bound there as well once that module is imported
+        ep.get_pointcloud_from_udf = extraction.get_pointcloud_from_udf
+        rm = sys.modules.get("src.runner.runner_udf")
+        if rm is not None and hasattr(rm, "get_pointcloud_from_udf"):
+            rm.get_pointcloud_from_udf = extraction.get_pointcloud_from_udf
     return sorted(_ALIASES)
 
 

@@ -231,3 +231,18 @@ def convergence_batch(meta, edges, n_rays: int, seed: int, held_out: int = 0):
     ys, xs = np.nonzero(e > 0.1)
     k = rng.integers(0, len(ys), size=n_rays - half)
     return img, np.concatenate([px, xs[k]]), np.concatenate([py, ys[k]])
+
+
+def extract_edge_callables(runner):
+    """``(func, func_grad)`` as ``Runner_UDF.extract_edge`` hands them to ``get_pointcloud_from_udf`` (runner_udf.py:520-527): the
+    network's bound ``udf`` and a closure over the RUNNER that normalises ``runner.udf_network_fine.gradient``.  ``runner`` is
+    anything with a ``udf_network_fine`` attribute.  The one restatement of that closure for fixtures, tests and measurements."""
+    func = runner.udf_network_fine.udf
+
+    def func_grad(xyz):
+        gradients = runner.udf_network_fine.gradient(xyz)
+        gradients_mag = torch.linalg.norm(gradients, ord=2, dim=-1, keepdim=True)
+        gradients_norm = gradients / (gradients_mag + 1e-5)
+        return gradients_norm
+
+    return func, func_grad

@@ -387,6 +387,34 @@ int emap_adam_step_masked(float* params, const float* grads, float* exp_avg, flo
  *                       grads (n, k, 3) -> dir (n, 3); the sign is arbitrary, as in the reference */
 int emap_null_direction(const float* grads, int64_t n, int k, float* dir, void* stream);
 
+/* ---- streamed point-cloud extraction: get_pointcloud_from_udf (src/edge_extraction/extract_pointcloud.py:212-293) --------------
+ * Added functions only (no struct or signature of ABI 12 changes).  Every argument check below fails with EMAP_E_INVALID before a launch.
+ * emap_lattice_points : points [first, first + count) of the N^3 lattice on [-1, 1]^3, first coordinate slowest (:36-54) -> xyz (count, 3).
+ *                       Bit-identical to arange(N) * (2 / (N - 1)) + (-1): an fp32 multiply, then an fp32 add.  2 <= N <= EMAP_LATTICE_MAX_N,
+ *                       count <= EMAP_STAGE_MAX_POINTS per call (as n * k of emap_jitter_points and n of emap_shift_points).
+ * emap_compact_append : stable stream compaction.  Of the n points (df (n), xyz (n, 3)) those with df < threshold (inclusive = 0) or
+ *                       df <= threshold (inclusive = 1) are APPENDED in input order to out_xyz (capacity, 3) / out_df (capacity) /
+ *                       out_idx (capacity; first_index + position in the input); any of the three outputs may be NULL.
+ *                       state = int64[4] on the device, zeroed by the caller before the first call:
+ *                         [0] survivors appended so far (where this call appends), [1] error flag, [2] calls that appended,
+ *                         [3] the value [0] would have needed to reach when the error was raised.
+ *                       A call whose survivors do not fit below `capacity` writes NOTHING and sets [1]; while [1] is set every
+ *                       further call is a no-op, so the order of the output is kept: the caller grows the buffers, clears [1] and
+ *                       repeats from call number [2].  Three launches (count, scan, scatter) in stream order: no workgroup waits for another.
+ *                       workspace: emap_compact_workspace_bytes(n) bytes, used by this call only.  n <= EMAP_COMPACT_MAX_N.
+ * emap_jitter_points  : x (n, 3), noise (n, k, 3) -> out (n * k, 3) = x[:, None] + delta * noise (:76-80, 165-169); 1 <= k <= 128.
+ * emap_shift_points   : out (n, 3) = x + df[:, None] * normal (:273).  Both as the fp32 torch expressions: multiply, then add. */
+#define EMAP_LATTICE_MAX_N 1048576
+#define EMAP_COMPACT_MAX_N 1073741824
+#define EMAP_STAGE_MAX_POINTS 1073741824   /* per call: lattice count, jitter n * k, shift n (the launch grids are 32-bit) */
+int emap_lattice_points(int N, int64_t first, int64_t count, float* xyz, void* stream);
+int emap_compact_workspace_bytes(int64_t n, size_t* bytes);
+int emap_compact_append(const float* df, const float* xyz, int64_t n, int64_t first_index, float threshold, int inclusive, float* out_xyz,
+                        float* out_df, int64_t* out_idx, int64_t capacity, int64_t* state, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int emap_jitter_points(const float* x, const float* noise, int64_t n, int k, float delta, float* out, void* stream);
+int emap_shift_points(const float* x, const float* df, const float* normal, int64_t n, float* out, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * While enabled, emap_render_fwd / emap_render_bwd bracket their dominant kernels with hipEvents on the launch
  * stream; emap_profile_read[_kernel] (after the caller synchronised) returns the summed duration and the number of
