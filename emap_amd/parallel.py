@@ -9,7 +9,7 @@ ge_ns + igr_weight * ge, zero_grad / backward / step).
 ``Trainer`` is the native step (no autograd graph, no per-parameter copies):
 
   forward     emap_render_fwd on the rank's rays                                   (HIP, no collective)
-  stats       [sum(relax), sum(near), sum((edge-gt)^2), sum(relax*err), sum(near*err)]   5 floats
+  stats       [sum(relax), sum(near), sum(relax*err), sum(near*err), sum((edge-gt)^2)]   5 floats
   backward    emap_render_bwd writes dL/dtheta of the rank's share of the GLOBAL loss straight into one flat fp32 buffer laid
               out in parameters() order - the parameters themselves are views of one flat buffer as well
   all-reduce  ONE collective over that buffer (about 1.85 MB for d8 w256; the stats ride in its tail)
@@ -26,10 +26,14 @@ sphere) and the step has exactly one collective.
 """
 from __future__ import annotations
 
+import ctypes as C
+from dataclasses import dataclass
 from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def shard(t: torch.Tensor, rank: int, world: int) -> torch.Tensor:
@@ -54,8 +58,6 @@ class OneShotAllReduce:
     the ranks may even share one GPU, which is how the one-GPU tests run it).  One node only (IPC handles do not cross hosts)."""
 
     def __init__(self, n_floats: int, device, group=None):
-        import ctypes as C
-        from . import _lib
         assert dist.is_available() and dist.is_initialized(), "OneShotAllReduce needs an initialised process group (for the handle exchange)"
         self.group, self.device = group, torch.device(device)
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
@@ -87,7 +89,6 @@ class OneShotAllReduce:
     def __call__(self, t: torch.Tensor) -> torch.Tensor:
         """In place: t <- sum over the ranks of t.  fp32, contiguous, on this device, at most n_floats elements; every rank must call it
         with the same number of elements, in the same order."""
-        from . import _lib
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() <= self.n_floats
         with torch.cuda.device(t.device):
             _lib.check(_lib.lib().emap_ar_allreduce_sum(_lib.ptr(t), t.numel(), self.rank, self.world, self._regions, self.region_bytes,
@@ -97,15 +98,12 @@ class OneShotAllReduce:
     @staticmethod
     def set_timeout_ms(ms: int):
         """Bound of one peer wait inside the kernel (default 10 s; x6 for a region's first two launches).  Process-wide."""
-        from . import _lib
         _lib.check(_lib.lib().emap_ar_set_timeout_ms(int(ms)), "ar_set_timeout_ms")
 
     def check(self):
         """Raise if a launch gave up waiting for a peer (host read: synchronises).  Such a launch has also written NaN into its bucket
         (csrc/allreduce.hip step 4), so the loss and the parameters of this rank are NaN from that step on - the time-out cannot pass
         unnoticed even where nobody calls this."""
-        import ctypes as C
-        from . import _lib
         e = C.c_int()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().emap_ar_error(self._own, C.byref(e)), "ar_error")
@@ -114,7 +112,6 @@ class OneShotAllReduce:
                                "not call the collective in lock step)")
 
     def close(self):
-        from . import _lib
         L = _lib.lib()
         if getattr(self, "_own", None) is None:
             return
@@ -160,6 +157,101 @@ class FlatParams:
         return s, e
 
 
+class _FlatAdam:
+    """The state of emap_adam_step[_masked] over one flat fp32 buffer of `n` elements, the first `n_geo` of them the geometry range
+    (ONE step counter, `t`: its parameters always step together) and the rest the tail (`tail_sizes`: the element counts of its
+    parameters): every tail element has its own step count and a trainable mask.  Everything lives on the device - no host index
+    tensors in the step, nothing a captured graph could bake in; a graph reads the mask BUFFER, so set_mask() between replays takes
+    effect without re-capturing."""
+
+    def __init__(self, n: int, n_geo: int, tail_sizes: List[int], dev):
+        assert n_geo + sum(tail_sizes) == n
+        self.n, self.n_geo, self.tail_sizes = n, n_geo, list(tail_sizes)
+        self.m, self.v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        self.t = torch.zeros(1, device=dev)
+        self.spare_t = torch.zeros(1, device=dev)      # the counter a launch over the tail alone bumps (step(geo_grad_ptr=...))
+        nt = max(n - n_geo, 1)
+        self.tail_mask, self.tail_step = torch.ones(nt, device=dev), torch.zeros(nt, device=dev)
+        self.flags = None                              # per tail parameter, as last written to tail_mask
+        self._pinned = torch.ones(nt).pin_memory() if dev.type == "cuda" else None
+
+    def set_mask(self, flags, capturing: bool = False) -> bool:
+        """tail_mask <- one flag per tail parameter (True: the step updates it).  Nothing happens while the flags stay as they are."""
+        flags = tuple(flags)
+        if flags == self.flags:
+            return False
+        if capturing or (self.m.is_cuda and torch.cuda.is_current_stream_capturing()):
+            raise RuntimeError("flat Adam: the set of trainable tail parameters changed inside a graph capture")
+        vals = torch.tensor([1.0 if f else 0.0 for f, k in zip(flags, self.tail_sizes) for _ in range(k)])
+        k = vals.numel()
+        if self._pinned is not None:
+            self._pinned[:k].copy_(vals)
+            self.tail_mask[:k].copy_(self._pinned[:k], non_blocking=True)
+        else:
+            self.tail_mask[:k].copy_(vals)
+        self.flags = flags
+        return True
+
+    def step(self, data, grad, lr_geo, lr_tail, betas, eps, geo_grad_ptr: Optional[int] = None):
+        """One Adam step of `data` (n floats).  `grad` holds all n gradients - one launch - or, with `geo_grad_ptr` (the address of the
+        n_geo geometry gradients in a buffer of the caller), those of the tail alone: two launches on disjoint ranges with the same
+        arithmetic, the geometry range first (it bumps `t`), then the tail with its own step counts."""
+        L, dev = _lib.lib(), data.device
+        hyper = (float(lr_geo), float(lr_tail), float(betas[0]), float(betas[1]), float(eps))
+        tail = (_lib.ptr(self.tail_mask), _lib.ptr(self.tail_step), _lib.stream_ptr(dev))
+        with torch.cuda.device(dev):
+            if geo_grad_ptr is None:
+                _lib.check(L.emap_adam_step_masked(_lib.ptr(data), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
+                                                   self.n, self.n_geo, *hyper, *tail), "adam_step")
+                return
+            ng, nt = self.n_geo, self.n - self.n_geo
+            _lib.check(L.emap_adam_step(_lib.ptr(data), C.c_void_p(geo_grad_ptr), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
+                                        ng, ng, *hyper, tail[2]), "adam_step")
+            if nt > 0:
+                _lib.check(L.emap_adam_step_masked(_lib.ptr(data[ng:]), _lib.ptr(grad), _lib.ptr(self.m[ng:]), _lib.ptr(self.v[ng:]),
+                                                   _lib.ptr(self.spare_t), nt, 0, *hyper, *tail), "adam_step")
+
+
+def _loss_from_stats(stats, n_elem, edge_weight, igr_weight, igr_ns_weight):
+    """(loss, edge_loss) of the GLOBAL batch from its statistics [sum relax, sum near, sum relax*err, sum near*err, sum diff^2] - the one
+    order of the five floats everywhere (emap_train_stats / emap_train_loss are the device side of the same convention)."""
+    edge_loss = stats[4] / n_elem * edge_weight
+    loss = edge_loss + igr_weight * stats[2] / (stats[0] + 1e-5) + igr_ns_weight * stats[3] / (stats[1] + 1e-5)
+    return loss, edge_loss
+
+
+def _global_mask_sums(scalars, stats):
+    """The forward's scalars with the rank's two eikonal mask sums ([4], [6]) replaced by the GLOBAL ones of the all-reduced `stats`."""
+    sc = scalars.clone()
+    sc[4], sc[6] = stats[0], stats[1]
+    return sc
+
+
+def _run_phases(fns, coll, S):
+    """Call `fns` in order - the four phases of a step or the replays of their graphs - and after the i-th the collectives tagged i
+    (Trainer._collectives).  Returns what the last one returned."""
+    out = None
+    for i, fn in enumerate(fns):
+        out = fn()
+        for after, c in coll:
+            if after == i:
+                c(S)
+    return out
+
+
+@dataclass
+class _Step:
+    """What the phases of one native step hand to each other (and to the collectives between them)."""
+    call: Optional[dict] = None              # the forward: the prepared call, its outputs, its scalars
+    v: Optional[dict] = None
+    scalars: Optional[torch.Tensor] = None
+    d_edge: Optional[torch.Tensor] = None
+    n_glob: int = 0
+    sync: Optional[str] = None               # several ranks: "exact" (also exact_lagged) or "local"; one rank: None
+    sc_glob: Optional[torch.Tensor] = None   # `scalars` with the global mask sums ("exact")
+    lagged: bool = False                     # exact_lagged on several ranks: the range maxima ride in the bucket's tail
+
+
 class _AdamGroups:
     """What the step reads from `Trainer.optimizer` when the update runs in emap_adam_step: the two parameter groups of the
     reference (runner_base.py:110-117) with the keys its schedulers touch (`g["lr"] = ...`, runner_base.py:140-141,159-160)."""
@@ -173,7 +265,8 @@ class _AdamGroups:
         pass
 
     def step(self):
-        self._t._native_adam()
+        t, (g0, g1) = self._t, self.param_groups
+        t._adam.step(t.flat.data, t.flat.grad, g0["lr"], g1["lr"], g0["betas"], g0["eps"])
 
 
 class Trainer:
@@ -217,16 +310,11 @@ class Trainer:
         self.native_tail = bool(native_tail)
         if self.native_tail:
             assert g0 == 0 and s0 == g1 and s1 == self.flat.numel, "flat layout: geometry parameters first, then the scalars"
-            self._n_geo = g1
-            self._m = torch.zeros(self.flat.numel, device=dev)
-            self._v = torch.zeros(self.flat.numel, device=dev)
-            self._adam_t = torch.zeros(1, device=dev)          # step counter on the device: the update is graph-capturable
-            # the scalars' trainable mask and their own step counts live on the device too (emap_adam_step_masked): no host index tensors
-            # in the step, nothing a captured graph could bake in.  The mask is refreshed from requires_grad at every step() / replay().
-            self._tail_mask = torch.ones(self.flat.numel - g1, device=dev)
-            self._tail_step = torch.zeros(self.flat.numel - g1, device=dev)
-            self._tail_flags = None
-            self._mask_pinned = torch.ones(self.flat.numel - g1).pin_memory() if dev.type == "cuda" else None
+            # the step counter, the scalars' trainable mask and their own step counts live on the device: the update is graph-capturable.
+            # The mask is refreshed from requires_grad at every step() / replay().
+            a = self._adam = _FlatAdam(self.flat.numel, g1, [p.numel() for p in self.scalars], dev)
+            # the holder's buffers under the names the multi-process tests reset them by (the same tensors, not copies)
+            self._m, self._v, self._adam_t, self._tail_step = a.m, a.v, a.t, a.tail_step
             self._stats = torch.zeros(5, device=dev)
             self.optimizer = _AdamGroups(self, lr_geo, lr)
         else:
@@ -253,7 +341,7 @@ class Trainer:
         if allreduce == "oneshot" and _world(group) > 1:
             self._oneshot = OneShotAllReduce(self.flat.grad.numel(), dev, group)
 
-    # ---- the three device stages; the CPU tests substitute oracle implementations for the two HIP ones ----
+    # ---- the two HIP stages; the CPU tests substitute oracle implementations for them ----
     def _forward(self, rays):
         r = self.r
         call = r._prepare(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], rays.get("depth_scale"), rays.get("cos_anneal_ratio"),
@@ -261,9 +349,21 @@ class Trainer:
         v = r._render_hip(call)
         return call, v, v["edge"], v["scalars"]
 
-    def _backward(self, call, v, d_edge, scalars_glob, flat_grad):
+    def _backward(self, call, v, d_edge, scalars_glob, flat_grad, stages=3):
+        """stages: 3 the whole backward; 1 the compositing half (leaves the range maxima, renderer.bwd_absmax), 2 the MLP half"""
         self.r.backward_into(call, v, d_edge, None, self._igr, self._igr_ns if self.igr_ns_weight != 0.0 else None,
-                             flat=flat_grad, scalars=scalars_glob)
+                             flat=flat_grad, scalars=scalars_glob, stages=stages)
+
+    def _sync(self):
+        """What several ranks exchange besides the gradients: "exact" - the statistics, all-reduced before the backward (also exact_lagged) -
+        or "local" - nothing, the statistics ride in the gradient bucket's tail; None on one rank."""
+        if _world(self.group) == 1:
+            return None
+        return "local" if self.eikonal_sync == "local" else "exact"
+
+    def _stats_slot(self):
+        """The five step statistics' slot in the tail of the gradient bucket ("local")"""
+        return self.flat.grad[self.flat.numel:self.flat.numel + 5]
 
     def _scalar_flags(self):
         """Which of variance / beta / gamma the step updates: those with requires_grad, except `variance` under use_unbias_render=False,
@@ -271,7 +371,6 @@ class Trainer:
         for p in self.geo:
             if not p.requires_grad:
                 raise NotImplementedError("Trainer: a UDF network parameter with requires_grad=False is not supported")
-        from . import _lib
         plain = self.r.render_mode == _lib.RENDER_PLAIN
         return tuple(bool(p.requires_grad) and not (plain and i == 0) for i, p in enumerate(self.scalars))
 
@@ -294,74 +393,43 @@ class Trainer:
     def refresh_trainable_mask(self, capturing: bool = False):
         """Mirror `requires_grad` of variance / beta / gamma (runner_udf.py:141-154 flips them during training) into the device mask
         of the fused Adam.  Eager: called by every step.  Under a captured graph the mask BUFFER is what the graph reads, so a
-        refresh between replays takes effect without re-capturing."""
-        flags = self._scalar_flags()
-        if flags == self._tail_flags:
-            return False
-        if capturing:
-            raise RuntimeError("Trainer: requires_grad of variance / beta / gamma changed inside a graph capture")
-        vals = []
-        for p, f in zip(self.scalars, flags):
-            vals += [1.0 if f else 0.0] * p.numel()
-        if self._mask_pinned is not None:
-            self._mask_pinned.copy_(torch.tensor(vals))
-            self._tail_mask.copy_(self._mask_pinned, non_blocking=True)
-        else:
-            self._tail_mask.copy_(torch.tensor(vals))
-        self._tail_flags = flags
-        return True
-
-    def _native_adam(self):
-        from . import _lib
-        g0, g1 = self.optimizer.param_groups
-        dev = self.flat.data.device
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().emap_adam_step_masked(_lib.ptr(self.flat.data), _lib.ptr(self.flat.grad), _lib.ptr(self._m), _lib.ptr(self._v),
-                                                        _lib.ptr(self._adam_t), self.flat.numel, self._n_geo, float(g0["lr"]), float(g1["lr"]),
-                                                        float(g0["betas"][0]), float(g0["betas"][1]), float(g0["eps"]),
-                                                        _lib.ptr(self._tail_mask), _lib.ptr(self._tail_step), _lib.stream_ptr(dev)),
-                       "adam_step")
+        refresh between replays takes effect without re-capturing; a change inside a capture raises."""
+        return self._adam.set_mask(self._scalar_flags(), capturing)
 
     # The native step is written as four device phases separated by the (at most three) collectives, so that it can run eagerly, be
     # captured whole in one hipGraph (one rank) or be captured phase by phase with the collectives launched between the replays
     # (any backend, also gloo whose collectives are host code): capture(segmented=True).
+    def _phases(self, rays, true_edge, n_rays_global):
+        """-> (the step's record, its four phases): what _run_phases runs, or capture() records one by one."""
+        S = _Step()
+        return S, [lambda: self._ph_forward(S, rays, true_edge, n_rays_global), lambda: self._ph_composite_bwd(S),
+                   lambda: self._ph_mlp_bwd(S), lambda: self._ph_update(S)]
+
     def _ph_forward(self, S, rays, true_edge, n_rays_global):
-        from . import _lib
-        L = _lib.lib()
-        world = _world(self.group)
-        call, v, edge, scalars = self._forward(rays)
+        S.call, S.v, edge, S.scalars = self._forward(rays)
         dev = edge.device
         n_local = edge.numel()
-        S.update(call=call, v=v, scalars=scalars, dev=dev, world=world, n_local=n_local,
-                 n_glob=n_rays_global if n_rays_global is not None else n_local * world)
+        S.sync = self._sync()
+        S.n_glob = n_rays_global if n_rays_global is not None else n_local * _world(self.group)
         te = true_edge.reshape(-1).to(torch.float32).contiguous()
         assert te.numel() == n_local
-        S["d_edge"] = torch.empty(n_local, device=dev)
+        S.d_edge = torch.empty(n_local, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(L.emap_train_stats(_lib.ptr(edge), _lib.ptr(te), _lib.ptr(scalars), n_local, 2.0 * self.edge_weight / S["n_glob"],
-                                          _lib.ptr(S["d_edge"]), _lib.ptr(self._stats), _lib.stream_ptr(dev)), "train_stats")
-        S["stats"] = self._stats
+            _lib.check(_lib.lib().emap_train_stats(_lib.ptr(edge), _lib.ptr(te), _lib.ptr(S.scalars), n_local, 2.0 * self.edge_weight / S.n_glob,
+                                                   _lib.ptr(S.d_edge), _lib.ptr(self._stats), _lib.stream_ptr(dev)), "train_stats")
 
     def _ph_composite_bwd(self, S):
-        sc_glob = S["scalars"]
-        exactish = self.eikonal_sync in ("exact", "exact_lagged")
-        if S["world"] > 1 and exactish:      # self._stats now holds the GLOBAL sums
-            sc_glob = S["scalars"].clone()
-            sc_glob[4], sc_glob[6] = self._stats[0], self._stats[1]
-        S["sc_glob"] = sc_glob
-        g = self.flat.grad
-        both = not (S["world"] > 1 and exactish)
-        self.r.backward_into(S["call"], S["v"], S["d_edge"], None, self._igr, self._igr_ns if self.igr_ns_weight != 0.0 else None,
-                             flat=g[:self.flat.numel], scalars=sc_glob, stages=3 if both else 1)
-        S["staged"] = not both
-        S["lagged"] = S["staged"] and self.eikonal_sync == "exact_lagged"
-        if S["lagged"]:
+        exact = S.sync == "exact"            # self._stats now holds the GLOBAL sums
+        S.sc_glob = _global_mask_sums(S.scalars, self._stats) if exact else S.scalars
+        self._backward(S.call, S.v, S.d_edge, S.sc_glob, self.flat.grad[:self.flat.numel], stages=1 if exact else 3)
+        S.lagged = exact and self.eikonal_sync == "exact_lagged"
+        if S.lagged:
             # The two range maxima of this rank go into its slots of the bucket's tail (the SUM all-reduce of the bucket then works as an
             # all-gather of them: every other slot is zero) and become next step's GLOBAL maxima.  THIS step's sweep uses the previous
             # step's global maxima x 4 (the kernel rounds to a power of two) instead of waiting for a MAX all-reduce - or the rank's own
             # maxima where they exceed that, so that fp16 can never overflow: a rank whose gradients grew more than 4x in one step then
             # differs from the others in rounding for that step only.  The first step (no history) takes the exact path.
-            self._lag_publish(self.r.bwd_absmax(S["call"]), dist.get_rank(self.group))
+            self._lag_publish(self.r.bwd_absmax(S.call), dist.get_rank(self.group))
 
     def _lag_publish(self, cur: torch.Tensor, rank: int):
         """exact_lagged, before the sweep: write this rank's two range maxima `cur` into ITS two slots of the bucket's tail (all other
@@ -387,30 +455,24 @@ class Trainer:
         return self.flat.grad[n:n + 2 * self.MAX_RANKS]
 
     def _ph_mlp_bwd(self, S):
-        g = self.flat.grad
-        if S["lagged"] and not self._lag_valid:
-            self._lag.copy_(self.r.bwd_absmax(S["call"]))       # first step: the MAX all-reduce just ran; it seeds the history
-        if S["staged"]:
-            self.r.backward_into(S["call"], S["v"], S["d_edge"], None, self._igr, self._igr_ns if self.igr_ns_weight != 0.0 else None,
-                                 flat=g[:self.flat.numel], scalars=S["sc_glob"], stages=2)
-        if S["world"] > 1 and self.eikonal_sync == "local":
-            g[self.flat.numel:self.flat.numel + 5] = self._stats      # the statistics ride in the bucket's tail
+        if S.lagged and not self._lag_valid:
+            self._lag.copy_(self.r.bwd_absmax(S.call))       # first step: the MAX all-reduce just ran; it seeds the history
+        if S.sync == "exact":
+            self._backward(S.call, S.v, S.d_edge, S.sc_glob, self.flat.grad[:self.flat.numel], stages=2)
+        if S.sync == "local":
+            self._stats_slot().copy_(self._stats)      # the statistics ride in the bucket's tail
 
     def _ph_update(self, S):
-        from . import _lib
-        L = _lib.lib()
-        dev = S["dev"]
-        stats = self._stats
-        if S["world"] > 1 and self.eikonal_sync == "local":
-            stats = self.flat.grad[self.flat.numel:self.flat.numel + 5]
-        if S["lagged"]:
+        dev = self.flat.data.device
+        if S.lagged:
             self._lag_collect()
         self.optimizer.step()      # frozen scalars are skipped inside the kernel (device mask, refresh_trainable_mask)
         self.r.udf_network.invalidate_packed()   # the flat update does not bump the per-parameter version counters
+        stats = self._stats_slot() if S.sync == "local" else self._stats      # "local": the all-reduced bucket's tail holds the global sums
         out = torch.empty(2, device=dev)         # a fresh tensor per step: callers keep what step() returned
         with torch.cuda.device(dev):
-            _lib.check(L.emap_train_loss(_lib.ptr(stats), self.edge_weight / S["n_glob"], self.igr_weight, self.igr_ns_weight, _lib.ptr(out),
-                                         _lib.stream_ptr(dev)), "train_loss")
+            _lib.check(_lib.lib().emap_train_loss(_lib.ptr(stats), self.edge_weight / S.n_glob, self.igr_weight, self.igr_ns_weight,
+                                                  _lib.ptr(out), _lib.stream_ptr(dev)), "train_loss")
         self.last_stats = out
         return out
 
@@ -428,53 +490,45 @@ class Trainer:
         stats = (0, ar(lambda S: self._stats, dist.ReduceOp.SUM))
         if self.eikonal_sync == "exact_lagged" and self._lag_valid:      # the maxima ride in the gradient bucket's tail
             return [stats, (2, grad)]
-        return [stats, (1, ar(lambda S: self.r.bwd_absmax(S["call"]), dist.ReduceOp.MAX)), (2, grad)]
+        return [stats, (1, ar(lambda S: self.r.bwd_absmax(S.call), dist.ReduceOp.MAX)), (2, grad)]
 
     def _step_native(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int]):
-        S = {}
         coll = self._collectives()
-        phases = [lambda: self._ph_forward(S, rays, true_edge, n_rays_global), lambda: self._ph_composite_bwd(S),
-                  lambda: self._ph_mlp_bwd(S), lambda: self._ph_update(S)]
-        out = None
-        for i, ph in enumerate(phases):
-            out = ph()
-            for after, fn in coll:
-                if after == i:
-                    fn(S)
-        return out
+        S, phases = self._phases(rays, true_edge, n_rays_global)
+        return _run_phases(phases, coll, S)
 
     def step(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int] = None):
         """One optimizer step on this rank's rays.  Returns the device tensor [loss, edge_loss] of the GLOBAL batch (no host
         synchronisation happens here)."""
         if self.native_tail:
-            self.refresh_trainable_mask(capturing=torch.cuda.is_current_stream_capturing())
+            self.refresh_trainable_mask()
             return self._step_native(rays, true_edge, n_rays_global)
-        world = _world(self.group)
+        # the torch tail (the CPU tests): the native phases' arithmetic in element-wise torch ops, torch.optim.Adam, collectives in line
+        sync = self._sync()
         call, v, edge, scalars = self._forward(rays)
         n_local = edge.numel()
-        n_glob = n_rays_global if n_rays_global is not None else n_local * world
-        te = true_edge.reshape(-1).to(edge.dtype)
-        diff = edge.reshape(-1) - te
-        # stats: [sum(relax), sum(near), sum(relax*err), sum(near*err), sum(diff^2)] - scalars[3:7] = e_rel, c_rel, e_ns, c_ns
+        n_glob = n_rays_global if n_rays_global is not None else n_local * _world(self.group)
+        diff = edge.reshape(-1) - true_edge.reshape(-1).to(edge.dtype)
+        # scalars[3:7] = e_rel, c_rel, e_ns, c_ns
         stats = torch.cat([scalars[self._idx], (diff * diff).sum().reshape(1)])
         sc_glob = scalars
-        if world > 1 and self.eikonal_sync in ("exact", "exact_lagged"):      # (no fp16 range scale on this path: lagged = exact)
+        if sync == "exact":      # (no fp16 range scale on this path: lagged = exact)
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=self.group)
-            sc_glob = scalars.clone()
-            sc_glob[4], sc_glob[6] = stats[0], stats[1]
-        d_edge = diff * (2.0 * self.edge_weight / n_glob)
-        g = self.flat.grad
-        self._backward(call, v, d_edge, sc_glob, g[:self.flat.numel])
-        if world > 1:
-            if self.eikonal_sync == "local":
-                g[self.flat.numel:self.flat.numel + 5] = stats      # the statistics ride in the bucket's tail
-            dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group)
-            if self.eikonal_sync == "local":
-                stats = g[self.flat.numel:self.flat.numel + 5].clone()
+            sc_glob = _global_mask_sums(scalars, stats)
+        self._backward(call, v, diff * (2.0 * self.edge_weight / n_glob), sc_glob, self.flat.grad[:self.flat.numel])
+        if sync == "local":
+            self._stats_slot().copy_(stats)      # the statistics ride in the bucket's tail
+        if sync is not None:
+            dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM, group=self.group)
+            stats = self._stats_slot().clone() if sync == "local" else stats
         # torch.optim.Adam on the two flat parameters cannot skip single elements: a frozen scalar (requires_grad = False,
-        # runner_udf.py:144-154) is put back and its moments cleared (CPU tests only; the native path masks inside the kernel)
-        frozen = [i for p, f in zip(self.scalars, self._scalar_flags()) if not f
-                  for i in range(self.flat.offsets[id(p)] - self.flat.offsets[id(self.scalars[0])], self.flat.offsets[id(p)] - self.flat.offsets[id(self.scalars[0])] + p.numel())]
+        # runner_udf.py:144-154) is put back and its moments cleared (the native path masks inside the kernel)
+        s0 = self.flat.span(self.scalars)[0]
+        frozen = []                              # indices into p_sc
+        for p, trainable in zip(self.scalars, self._scalar_flags()):
+            if not trainable:
+                a, b = self.flat.span([p])
+                frozen += range(a - s0, b - s0)
         keep = self.p_sc.data[frozen].clone() if frozen else None
         self.optimizer.step()
         if frozen:
@@ -484,11 +538,8 @@ class Trainer:
                 if k in st:
                     st[k][frozen] = 0.0
         self.r.udf_network.invalidate_packed()   # the flat update does not bump the per-parameter version counters
-        edge_loss = stats[4] / n_glob * self.edge_weight
-        loss = edge_loss + self.igr_weight * stats[2] / (stats[0] + 1e-5) + self.igr_ns_weight * stats[3] / (stats[1] + 1e-5)
-        self.last_stats = torch.stack([loss, edge_loss])
+        self.last_stats = torch.stack(_loss_from_stats(stats, n_glob, self.edge_weight, self.igr_weight, self.igr_ns_weight))
         return self.last_stats
-
 
     def capture(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int] = None, warmup: int = 3,
                 segmented: Optional[bool] = None):
@@ -505,9 +556,8 @@ class Trainer:
                 raise ValueError("Trainer.capture(segmented=True) needs the native tail (native_tail=True): the per-phase graphs are the "
                                  "native step's four device phases")
             segmented = False
-        world = _world(self.group)
         if segmented is None:
-            segmented = world > 1
+            segmented = _world(self.group) > 1
         if rays.get("t_rand") is None and (rays.get("perturb_overwrite", -1) != 0) and self.r.perturb > 0:
             raise ValueError("Trainer.capture: pass rays['t_rand'] explicitly (the reference's CPU-generator jitter draw plus its "
                              "host-to-device copy cannot be part of a device graph)")
@@ -520,28 +570,25 @@ class Trainer:
             for _ in range(max(warmup, 1)):
                 self.step(static, te, n_rays_global)
         torch.cuda.current_stream(dev).wait_stream(side)
+        graphs, outs = [], []
+
+        def captured(fn):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
+                outs.append(fn())
+            graphs.append(g)
+            return g
+
         if not segmented:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                out = self.step(static, te, n_rays_global)
-            graphs, coll, S = [graph], [], None
+            captured(lambda: self.step(static, te, n_rays_global))
+            coll, S = [], None
         else:
-            S = {}
+            # capture does not execute: every phase is replayed as soon as it is captured and its collectives run, so that this pass is
+            # one real step and the next phase is captured on real data
             coll = self._collectives()
-            phases = [lambda: self._ph_forward(S, static, te, n_rays_global), lambda: self._ph_composite_bwd(S),
-                      lambda: self._ph_mlp_bwd(S), lambda: self._ph_update(S)]
-            graphs, out = [], None
-            pool = None
-            for i, ph in enumerate(phases):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool):
-                    out = ph()
-                pool = g.pool()
-                graphs.append(g)
-                g.replay()                  # capture does not execute: run the phase now, so that this pass is one real step and
-                for after, fn in coll:      # the next phase is captured on real data
-                    if after == i:
-                        fn(S)
+            S, phases = self._phases(static, te, n_rays_global)
+            _run_phases([lambda ph=ph: captured(ph).replay() for ph in phases], coll, S)
+        out = outs[-1]
         keep = self.r.live_buffers()
 
         def replay(rays: Optional[Dict] = None, true_edge: Optional[torch.Tensor] = None):
@@ -553,11 +600,7 @@ class Trainer:
                         static[k].copy_(v)
             if true_edge is not None:
                 te.copy_(true_edge)
-            for i, g in enumerate(graphs):
-                g.replay()
-                for after, fn in coll:
-                    if after == i:
-                        fn(S)
+            _run_phases([g.replay for g in graphs], coll, S)
             return out
 
         replay.graph = graphs[0] if len(graphs) == 1 else None
@@ -622,36 +665,26 @@ class FusedAdam(torch.optim.Optimizer):
         self._flat = FlatParams(geo + tail)     # (or the caller) put there, so they are put back
         for p, g_ in zip(geo + tail, grads):
             p.grad = g_
-        dev = self._flat.data.device
-        self._n_geo = sum(p.numel() for p in geo)
         self._geo, self._tail = geo, tail
-        n = self._flat.numel
-        self._m, self._v = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
-        self._t = torch.zeros(1, device=dev)
-        self._tail_mask = torch.ones(max(n - self._n_geo, 1), device=dev)
-        self._tail_step = torch.zeros(max(n - self._n_geo, 1), device=dev)
-        self._flags = None
+        self._adam = _FlatAdam(self._flat.numel, sum(p.numel() for p in geo), [p.numel() for p in tail], self._flat.data.device)
         self._zeros = {}
 
     # ---- checkpointing (runner_udf.py:260 saves optimizer.state_dict(), :273 loads it): torch.optim.Adam's per-parameter layout ----
-    def _span(self, p):
-        o = self._flat.offsets[id(p)]
-        return o, o + p.numel()
-
     def _mirror_state(self):
         """Expose the flat moments as ``self.state[p] = {step, exp_avg, exp_avg_sq}`` (views of the flat buffers, torch.optim.Adam's
         keys), so that ``Optimizer.state_dict()`` writes a checkpoint a stock Adam can load and vice versa.  A parameter that has
         never been stepped (frozen so far) has no entry, exactly like torch's Adam.  Reads the step counters: a host sync."""
-        t_geo = float(self._t.item())
-        tail_steps = self._tail_step.tolist()
+        A = self._adam
+        t_geo = float(A.t.item())
+        tail_steps = A.tail_step.tolist()
         self.state.clear()
         for p in self._geo + self._tail:
-            a, b = self._span(p)
-            step = t_geo if a < self._n_geo else float(tail_steps[a - self._n_geo])
+            a, b = self._flat.span([p])
+            step = t_geo if a < A.n_geo else float(tail_steps[a - A.n_geo])
             if step <= 0:
                 continue
-            self.state[p] = {"step": torch.tensor(step, dtype=torch.float32), "exp_avg": self._m[a:b].view(p.shape),
-                             "exp_avg_sq": self._v[a:b].view(p.shape)}
+            self.state[p] = {"step": torch.tensor(step, dtype=torch.float32), "exp_avg": A.m[a:b].view(p.shape),
+                             "exp_avg_sq": A.v[a:b].view(p.shape)}
 
     def state_dict(self):
         if self._flat is not None:
@@ -665,27 +698,27 @@ class FusedAdam(torch.optim.Optimizer):
         super().load_state_dict(state_dict)           # validates the groups, casts the tensors to the parameters' device
         if self._flat is None:
             self._build()
-        self._m.zero_(); self._v.zero_(); self._t.zero_(); self._tail_step.zero_()
+        A = self._adam
+        A.m.zero_(); A.v.zero_(); A.t.zero_(); A.tail_step.zero_()
         t_geo = 0.0
         for p in self._geo + self._tail:
             st = self.state.get(p)
             if not st:
                 continue
-            a, b = self._span(p)
-            self._m[a:b].copy_(st["exp_avg"].reshape(-1))
-            self._v[a:b].copy_(st["exp_avg_sq"].reshape(-1))
+            a, b = self._flat.span([p])
+            A.m[a:b].copy_(st["exp_avg"].reshape(-1))
+            A.v[a:b].copy_(st["exp_avg_sq"].reshape(-1))
             step = float(st["step"])
-            if a < self._n_geo:
+            if a < A.n_geo:
                 t_geo = max(t_geo, step)
             else:
-                self._tail_step[a - self._n_geo:b - self._n_geo] = step
-        self._t.fill_(t_geo)
-        self._flags = None
+                A.tail_step[a - A.n_geo:b - A.n_geo] = step
+        A.t.fill_(t_geo)
+        A.flags = None                                # the next step writes the mask afresh
         self._mirror_state()
 
     @torch.no_grad()
     def step(self, closure=None):
-        from . import _lib
         loss = closure() if closure is not None else None
         if self._flat is None:
             self._build()
@@ -705,48 +738,21 @@ class FusedAdam(torch.optim.Optimizer):
             off += p.numel()
         if geo_ptr is None:
             parts = [p.grad.reshape(-1) for p in self._geo]
-        flags = []
         for p in self._tail:
-            has = p.grad is not None
-            flags += [1.0 if has else 0.0] * p.numel()
-            if has:
+            if p.grad is not None:
                 parts.append(p.grad.reshape(-1))
             else:
                 z = self._zeros.get(p.numel())
                 if z is None:
                     z = self._zeros[p.numel()] = torch.zeros(p.numel(), device=dev)
                 parts.append(z)
-        if flags != self._flags:                # rare: a set_trainable() of the runner
-            self._tail_mask[:len(flags)].copy_(torch.tensor(flags))
-            self._flags = flags
+        self._adam.set_mask(p.grad is not None for p in self._tail)      # changes rarely: a set_trainable() of the runner
         live = self._live_groups()              # the CURRENT group dicts (see _live_groups): lr is read per step
         geo_group, tail_groups = live[0], live[1:]
         lr_tail = tail_groups[0]["lr"] if tail_groups else geo_group["lr"]
-        b1, b2 = geo_group["betas"]
-        L, st = _lib.lib(), _lib.stream_ptr(dev)
-        with torch.cuda.device(dev):
-            if geo_ptr is None:
-                grad = torch.cat(parts)
-                _lib.check(L.emap_adam_step_masked(_lib.ptr(self._flat.data), _lib.ptr(grad), _lib.ptr(self._m), _lib.ptr(self._v),
-                                                   _lib.ptr(self._t), self._flat.numel, self._n_geo, float(geo_group["lr"]),
-                                                   float(lr_tail), float(b1), float(b2), float(geo_group["eps"]),
-                                                   _lib.ptr(self._tail_mask), _lib.ptr(self._tail_step), st), "adam_step")
-            else:
-                # two launches on disjoint ranges, same arithmetic: the geometry range straight from the caller's flat gradient buffer
-                # (its step counter self._t is bumped by this call), the few tail scalars gathered as before (their own step counts)
-                import ctypes as C
-                ng, nt = self._n_geo, self._flat.numel - self._n_geo
-                _lib.check(L.emap_adam_step(_lib.ptr(self._flat.data), C.c_void_p(geo_ptr), _lib.ptr(self._m), _lib.ptr(self._v),
-                                            _lib.ptr(self._t), ng, ng, float(geo_group["lr"]), float(lr_tail), float(b1), float(b2),
-                                            float(geo_group["eps"]), st), "adam_step")
-                if nt > 0:
-                    gt = torch.cat(parts)
-                    if getattr(self, "_t_tail_dummy", None) is None:
-                        self._t_tail_dummy = torch.zeros(1, device=dev)
-                    _lib.check(L.emap_adam_step_masked(_lib.ptr(self._flat.data[ng:]), _lib.ptr(gt), _lib.ptr(self._m[ng:]), _lib.ptr(self._v[ng:]),
-                                                       _lib.ptr(self._t_tail_dummy), nt, 0, float(geo_group["lr"]), float(lr_tail),
-                                                       float(b1), float(b2), float(geo_group["eps"]), _lib.ptr(self._tail_mask),
-                                                       _lib.ptr(self._tail_step), st), "adam_step")
+        # geo_ptr: the geometry range straight from the caller's flat gradient buffer, the few tail scalars gathered as before
+        grad = torch.cat(parts) if parts else None
+        self._adam.step(self._flat.data, grad, geo_group["lr"], lr_tail, geo_group["betas"], geo_group["eps"], geo_grad_ptr=geo_ptr)
         # the in-place flat update is invisible to the per-tensor version counters UDFNetwork.packed() keys its fragment cache on
         inc = getattr(torch.autograd.graph, "increment_version", None)
         for p in self._geo:
@@ -775,7 +781,7 @@ def training_step(render_fn: Callable[[], Dict[str, torch.Tensor]], true_edge: t
     n_glob = n_rays_global if n_rays_global is not None else n_local * world
     sums = out["eikonal_sums"].detach()
     mse_sum = ((edge - true_edge) ** 2).sum()
-    stats = torch.stack([sums[1], sums[3], mse_sum.detach(), sums[0], sums[2]]).to(torch.float32)
+    stats = torch.stack([sums[1], sums[3], sums[0], sums[2], mse_sum.detach()]).to(torch.float32)      # the order of _loss_from_stats
     if world > 1:
         dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=group)   # global mask counts before backward (+ the loss statistics)
     # local numerators with gradient: ge_local * (c_local + 1e-5)
@@ -790,6 +796,4 @@ def training_step(render_fn: Callable[[], Dict[str, torch.Tensor]], true_edge: t
     if world > 1:
         dist.all_reduce(flat.grad, op=dist.ReduceOp.SUM, group=group)
     optimizer.step()
-    edge_loss = stats[2] / n_elem_glob * edge_weight
-    loss = edge_loss + igr_weight * stats[3] / (stats[0] + 1e-5) + igr_ns_weight * stats[4] / (stats[1] + 1e-5)
-    return loss, edge_loss
+    return _loss_from_stats(stats, n_elem_glob, edge_weight, igr_weight, igr_ns_weight)

@@ -1,0 +1,124 @@
+"""The training step bit for bit: sha256 of everything three optimizer steps leave behind.
+
+The parity tests bound the step by tolerances; a host-side slip in emap_amd/parallel.py - a wrong argument order in the Adam call, a
+mask refreshed one step late, a phase run twice in a replay, the statistics read from the wrong slot - could hide under them.  The
+statistics, loss and Adam kernels of csrc/train.hip use no atomics and the backward is bit-stable run to run
+(test_gpu_backward_digests.py), so every case here takes three steps from a fixed start and compares one digest over the flat
+parameters, both moment buffers, the geometry step counter, the tail step counts and the three returned [loss, edge_loss] tensors
+(FusedAdam: the parameters and the tensors of its state_dict()) with the digest recorded from the parent commit.  Rays, jitter and
+targets come from synthetic.make_rays / make_t_rand / make_true_edge, weights from synthetic.make_udf_state, the FusedAdam cases'
+parameters and gradients from numpy's PCG64: nothing depends on the torch version."""
+import hashlib
+
+import numpy as np
+import pytest
+import torch
+
+from emap_amd import synthetic
+from emap_amd.parallel import Trainer, FusedAdam
+from test_gpu_parity import mk, DEV
+from test_gpu_render_modes import mk_renderer
+
+pytestmark = pytest.mark.gpu
+
+N_RAYS = 64
+
+
+def _digest(tensors):
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for x in tensors:
+        h.update(x.detach().to(torch.float32).contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
+def _batch(seed):
+    ro, rd, near, far, ds = [v.to(DEV) for v in synthetic.make_rays(N_RAYS, seed=seed)]
+    rays = {"rays_o": ro, "rays_d": rd, "near": near, "far": far, "depth_scale": ds, "cos_anneal_ratio": 1.0, "flip_saturation": 0.9,
+            "t_rand": synthetic.make_t_rand(N_RAYS, seed=seed + 100).to(DEV)}
+    return rays, synthetic.make_true_edge(N_RAYS, seed=seed + 200).to(DEV)
+
+
+def _adam_state(tr):
+    """The flat Adam state of a native Trainer: moments, geometry step counter, tail step counts"""
+    a = tr._adam
+    return [a.m, a.v, a.t, a.tail_step]
+
+
+def trainer_digest(name, ns, ni, steps, capture=False, freeze_beta=False, **mode):
+    net, _, _ = mk(name, "f16x3")
+    r = mk_renderer(net, ns, ni, steps, **mode)
+    tr = Trainer(r, lr_geo=1e-3, lr=5e-3, igr_weight=0.1, igr_ns_weight=0.05)
+    batches = [_batch(31), _batch(32), _batch(33)]
+    outs = []
+    if capture:      # one warm-up step and the capture on the first batch, then three replays: the second and third on fresh rays
+        replay = tr.capture(*batches[0], warmup=1)
+        for i, (rays, te) in enumerate(batches):
+            outs.append((replay() if i == 0 else replay(rays, te)).clone())
+    else:
+        for i, (rays, te) in enumerate(batches):
+            outs.append(tr.step(rays, te))
+            if freeze_beta and i == 0:
+                r.beta_network.beta.requires_grad_(False)      # the next step rewrites the device mask of the fused Adam
+    d = _digest([tr.flat.data] + _adam_state(tr) + outs)
+    tr.check_errors()
+    assert all(bool(torch.isfinite(o).all()) for o in outs)
+    return d
+
+
+def fused_adam_digest(flat_geo_grads):
+    """FusedAdam alone on the parameter groups of test_gpu_round5.py: three steps with fixed gradients; the third tail parameter is frozen
+    at first and gets its gradient from step 2 on.  flat_geo_grads: the geometry gradients are consecutive views of one buffer (the
+    optimizer then reads them in place: one launch for the geometry range, one for the tail)."""
+    rng = np.random.Generator(np.random.PCG64(501))
+    draw = lambda *s: torch.from_numpy(rng.standard_normal(s, dtype=np.float32)).to(DEV)
+    geo = [torch.nn.Parameter(draw(*s)) for s in [(16, 7), (16,), (16, 1), (8, 16), (8,)]]
+    tail = [torch.nn.Parameter(draw(1)) for _ in range(4)]
+    tail[2].requires_grad_(False)
+    opt = FusedAdam([{"params": geo, "lr": 1e-3}, {"params": tail[:2]}, {"params": tail[2:]}, {"params": []}], lr=5e-3)
+    n_geo = sum(p.numel() for p in geo)
+    for s in range(3):
+        if s == 1:
+            tail[2].requires_grad_(True)
+        opt.zero_grad()
+        buf, off = draw(n_geo), 0
+        for p in geo:
+            g = buf[off:off + p.numel()].view(p.shape)
+            p.grad = g if flat_geo_grads else g.clone()
+            off += p.numel()
+        for p in tail:
+            g = draw(1)
+            if p.requires_grad:
+                p.grad = g
+        opt.step()
+    state = opt.state_dict()["state"]
+    return _digest(geo + tail + [state[k][f] for k in sorted(state) for f in ("step", "exp_avg", "exp_avg_sq")])
+
+
+CASES = {
+    "a/eager/d4w128L10": lambda: trainer_digest("d4w128L10", 32, 32, 4),
+    "b/eager/d8w256L10": lambda: trainer_digest("d8w256L10", 64, 64, 4),
+    "c/capture/d8w256L10": lambda: trainer_digest("d8w256L10", 64, 64, 4, capture=True),
+    "d/freeze_beta/d4w128L10": lambda: trainer_digest("d4w128L10", 32, 32, 4, freeze_beta=True),
+    "e/plain/d4w128L10": lambda: trainer_digest("d4w128L10", 32, 32, 4, use_unbias_render=False),
+    "f/fused_adam": lambda: fused_adam_digest(False),
+    "g/fused_adam/flat_geo_grads": lambda: fused_adam_digest(True),
+}
+
+# recorded on an MI355X from the parent commit (emap_amd/parallel.py as it stood before the step's host path was consolidated), twice, in
+# two separate processes that agreed on every case
+DIGESTS = {
+    "a/eager/d4w128L10": "041700e329ddf80cbeac2468f48d8c9ebe83fbe3eb71425bbee8fef3d74e03ab",
+    "b/eager/d8w256L10": "550aa0ac959a61ccb6a59b00130fba093e7d6dd6e2e5b8c7588e2ccdaa23f7ef",
+    "c/capture/d8w256L10": "c69b6da5905dfc543b39038ea6b87d96f5e4ced032addab8c029623748d72757",
+    "d/freeze_beta/d4w128L10": "582d0a22a3ad292f02caacaf5cc2eb9650c3b96e660c2fcd9c20b727506a1695",
+    "e/plain/d4w128L10": "1d49753f21430965e48a300a4541ecc5bd795e6b04dae45e0183fe57579f1311",
+    # the two launches over disjoint ranges do the arithmetic of the one: the same digest
+    "f/fused_adam": "c680b40d62d440d7026c93cab183acdaa1d487b41b47a20b3ccdbd2bc0b84a7a",
+    "g/fused_adam/flat_geo_grads": "c680b40d62d440d7026c93cab183acdaa1d487b41b47a20b3ccdbd2bc0b84a7a",
+}
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_train_step_digest(case):
+    assert CASES[case]() == DIGESTS[case]
