@@ -613,6 +613,14 @@ int emap_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int impor
     return launch_sample_rays(ds, img_idx, batch, importance, seed, offset, counter_dev, pixels_in, out, static_cast<hipStream_t>(stream));
 }
 
+int emap_gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w) {
+    return gen_rays_count(ds, resolution_level, n, h, w);
+}
+int emap_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
+                     float* depth_scale, void* stream) {
+    return launch_gen_rays_at(ds, img_idx, resolution_level, first, count, rays_o, rays_d, depth_scale, static_cast<hipStream_t>(stream));
+}
+
 int emap_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge,
                      float* stats5, void* stream) {
     return launch_train_stats(edge, true_edge, scalars, N, d_scale, d_edge, stats5, static_cast<hipStream_t>(stream));

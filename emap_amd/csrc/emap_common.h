@@ -335,6 +335,9 @@ void linspace_host(float start, float end, int steps, float* out);
 // rays.hip
 int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset, uint64_t* counter,
                        const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st);
+int gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w);
+int launch_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
+                       float* depth_scale, hipStream_t st);
 // train.hip: the scalar tail of a training step
 int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
                        hipStream_t st);

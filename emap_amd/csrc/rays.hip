@@ -137,4 +137,85 @@ int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int imp
     return check_launch("sample_rays");
 }
 
+// ---- full-image rays: Dataset.gen_rays_at (dataset.py:137-167) ----------------------------------------------------------------------
+// The rays of a whole validation view, from the K^-1 and poses the sampler already keeps on the device.  The reference builds a
+// meshgrid over the image on the HOST, runs two batched 3x3 matmuls over its pixels and copies five tensors to the GPU; here one thread
+// per ray writes rays [first, first + count) of the view in row-major (H/l, W/l) order - the order of the reference's TRANSPOSED
+// rays_o / rays_v (:162-163) - so a caller renders a view chunk by chunk and the view's rays never exist in full.
+// Pixel coordinates are torch.linspace(0, W-1, W//l) / linspace(0, H-1, H//l) (:142-143), non-integer for l > 1: ATen's formula, a step
+// from the start for the first half and from the end for the second, each product and difference rounded on its own.
+// The camera arithmetic is sample_ray's above, on those coordinates.  Bound: HBM writes, 28 B per ray; nothing is read but 25 floats.
+
+__device__ __forceinline__ float view_coord(float last, int steps, int i) {
+#pragma clang fp contract(off)
+    if (steps == 1) return 0.0f;
+    const float step = last / (float)(steps - 1);
+    const float up = step * (float)i, down = step * (float)(steps - i - 1);
+    return (i < steps / 2) ? up : last - down;
+}
+
+struct ViewArgs {
+    const float* kinv;
+    const float* pose;
+    const int32_t* image_perm;
+    float *rays_o, *rays_d, *depth_scale;
+    long long first, count;
+    int32_t img_idx, n_images, H, W, h, w;
+};
+
+__global__ __launch_bounds__(256) void gen_rays_at_kernel(const ViewArgs a) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.count) return;
+    int img = a.img_idx;
+    if (img < 0) {                                              // entry -1 - img_idx of the runner's image permutation
+        const int k = (int)((-1LL - (long long)img) % a.n_images);
+        img = a.image_perm ? a.image_perm[k] : k;
+    }
+    const long long i = a.first + t;
+    const int iy = (int)(i / a.w), ix = (int)(i - (long long)iy * a.w);
+    const float fx = view_coord((float)(a.W - 1), a.w, ix), fy = view_coord((float)(a.H - 1), a.h, iy);   // :142-143
+    const float* K = a.kinv + (size_t)img * 9;
+    const float* P = a.pose + (size_t)img * 16;
+    // p = K^-1 [x, y, 1]   (:145-150)
+    const float p0 = K[0] * fx + K[1] * fy + K[2], p1 = K[3] * fx + K[4] * fy + K[5], p2 = K[6] * fx + K[7] * fy + K[8];
+    const float n = sqrtf(p0 * p0 + p1 * p1 + p2 * p2);
+    const float v0 = p0 / n, v1 = p1 / n, v2 = p2 / n;          // :151
+    a.depth_scale[t] = v2;                                      // :152
+    float* d = a.rays_d + t * 3;                                // :153-155
+    d[0] = P[0] * v0 + P[1] * v1 + P[2] * v2;
+    d[1] = P[4] * v0 + P[5] * v1 + P[6] * v2;
+    d[2] = P[8] * v0 + P[9] * v1 + P[10] * v2;
+    float* o = a.rays_o + t * 3;                                // :156-158
+    o[0] = P[3]; o[1] = P[7]; o[2] = P[11];
+}
+
+int gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w) {
+    if (!ds) { set_error("gen_rays_count: null dataset"); return EMAP_E_INVALID; }
+    if (ds->H < 1 || ds->W < 1) { set_error("gen_rays_count: image size %d x %d", ds->W, ds->H); return EMAP_E_INVALID; }
+    if (resolution_level < 1) { set_error("gen_rays_count: resolution_level must be >= 1 (got %d)", resolution_level); return EMAP_E_INVALID; }
+    const int hh = ds->H / resolution_level, ww = ds->W / resolution_level;
+    if (hh == 0 || ww == 0) { set_error("gen_rays_count: resolution_level %d leaves no pixel of a %d x %d image", resolution_level, ds->W, ds->H); return EMAP_E_INVALID; }
+    if (n) *n = (int64_t)hh * ww;
+    if (h) *h = hh;
+    if (w) *w = ww;
+    return EMAP_OK;
+}
+
+int launch_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
+                       float* depth_scale, hipStream_t st) {
+    int64_t total = 0;
+    ViewArgs a;
+    if (int rc = gen_rays_count(ds, resolution_level, &total, &a.h, &a.w)) return rc;
+    if (!ds->kinv || !ds->pose || ds->n_images < 1) { set_error("gen_rays_at: incomplete dataset"); return EMAP_E_INVALID; }
+    if (img_idx >= ds->n_images) { set_error("gen_rays_at: image %d out of range (%d images)", img_idx, ds->n_images); return EMAP_E_INVALID; }
+    if (first < 0 || count < 0) { set_error("gen_rays_at: negative first / count"); return EMAP_E_INVALID; }
+    if (count > total - first) { set_error("gen_rays_at: [first, first + count) leaves the view's %lld rays", (long long)total); return EMAP_E_INVALID; }
+    if (count == 0) return EMAP_OK;
+    if (!rays_o || !rays_d || !depth_scale) { set_error("gen_rays_at: null pointer"); return EMAP_E_INVALID; }
+    a.kinv = ds->kinv; a.pose = ds->pose; a.image_perm = ds->image_perm; a.rays_o = rays_o; a.rays_d = rays_d; a.depth_scale = depth_scale;
+    a.first = first; a.count = count; a.img_idx = img_idx; a.n_images = ds->n_images; a.H = ds->H; a.W = ds->W;
+    hipLaunchKernelGGL(gen_rays_at_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, a);
+    return check_launch("gen_rays_at");
+}
+
 }  // namespace emap

@@ -5,8 +5,8 @@
 registers ``src.models.udf_model``, ``src.models.udf_renderer_blending``, ``src.models.embedder`` and
 ``src.models.loss`` in ``sys.modules`` as aliases of the emap_amd modules of the same names, so
 ``runner_base.py:9-13``'s imports resolve to the HIP-backed classes.  Where the reference's other modules can be imported
-it also re-routes the two callers either side of the path: ``Dataset.gen_random_rays_patches_at`` (on-device ray sampler,
-SURVEY f3) and - once ``src.runner.runner_udf`` is imported, call ``install()`` again or ``patch_runner()`` - the
+it also re-routes the callers either side of the path: ``Dataset.gen_random_rays_patches_at`` and ``Dataset.gen_rays_at``
+(on-device ray sampler and full-image rays) and - once ``src.runner.runner_udf`` is imported, call ``install()`` again or ``patch_runner()`` - the
 validation loop (reduced-output renders).  See INTEGRATION.md.
 """
 import importlib
@@ -33,6 +33,19 @@ def _default_seed():
     return seed
 
 
+def _dataset_sampler(dataset, sampler_cls=None):
+    """The dataset's ``DeviceRaySampler``, made on first use: the one upload of its edge maps / intrinsics / poses."""
+    s = getattr(dataset, "_emap_sampler", None)
+    if s is None:
+        cls = sampler_cls
+        if cls is None:
+            from .ray_sampler import DeviceRaySampler as cls
+        seed = getattr(dataset, "emap_seed", None)
+        s = cls(dataset.edges, dataset.intrinsics_all, dataset.pose_all, device=dataset.device, seed=_default_seed() if seed is None else seed)
+        dataset._emap_sampler = s
+    return s
+
+
 def dataset_method(sampler_cls=None, original=None):
     """Replacement for ``Dataset.gen_random_rays_patches_at`` (src/dataset/dataset.py:222-307): the first call uploads the dataset's
     edge maps / intrinsics / poses once (``DeviceRaySampler``), every call is then ONE kernel launch and no host->device copy.
@@ -44,20 +57,26 @@ def dataset_method(sampler_cls=None, original=None):
         import torch
         if original is not None and torch.device(self.device).type != "cuda":
             return original(self, img_idx, batch_size, importance_sample)
-        s = getattr(self, "_emap_sampler", None)
-        if s is None:
-            cls = sampler_cls
-            if cls is None:
-                from .ray_sampler import DeviceRaySampler as cls
-            seed = getattr(self, "emap_seed", None)
-            s = cls(self.edges, self.intrinsics_all, self.pose_all, device=self.device, seed=_default_seed() if seed is None else seed)
-            self._emap_sampler = s
+        s = _dataset_sampler(self, sampler_cls)
         # the reference takes the importance branch only when the dataset has masks (:236-238)
         smp = s.gen_random_rays_patches_at(int(img_idx), batch_size, importance_sample=bool(importance_sample and self.masks is not None))
         return {"rays": {k: smp["rays"][k] for k in ("rays_o", "rays_v", "edge")}, "pose": self.pose_all[int(img_idx)],
                 "intrinsics": self.intrinsics_all[int(img_idx)], "rays_ndc_uv": smp["rays_ndc_uv"],
                 "rays_norm_XYZ_cam": smp["rays_norm_XYZ_cam"], "depth_scale": smp["depth_scale"]}
     return gen_random_rays_patches_at
+
+
+def dataset_view_method(sampler_cls=None, original=None):
+    """Replacement for ``Dataset.gen_rays_at`` (src/dataset/dataset.py:137-167), the rays of a validation view: one kernel launch on the
+    dataset's ``DeviceRaySampler`` (shared with ``gen_random_rays_patches_at``) instead of a host meshgrid, two batched matmuls over
+    the image and five host->device copies.  Returns the reference's 5-tuple with its shapes - depth_scale un-transposed, as there.
+    A dataset on a non-CUDA device keeps the reference's own method (`original`)."""
+    def gen_rays_at(self, img_idx, resolution_level=1):
+        import torch
+        if original is not None and torch.device(self.device).type != "cuda":
+            return original(self, img_idx, resolution_level=resolution_level)
+        return _dataset_sampler(self, sampler_cls).gen_rays_at(int(img_idx), resolution_level)
+    return gen_rays_at
 
 
 def validate_wrapper(orig_validate):
@@ -84,11 +103,14 @@ def _patch_dataset():
         ds = importlib.import_module("src.dataset.dataset")
     except Exception:
         return False
-    if getattr(ds.Dataset.gen_random_rays_patches_at, "_emap_patched", False):
-        return True
-    fn = dataset_method(original=ds.Dataset.gen_random_rays_patches_at)
-    fn._emap_patched = True
-    ds.Dataset.gen_random_rays_patches_at = fn
+    for name, make in (("gen_random_rays_patches_at", dataset_method), ("gen_rays_at", dataset_view_method)):
+        orig = getattr(ds.Dataset, name, None)
+        if orig is None or getattr(orig, "_emap_patched", False):
+            continue
+        fn = make(original=orig)
+        fn._emap_patched = True
+        fn.__wrapped__ = orig
+        setattr(ds.Dataset, name, fn)
     return True
 
 

@@ -11,6 +11,9 @@ Wire format respected: ``meta_data.json`` {scene_box{near,far,radius,aabb}, heig
 camtoworld 4x4, rgb_path}]} (dataset.py:66-104) via ``from_meta``; edge maps are whatever ``cv.imread(path, 0) / 255`` gave the
 caller (dataset.py:133-135) - image decoding is outside the hot path and stays with the caller (no cv2 in this image).
 
+``gen_rays_at`` / ``rays_at_flat`` are the rays of a whole validation view with the interface of ``Dataset.gen_rays_at``
+(dataset.py:137-167), from the same device-resident K^-1 and poses (``emap_gen_rays_at``: one launch, 28 B written per ray).
+
 The host RNG streams (torch CPU generator, python ``random``) cannot be reproduced on a device: the draw is a
 Philox4x32-10 stream keyed by ``seed``; the deterministic part (rays of given pixels) and the sampling distribution are what
 the parity tests pin.
@@ -52,7 +55,7 @@ class DeviceRaySampler:
         self._density = flat.mean(1).float().to(dev)                 # edge_density = np.mean(img_np), :238
         self._kinv = self.intrinsics_all_inv[:, :3, :3].contiguous().to(dev)
         self._pose = P.contiguous().to(dev)
-        self._perm = None
+        self._perm, self._perm_host = None, None
         self._counter = torch.zeros(1, dtype=torch.int64, device=dev)   # device-resident step counter (uint64 bits)
         self._ds = _lib.RayDataset(self._edges.data_ptr(), self._order.data_ptr(), self._n_edge.data_ptr(), self._density.data_ptr(),
                                    self._kinv.data_ptr(), self._pose.data_ptr(), None, self.n_images, self.H, self.W, 0)
@@ -68,7 +71,9 @@ class DeviceRaySampler:
 
     def set_image_perm(self, perm):
         """The runner's ``image_perm`` (runner_udf.py:79-82): with it ``img_idx=None`` walks the permutation on the device."""
-        self._perm = torch.as_tensor(perm, dtype=torch.int32).contiguous().to(self.device)
+        perm = torch.as_tensor(perm, dtype=torch.int32).contiguous()
+        self._perm_host = perm.cpu().tolist()
+        self._perm = perm.to(self.device)
         self._ds.image_perm = self._perm.data_ptr()
 
     def gen_random_rays_patches_at(self, img_idx, batch_size, importance_sample=False, pixels=None):
@@ -108,3 +113,58 @@ class DeviceRaySampler:
             sample["pose"] = self.pose_all[int(img_idx)]
             sample["intrinsics"] = self.intrinsics_all[int(img_idx)]
         return sample
+
+    # ---- full-image rays: Dataset.gen_rays_at (dataset.py:137-167) ----
+
+    def view_size(self, resolution_level=1):
+        """-> (n, h, w): the (H // l) * (W // l) rays of a view at ``resolution_level`` l and its image size (host only)."""
+        n, h, w = C.c_int64(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().emap_gen_rays_count(C.byref(self._ds), int(resolution_level), C.byref(n), C.byref(h), C.byref(w)), "gen_rays_count")
+        return n.value, h.value, w.value
+
+    def _view_image(self, img_idx, via_perm):
+        """(the index the kernel takes, the image it resolves to).  ``via_perm``: ``img_idx`` is a position in the runner's image
+        permutation (``image_perm[img_idx % n_images]``, runner_udf.py:79-82), looked up on the device like the random sampler's."""
+        img_idx = int(img_idx)
+        if not via_perm:
+            if not 0 <= img_idx < self.n_images:
+                raise IndexError(f"DeviceRaySampler: image {img_idx} out of range ({self.n_images} images)")
+            return img_idx, img_idx
+        k = img_idx % self.n_images
+        return -1 - k, (k if self._perm_host is None else self._perm_host[k])
+
+    def rays_at_flat(self, img_idx, resolution_level=1, first=0, count=None, out=None, via_perm=False):
+        """Rays [first, first + count) of a view in row-major (H // l, W // l) order, ONE launch (``emap_gen_rays_at``):
+        -> rays_o (count, 3), rays_v (count, 3), depth_scale (count, 1), views of one buffer of 7 * count floats.  ``count=None``: up to the
+        end of the view.  ``out``: a contiguous float32 tensor on the sampler's device with at least 7 * count elements to write into (a
+        chunked caller reuses one)."""
+        dev = self.device
+        if dev.type != "cuda":
+            raise RuntimeError("emap_amd.DeviceRaySampler: the ray kernel needs an MI355X (cuda) device; there is no CPU fallback "
+                               "(the reference's own host routine is Dataset.gen_rays_at)")
+        n = self.view_size(resolution_level)[0]
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError(f"DeviceRaySampler: rays [{first}, {first + count}) leave the view's {n} rays")
+        if out is None:
+            out = torch.empty(7 * count, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.numel() < 7 * count:
+            raise ValueError(f"DeviceRaySampler: `out` must be a contiguous float32 tensor on {dev} with at least {7 * count} elements")
+        f = out.view(-1)
+        rays_o, rays_v, ds = f[:3 * count].view(count, 3), f[3 * count:6 * count].view(count, 3), f[6 * count:7 * count].view(count, 1)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().emap_gen_rays_at(C.byref(self._ds), self._view_image(img_idx, via_perm)[0], int(resolution_level),
+                                                   C.c_int64(first), C.c_int64(count), _lib.ptr(rays_o), _lib.ptr(rays_v), _lib.ptr(ds),
+                                                   _lib.stream_ptr(dev)), "gen_rays_at")
+        return rays_o, rays_v, ds
+
+    def gen_rays_at(self, img_idx, resolution_level=1, via_perm=False):
+        """-> the reference's 5-tuple (dataset.py:161-167), every tensor on the device: rays_o, rays_v (H // l, W // l, 3), pose,
+        intrinsics (4, 4) and depth_scale (W // l, H // l, 1).  The reference transposes rays_o and rays_v but NOT depth_scale, and
+        ``Runner_UDF.validate`` reshapes it as it is (runner_udf.py:300); that layout is kept: depth_scale is the transposed view of the
+        kernel's row-major (H // l, W // l, 1) output, so ``depth_scale.transpose(0, 1)`` is the scale of the ray at the same index."""
+        _, h, w = self.view_size(resolution_level)
+        rays_o, rays_v, ds = self.rays_at_flat(img_idx, resolution_level, via_perm=via_perm)
+        img = self._view_image(img_idx, via_perm)[1]
+        return rays_o.view(h, w, 3), rays_v.view(h, w, 3), self.pose_all[img], self.intrinsics_all[img], ds.view(h, w, 1).transpose(0, 1)

@@ -353,6 +353,23 @@ typedef struct EmapRayBatch {
 int emap_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
                      uint64_t* counter_dev, const int64_t* pixels_in, const EmapRayBatch* out, void* stream);
 
+/* ---- full-image rays: Dataset.gen_rays_at (src/dataset/dataset.py:137-167) -------------------------------------------------
+ * Added functions only (no struct or signature of ABI 12 changes).
+ * emap_gen_rays_count : n = (H // l) * (W // l) rays, h = H // l, w = W // l of a view at resolution_level l (any of the three may be
+ *                       NULL).  Host only: reads ds->H and ds->W, launches nothing.
+ * emap_gen_rays_at    : rays [first, first + count) of image img_idx in ROW-MAJOR (h, w) order - the order of the reference's
+ *                       transposed rays_o / rays_v (:162-163) - from ds->kinv / ds->pose on the device:
+ *                         x = torch.linspace(0, W-1, w)[i % w], y = torch.linspace(0, H-1, h)[i / w]   (fp32; non-integer when l > 1)
+ *                         p = K^-1 [x, y, 1];  v = p / |p|;  depth_scale = v_z;  rays_d = R v;  rays_o = t
+ *                       rays_o, rays_d (count, 3), depth_scale (count).  One launch, 28 B written per ray.
+ *                       img_idx < 0 goes through the image permutation as in emap_sample_rays, with the position given by the caller:
+ *                       entry k = (-1 - img_idx) % n_images, image_perm[k] (k itself when image_perm is NULL).
+ * Both fail with EMAP_E_INVALID (text in emap_last_error) before any launch: NULL dataset, resolution_level < 1, H // l == 0 or
+ * W // l == 0, img_idx >= n_images, negative first / count, first + count beyond the view, a NULL output with count > 0. */
+int emap_gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w);
+int emap_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
+                     float* depth_scale, void* stream);
+
 /* ---- scalar tail of a training step (SURVEY par. 8 a15; src/runner/runner_udf.py:124-168, src/models/loss.py:14-17,
  *      src/runner/runner_base.py:110-117) ---------------------------------------------------------------
  * emap_train_stats : the rank-local statistics of a step and dL/d(edge) of EdgeLoss("mse") * edge_weight:
