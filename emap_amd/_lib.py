@@ -131,6 +131,13 @@ SYMBOLS = {
     "emap_train_loss": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, _P, _P]),
     "emap_adam_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P]),
     "emap_adam_step_masked": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
+    "emap_train_schedule": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int64,
+                                      C.c_double, _P, _P]),
+    "emap_render_fwd_sched": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P,
+                                        _P, _P, _P, C.POINTER(CompositeOut), _P, C.c_size_t, _P, _P, _P]),
+    "emap_render_bwd_staged_sched": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
+                                               C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P, C.c_int, _P]),
+    "emap_adam_step_masked_sched": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
     "emap_ar_local_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
     "emap_ar_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p), _P]),
     "emap_ar_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),

@@ -363,10 +363,18 @@ int emap_render_workspace_bytes(const EmapNetConfig* cfg, int prec, const EmapRe
     return EMAP_OK;
 }
 
-int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p,
-                    const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
-                    const float* depth_scale, float* z_vals, float* udf, float* grad3, const EmapCompositeOut* out,
-                    void* workspace, size_t workspace_bytes, int32_t* err_flags, void* stream) {
+// a *_sched entry point was given its schedule pointer: the kernels then take cos_anneal_ratio from it, so the annealed cosine must be on
+static int check_sched(const EmapRenderParams* p, const float* sched, const char* who) {
+    if (!sched) { set_error("%s: sched_dev is null", who); return EMAP_E_INVALID; }
+    if (p->has_cos_anneal != 1) { set_error("%s: a device-fed cos_anneal_ratio needs has_cos_anneal = 1 (got %d)", who, p->has_cos_anneal); return EMAP_E_INVALID; }
+    return EMAP_OK;
+}
+
+// emap_render_fwd (sched == null) and emap_render_fwd_sched
+static int render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p,
+                      const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                      const float* depth_scale, float* z_vals, float* udf, float* grad3, const EmapCompositeOut* out,
+                      void* workspace, size_t workspace_bytes, int32_t* err_flags, void* stream, const float* sched) {
     NetLayout L;
     int rc = build_layout(cfg, prec, &L);
     if (rc) return rc;
@@ -460,7 +468,7 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     fin.rays_o = rays_o; fin.rays_d = rays_d; fin.z = z_vals; fin.n_per_ray = S; fin.mid = 1; fin.sample_dist = sample_dist;
     CompositeFuse cf;
     if (fuse_comp) {
-        rc = fill_composite_args(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, &cf.c);
+        rc = fill_composite_args(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, &cf.c, sched);
         if (rc) return rc;
         cf.ray_cnt = ray_cnt;
         cf.done_cnt = ray_cnt + N;   // the fused tail also runs the cross-ray reduction
@@ -472,7 +480,25 @@ int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
     if (rc) return rc;
     // 3 launches per render: value pass, importance_sample, value + grad_x + compositing + cross-ray reduction
     if (fuse_comp) return cf.c.out.scalars ? EMAP_OK : launch_composite_reduce(cf.c, err_flags, st);
-    return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, err_flags, st);
+    return launch_composite(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist, *p, out, partials, err_flags, st, sched);
+}
+
+int emap_render_fwd(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p,
+                    const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                    const float* depth_scale, float* z_vals, float* udf, float* grad3, const EmapCompositeOut* out,
+                    void* workspace, size_t workspace_bytes, int32_t* err_flags, void* stream) {
+    return render_fwd(cfg, packed, prec, p, rays_o, rays_d, near, far, t_rand, depth_scale, z_vals, udf, grad3, out, workspace, workspace_bytes,
+                      err_flags, stream, nullptr);
+}
+int emap_render_fwd_sched(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p,
+                          const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                          const float* depth_scale, float* z_vals, float* udf, float* grad3, const EmapCompositeOut* out,
+                          void* workspace, size_t workspace_bytes, int32_t* err_flags, void* stream, const float* sched_dev) {
+    if (!p) { set_error("render_fwd_sched: null pointer"); return EMAP_E_INVALID; }
+    const int rc = check_sched(p, sched_dev, "render_fwd_sched");
+    if (rc) return rc;
+    return render_fwd(cfg, packed, prec, p, rays_o, rays_d, near, far, t_rand, depth_scale, z_vals, udf, grad3, out, workspace, workspace_bytes,
+                      err_flags, stream, sched_dev);
 }
 
 int emap_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
@@ -573,10 +599,11 @@ int emap_render_bwd(const EmapNetConfig* cfg, const void* packed, int prec, cons
                                   workspace, workspace_bytes, err_flags, stream, 3);
 }
 
-int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p, const float* rays_o,
-                           const float* rays_d, const float* depth_scale, const float* z_vals, const float* udf, const float* grad3,
-                           const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
-                           size_t workspace_bytes, int32_t* err_flags, void* stream, int stages) {
+// emap_render_bwd_staged (sched == null) and emap_render_bwd_staged_sched
+static int render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p, const float* rays_o,
+                             const float* rays_d, const float* depth_scale, const float* z_vals, const float* udf, const float* grad3,
+                             const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
+                             size_t workspace_bytes, int32_t* err_flags, void* stream, int stages, const float* sched) {
     NetLayout L;
     RenderShape r;
     int rc = render_bwd_begin(cfg, prec, p, g && packed && rays_o && rays_d && z_vals && udf && grad3 && sample_dist_dev && workspace, "render_bwd", &L, &r);
@@ -598,7 +625,7 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
     if (stages & 1) {
         // render_core's tail in reverse; it also leaves max|d_udf|, max|d_grad| for the sweep's range scale
         rc = launch_composite_bwd(rays_o, rays_d, z_vals, udf, grad3, depth_scale, N, S, sample_dist_dev, p, g, d_udf, d_grad,
-                                  reinterpret_cast<float*>(ws + b.off_part), reinterpret_cast<uint32_t*>(vws + pl.off_absmax), st);
+                                  reinterpret_cast<float*>(ws + b.off_part), reinterpret_cast<uint32_t*>(vws + pl.off_absmax), st, sched);
         if (rc) return rc;
     }
     if (!(stages & 2)) return EMAP_OK;
@@ -606,6 +633,24 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
     memset(&fin, 0, sizeof(fin));
     fin.rays_o = rays_o; fin.rays_d = rays_d; fin.z = z_vals; fin.n_per_ray = S; fin.mid = 1; fin.sample_dist = sample_dist_dev;
     return run_vjp(L, packed, prec, fin, (int64_t)N * S, d_udf, d_grad, out, pl, vws, err_flags, st);
+}
+
+int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p, const float* rays_o,
+                           const float* rays_d, const float* depth_scale, const float* z_vals, const float* udf, const float* grad3,
+                           const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
+                           size_t workspace_bytes, int32_t* err_flags, void* stream, int stages) {
+    return render_bwd_staged(cfg, packed, prec, p, rays_o, rays_d, depth_scale, z_vals, udf, grad3, sample_dist_dev, g, out, workspace,
+                             workspace_bytes, err_flags, stream, stages, nullptr);
+}
+int emap_render_bwd_staged_sched(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p, const float* rays_o,
+                                 const float* rays_d, const float* depth_scale, const float* z_vals, const float* udf, const float* grad3,
+                                 const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
+                                 size_t workspace_bytes, int32_t* err_flags, void* stream, int stages, const float* sched_dev) {
+    if (!p) { set_error("render_bwd_staged_sched: null pointer"); return EMAP_E_INVALID; }
+    const int rc = check_sched(p, sched_dev, "render_bwd_staged_sched");
+    if (rc) return rc;
+    return render_bwd_staged(cfg, packed, prec, p, rays_o, rays_d, depth_scale, z_vals, udf, grad3, sample_dist_dev, g, out, workspace,
+                             workspace_bytes, err_flags, stream, stages, sched_dev);
 }
 
 int emap_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
@@ -636,6 +681,19 @@ int emap_adam_step_masked(float* params, const float* grads, float* exp_avg, flo
                           float lr_geo, float lr, double beta1, double beta2, float eps, const float* tail_mask, float* tail_step, void* stream) {
     return launch_adam(params, grads, exp_avg, exp_avg_sq, step_dev, n, n_geo, lr_geo, lr, beta1, beta2, eps, tail_mask, tail_step,
                        static_cast<hipStream_t>(stream));
+}
+int emap_adam_step_masked_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, int64_t n, int64_t n_geo,
+                                const float* lr_dev, double beta1, double beta2, float eps, const float* tail_mask, float* tail_step,
+                                void* stream) {
+    if (!lr_dev) { set_error("adam_step_masked_sched: lr_dev is null"); return EMAP_E_INVALID; }
+    return launch_adam(params, grads, exp_avg, exp_avg_sq, step_dev, n, n_geo, 0.f, 0.f, beta1, beta2, eps, tail_mask, tail_step,
+                       static_cast<hipStream_t>(stream), lr_dev);
+}
+int emap_train_schedule(int64_t* iter_dev, int64_t end_iter, double warm_up_end, double fix_geo_end, double anneal_end, double learning_rate,
+                        double learning_rate_geo, double learning_rate_alpha, int same_lr, int64_t flip_start, double flip_saturation_max,
+                        float* sched_dev, void* stream) {
+    return launch_train_schedule(iter_dev, end_iter, warm_up_end, fix_geo_end, anneal_end, learning_rate, learning_rate_geo, learning_rate_alpha,
+                                 same_lr, flip_start, flip_saturation_max, sched_dev, static_cast<hipStream_t>(stream));
 }
 
 int emap_null_direction(const float* grads, int64_t n, int k, float* dir, void* stream) {

@@ -35,6 +35,8 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int 
     const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
     const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
     const float sd = *a.sample_dist;
+    // cos_anneal_ratio / flip_saturation of this step: from the schedule kernel's device words where the caller fed them (uniform loads)
+    const float car = a.sched ? a.sched[2] : a.car, flip_sat = a.sched ? a.sched[3] : a.flip_sat;
     float inv_s_ = a.inv_s, beta_ = a.beta, gamma_ = a.gamma;
     if (a.var_p) {  // udf_model.py:226-227,259-263 + udf_renderer_blending.py:466-472
         inv_s_ = clipf(expf(FMUL(a.var_p[0], 10.0f)), 1e-6f, 1e6f);
@@ -70,15 +72,15 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int 
             const float raw_occ = udf2logistic1(u[i], beta_);                               // :492
             const float occ = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma_), dists[i])));   // :497
             const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);    // :500-509
-            av[i] = FADD(clipf(FADD(FSUB(1.0f, occ), FMUL(a.flip_sat, vis_mask)), 0.0f, 1.0f), 1e-7f);  // :515
+            av[i] = FADD(clipf(FADD(FSUB(1.0f, occ), FMUL(flip_sat, vis_mask)), 0.0f, 1.0f), 1e-7f);  // :515
         }
         ray_prefix_prod<C>(av, ok, sb);     // vis_prob (:511-523)
 #pragma unroll
         for (int i = 0; i < C; ++i) {
             const float vp = clipf(sb[i], 0.0f, 1.0f);                                      // :528
             const float tcn = -fabsf(tc[i]);
-            const float ap = sdf2alpha(u[i], tcn, dists[i], inv_s_, a.anneal != 0, a.car);  // :530-543
-            const float am = sdf2alpha(-u[i], tcn, dists[i], inv_s_, a.anneal != 0, a.car);
+            const float ap = sdf2alpha(u[i], tcn, dists[i], inv_s_, a.anneal != 0, car);  // :530-543
+            const float am = sdf2alpha(-u[i], tcn, dists[i], inv_s_, a.anneal != 0, car);
             alpha[i] = FADD(FMUL(ap, vp), FMUL(am, FSUB(1.0f, vp)));                        // :545
             av[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
         }

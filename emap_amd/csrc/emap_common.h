@@ -161,6 +161,8 @@ struct CompositeArgs {
     float beta_min;
     EmapCompositeOut out;
     float* partials;
+    // device-fed schedule (the *_sched entry points), or null: [2] replaces car and [3] flip_sat, read once per wave as uniform values
+    const float* sched;
 };
 
 // What the fused tail of udf_mlp_rev32_kernel needs beside the compositing arguments: one arrival counter per ray (points of the ray
@@ -322,14 +324,14 @@ int launch_coarse(const float* near, const float* far, const float* t_rand, int 
 // render_core's tail: the render scalars and the mode (render_mode) come from p; fill_composite_args checks the arguments and fills *a
 int fill_composite_args(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
                         int N, int S, const float* sample_dist, const EmapRenderParams& p, const EmapCompositeOut* out, float* partials,
-                        CompositeArgs* a);
+                        CompositeArgs* a, const float* sched = nullptr);
 int launch_composite(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
                      int N, int S, const float* sample_dist, const EmapRenderParams& p, const EmapCompositeOut* out, float* partials,
-                     int32_t* err, hipStream_t st);
+                     int32_t* err, hipStream_t st, const float* sched = nullptr);
 int launch_composite_reduce(const CompositeArgs& a, int32_t* err, hipStream_t st);
 int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3, const float* depth_scale,
                          int N, int S, const float* sample_dist, const EmapRenderParams* p, const EmapCompositeGrads* gr, float* d_udf,
-                         float* d_grad3, float* partials, uint32_t* absmax, hipStream_t st);
+                         float* d_grad3, float* partials, uint32_t* absmax, hipStream_t st, const float* sched = nullptr);
 int launch_embed(const float* x, int64_t P, int L, float* pe, hipStream_t st);
 void linspace_host(float start, float end, int steps, float* out);
 // rays.hip
@@ -342,8 +344,12 @@ int launch_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_lev
 int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
                        hipStream_t st);
 int launch_train_loss(const float* stats, float w_over_n, float igr, float igr_ns, float* out, hipStream_t st);
+// lr_dev: two device floats (geometry range, the rest) that replace lr_geo / lr, or null
 int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64_t n, int64_t n_geo, float lr_geo, float lr, double b1,
-                double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st);
+                double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st, const float* lr_dev = nullptr);
+int launch_train_schedule(int64_t* iter, int64_t end_iter, double warm_up_end, double fix_geo_end, double anneal_end, double learning_rate,
+                          double learning_rate_geo, double learning_rate_alpha, int same_lr, int64_t flip_start, double flip_saturation_max,
+                          float* sched, hipStream_t st);
 // wgrad.hip: the training backward's weight-gradient GEMMs
 WgradPlan plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget);
 int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hipStream_t st);

@@ -256,6 +256,7 @@ struct CompositeBwdArgs {
     float* raymax;                      // (N,2): the per-ray maxima behind them (null iff absmax is)
     float* zero_tail;                   // EmapCompositeGrads.zero_tail / n_zero_tail (cleared by the reduce kernel), or null
     long long n_zero_tail;
+    const float* sched;                 // CompositeArgs::sched
 };
 
 // lane l <- lane 63 - l
@@ -345,6 +346,7 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
     const float c_ge = a.d_ge ? a.d_ge[0] / (a.scalars[4] + 1e-5f) : 0.f;
     const float c_ns = a.d_ge_ns ? a.d_ge_ns[0] / (a.scalars[6] + 1e-5f) : 0.f;
     const bool anneal = a.anneal != 0;
+    const float car = a.sched ? a.sched[2] : a.car, flip_sat = a.sched ? a.sched[3] : a.flip_sat;      // composite_ray's
 
     // C >= 8 (S > 256): the per-sample pieces of the forward recomputation that the adjoint reuses (udf2logistic's, sdf2alpha_keep's, |g| + 1e-5)
     // do not all stay in registers next to the rest (C = 16 spilled to scratch): they are evaluated a second time where the adjoint needs them -
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
         if constexpr (MODE != EMAP_RENDER_PLAIN) {
             const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);
             const float occ = FSUB(1.0f, eq[k]);
-            ain[i] = FADD(FSUB(1.0f, occ), FMUL(a.flip_sat, vis_mask));
+            ain[i] = FADD(FSUB(1.0f, occ), FMUL(flip_sat, vis_mask));
             av[i] = FADD(clipf(ain[i], 0.0f, 1.0f), 1e-7f);
         }
     }
@@ -394,8 +396,8 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
         } else {
             vp[i] = clipf(vpr[i], 0.0f, 1.0f);
             const float tcn = -fabsf(tc[i]);
-            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, a.car, kp[KEEP ? i : 0]);
-            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, a.car, km[KEEP ? i : 0]);
+            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, car, kp[KEEP ? i : 0]);
+            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, car, km[KEEP ? i : 0]);
             alpha[i] = FADD(FMUL(ap[i], vp[i]), FMUL(am[i], FSUB(1.0f, vp[i])));
         }
         om[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
@@ -455,11 +457,11 @@ __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArg
             const float tabs = fabsf(tc[i]);
             float s1, t1, i1, s2, t2, i2;
             if constexpr (!KEEP) {
-                (void)sdf2alpha_keep(uk, -tabs, dists[i], inv_s_, anneal, a.car, kp[0]);
-                (void)sdf2alpha_keep(-uk, -tabs, dists[i], inv_s_, anneal, a.car, km[0]);
+                (void)sdf2alpha_keep(uk, -tabs, dists[i], inv_s_, anneal, car, kp[0]);
+                (void)sdf2alpha_keep(-uk, -tabs, dists[i], inv_s_, anneal, car, km[0]);
             }
-            sdf2alpha_bwd(kp[k], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * vp[i], s1, t1, i1);
-            sdf2alpha_bwd(km[k], tabs, dists[i], inv_s_, anneal, a.car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
+            sdf2alpha_bwd(kp[k], tabs, dists[i], inv_s_, anneal, car, dal[i] * vp[i], s1, t1, i1);
+            sdf2alpha_bwd(km[k], tabs, dists[i], inv_s_, anneal, car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
             du += s1 - s2;
             d_is = i1 + i2;
             dtc = (t1 + t2) * ((tc[i] > 0.f) ? 1.f : ((tc[i] < 0.f) ? -1.f : 0.f));
@@ -678,7 +680,7 @@ static void copy_render_scalars(const EmapRenderParams& p, A& a) {
 
 int fill_composite_args(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
                         const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
-                        const EmapCompositeOut* out, float* partials, CompositeArgs* pa) {
+                        const EmapCompositeOut* out, float* partials, CompositeArgs* pa, const float* sched) {
     if (S < 1 || S > MAXS_WIDE) { set_error("composite: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (!out || !partials) { set_error("composite: out/partials must not be null"); return EMAP_E_INVALID; }
     if (p.variance_dev && (!p.beta_dev || !p.gamma_dev)) { set_error("composite: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
@@ -686,7 +688,7 @@ int fill_composite_args(const float* rays_o, const float* rays_d, const float* z
     a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
     a.sample_dist = sample_dist; a.N = N; a.S = S;
     copy_render_scalars(p, a);
-    a.sparse_scale = p.sparse_scale; a.out = *out; a.partials = partials;
+    a.sparse_scale = p.sparse_scale; a.out = *out; a.partials = partials; a.sched = sched;
     return EMAP_OK;
 }
 
@@ -698,9 +700,9 @@ int launch_composite_reduce(const CompositeArgs& a, int32_t* err, hipStream_t st
 
 int launch_composite(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
                      const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
-                     const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st) {
+                     const EmapCompositeOut* out, float* partials, int32_t* err, hipStream_t st, const float* sched) {
     CompositeArgs a;
-    const int rc = fill_composite_args(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, p, out, partials, &a);
+    const int rc = fill_composite_args(rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, p, out, partials, &a, sched);
     if (rc) return rc;
     if (N <= 0) return EMAP_OK;
     with_render_mode(p.render_mode, [&](auto mode) {
@@ -713,7 +715,7 @@ int launch_composite(const float* rays_o, const float* rays_d, const float* z, c
 int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
                          const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams* p,
                          const EmapCompositeGrads* gr, float* d_udf, float* d_grad3, float* partials, uint32_t* absmax,
-                         hipStream_t st) {
+                         hipStream_t st, const float* sched) {
     if (S < 1 || S > MAXS_WIDE) { set_error("composite_bwd: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
     if (N <= 0) return EMAP_OK;
     if (p->variance_dev && (!p->beta_dev || !p->gamma_dev)) { set_error("composite_bwd: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
@@ -723,7 +725,7 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
     copy_render_scalars(*p, a);
     a.d_edge = gr->d_edge; a.d_depth = gr->d_depth; a.d_ge = gr->d_gradient_error; a.d_ge_ns = gr->d_gradient_error_near_surface;
     a.scalars = gr->scalars; a.d_udf = d_udf; a.d_grad = d_grad3; a.partials = partials; a.absmax = absmax;
-    a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail;
+    a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail; a.sched = sched;
     a.raymax = absmax ? partials + (size_t)N * 4 : nullptr;     // internal callers (emap_render_bwd) size `partials` as (N,4) + (N,2)
     if ((a.d_ge || a.d_ge_ns) && !a.scalars) { set_error("composite_bwd: the eikonal gradients need the forward's scalars"); return EMAP_E_INVALID; }
     with_render_mode(p->render_mode, [&](auto mode) {

@@ -7,7 +7,10 @@
 //                        the (global) statistics
 //   adam_kernel        : torch.optim.Adam with the reference's two parameter groups (runner_base.py:110-117) on the flat
 //                        parameter / gradient buffers; the step counter is a device word (graph-capturable)
+//   train_schedule_kernel : the four numbers the runner changes every iteration (runner_base.py:128-180) from a device iteration counter,
+//                        so that a captured step follows the schedules: the *_sched entry points read them from device memory
 #include "emap_common.h"
+#include <type_traits>
 
 namespace emap {
 
@@ -44,9 +47,17 @@ __global__ void train_loss_kernel(const float* stats, float w_over_n, float igr,
 // without gradient and starts its `step` state when the parameter first gets one (runner_udf.py:144-154 un-freezes variance / beta late)
 // b1, b2 arrive as DOUBLES and 1 - b, b^t are formed in double like torch does (python floats / the fused kernel's double arguments):
 // 1.0f - 0.999f is 4.7e-5 off 0.001, which scaled exp_avg_sq by that factor against a torch.optim.Adam checkpoint (round 5).
+// LR: where the two learning rates come from - LrByValue (emap_adam_step[_masked]) or LrOnDevice (emap_adam_step_masked_sched: two device
+// floats, uniform loads).  The by-value instantiation is the kernel as it always was, argument for argument.
+struct LrByValue { float lr_geo, lr; };
+struct LrOnDevice { const float* lr_dev; };
+template <class LR>
 __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, float* m, float* v, float* step, long long n, long long n_geo,
-                                                   float lr_geo, float lr, double b1d, double b2d, float eps, const float* tail_mask,
+                                                   const LR lrs, double b1d, double b2d, float eps, const float* tail_mask,
                                                    float* tail_step) {
+    float lr_geo, lr;
+    if constexpr (std::is_same_v<LR, LrOnDevice>) { lr_geo = lrs.lr_dev[0]; lr = lrs.lr_dev[1]; }
+    else { lr_geo = lrs.lr_geo; lr = lrs.lr; }
     const float t = *step + 1.0f;
     const float b2 = (float)b2d, omb1 = (float)(1.0 - b1d), omb2 = (float)(1.0 - b2d);
     __shared__ float s_bc[2];      // the two double-precision powers once per workgroup, not once per thread (9 -> 12 us otherwise)
@@ -89,6 +100,45 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
 }
 __global__ void adam_bump_kernel(float* step) { *step += 1.0f; }
 
+// runner_base.py:128-180 at iter_step = *iter, in doubles and in the reference's order of operations (python floats / numpy doubles there);
+// every product and sum below is rounded on its own (no fused multiply-add), the four results are rounded to fp32 once, on the store.
+//   factor(it)     :128-141  warm-up it / warm_up_end, then the cosine decay to alpha over [warm_up_end, end_iter]
+//   factor_geo(it) :143-160  0 below fix_geo_end, warm-up it / (2 warm_up_end), 1 up to end_iter / 2, then the cosine decay
+// One thread; then the counter moves on (runner_udf.py:170).
+__global__ void train_schedule_kernel(long long* iter, long long end_iter, double warm_up_end, double fix_geo_end, double anneal_end,
+                                      double learning_rate, double learning_rate_geo, double alpha, int same_lr, long long flip_start,
+                                      double flip_max, float* sched) {
+#pragma clang fp contract(off)
+    const long long it_i = *iter;
+    const double it = (double)it_i, end = (double)end_iter, half = end * 0.5;
+    double f;
+    if (it < warm_up_end) {
+        f = it / warm_up_end;
+    } else {
+        const double progress = (it - warm_up_end) / (end - warm_up_end);
+        f = (cos(M_PI * progress) + 1.0) * 0.5 * (1.0 - alpha) + alpha;
+    }
+    double fg;
+    if (it < fix_geo_end) {
+        fg = 0.0;
+    } else if (it < warm_up_end * 2.0) {
+        fg = it / (warm_up_end * 2.0);
+    } else if (it < half) {
+        fg = 1.0;
+    } else {
+        const double progress = (it - half) / (end - half);
+        fg = (cos(M_PI * progress) + 1.0) * 0.5 * (1.0 - alpha) + alpha;
+    }
+    const double lr = learning_rate * f;
+    const double car = anneal_end == 0.0 ? 1.0 : fmin(1.0, it / anneal_end);                          // :162-166
+    const double flip = it_i < flip_start ? 0.0 : (it < half ? flip_max : 1.0);                        // :171-180
+    sched[0] = (float)(same_lr ? lr : learning_rate_geo * fg);                                         // runner_udf.py:64-68
+    sched[1] = (float)lr;
+    sched[2] = (float)car;
+    sched[3] = (float)flip;
+    *iter = it_i + 1;
+}
+
 int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
                        hipStream_t st) {
     if (!edge || !true_edge || !scalars || !stats || N < 0) { set_error("train_stats: null pointer"); return EMAP_E_INVALID; }
@@ -101,7 +151,7 @@ int launch_train_loss(const float* stats, float w_over_n, float igr, float igr_n
     return check_launch("train_loss");
 }
 int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64_t n, int64_t n_geo, float lr_geo, float lr, double b1,
-                double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st) {
+                double b2, float eps, const float* tail_mask, float* tail_step, hipStream_t st, const float* lr_dev) {
     if (!p || !g || !m || !v || !step || n < 0 || n_geo < 0 || n_geo > n || ((tail_mask == nullptr) != (tail_step == nullptr))) {
         set_error("adam_step: bad arguments");
         return EMAP_E_INVALID;
@@ -109,9 +159,29 @@ int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64
     if (n == 0) return EMAP_OK;
     const int64_t work = n_geo / 4 + (n - (n_geo & ~(int64_t)3));      // float4 words of the geometry range + the remaining elements
     const int grid = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, lr_geo, lr, b1, b2, eps, tail_mask, tail_step);
+    if (lr_dev) hipLaunchKernelGGL(adam_kernel<LrOnDevice>, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, LrOnDevice{lr_dev}, b1, b2, eps, tail_mask, tail_step);
+    else hipLaunchKernelGGL(adam_kernel<LrByValue>, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, LrByValue{lr_geo, lr}, b1, b2, eps, tail_mask, tail_step);
     hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, step);
     return check_launch("adam_step");
+}
+
+int launch_train_schedule(int64_t* iter, int64_t end_iter, double warm_up_end, double fix_geo_end, double anneal_end, double learning_rate,
+                          double learning_rate_geo, double learning_rate_alpha, int same_lr, int64_t flip_start, double flip_saturation_max,
+                          float* sched, hipStream_t st) {
+    if (!iter || !sched) { set_error("train_schedule: null pointer"); return EMAP_E_INVALID; }
+    if (end_iter <= 0) { set_error("train_schedule: end_iter must be > 0 (got %lld)", (long long)end_iter); return EMAP_E_INVALID; }
+    if (!(warm_up_end >= 0.0) || !(fix_geo_end >= 0.0) || !(anneal_end >= 0.0)) {
+        set_error("train_schedule: warm_up_end, fix_geo_end and anneal_end must be >= 0 (got %g, %g, %g)", warm_up_end, fix_geo_end, anneal_end);
+        return EMAP_E_INVALID;
+    }
+    if (!((double)end_iter > warm_up_end)) {      // runner_base.py:133-135 would divide by zero
+        set_error("train_schedule: end_iter (%lld) must be > warm_up_end (%g)", (long long)end_iter, warm_up_end);
+        return EMAP_E_INVALID;
+    }
+    hipLaunchKernelGGL(train_schedule_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<long long*>(iter), (long long)end_iter, warm_up_end,
+                       fix_geo_end, anneal_end, learning_rate, learning_rate_geo, learning_rate_alpha, same_lr, (long long)flip_start,
+                       flip_saturation_max, sched);
+    return check_launch("train_schedule");
 }
 
 }  // namespace emap

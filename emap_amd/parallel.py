@@ -23,6 +23,12 @@ the global mask sums for the step to equal the single-GPU step.  ``eikonal_sync=
 stats before the backward (20 bytes, the only other collective of the step); ``eikonal_sync="local"`` uses the rank's own
 denominators (a mean of per-rank means - exact whenever the masks cover every sample, as they do for scenes inside the unit
 sphere) and the step has exactly one collective.
+
+``Trainer(..., schedule=TrainSchedule(...))`` also keeps the four numbers the runner changes every iteration (runner_base.py:128-180:
+the two learning rates, cos_anneal_ratio, flip_saturation) on the device: every step first enqueues ``emap_train_schedule``, which
+evaluates them from a device iteration counter, and the render, the backward and Adam read them from device memory.  A captured step
+then follows the schedules, and with ``capture(sampler=...)`` the ray draw is in the graph too: one replay is one whole iteration of
+runner_udf.py:63-170 with no per-step host work.
 """
 from __future__ import annotations
 
@@ -192,13 +198,21 @@ class _FlatAdam:
         self.flags = flags
         return True
 
-    def step(self, data, grad, lr_geo, lr_tail, betas, eps, geo_grad_ptr: Optional[int] = None):
+    def step(self, data, grad, lr_geo, lr_tail, betas, eps, geo_grad_ptr: Optional[int] = None, lr_dev: Optional[torch.Tensor] = None):
         """One Adam step of `data` (n floats).  `grad` holds all n gradients - one launch - or, with `geo_grad_ptr` (the address of the
         n_geo geometry gradients in a buffer of the caller), those of the tail alone: two launches on disjoint ranges with the same
-        arithmetic, the geometry range first (it bumps `t`), then the tail with its own step counts."""
+        arithmetic, the geometry range first (it bumps `t`), then the tail with its own step counts.  `lr_dev` (two device floats:
+        geometry, tail; one launch only): the learning rates are read on the device and `lr_geo` / `lr_tail` are not used."""
         L, dev = _lib.lib(), data.device
-        hyper = (float(lr_geo), float(lr_tail), float(betas[0]), float(betas[1]), float(eps))
         tail = (_lib.ptr(self.tail_mask), _lib.ptr(self.tail_step), _lib.stream_ptr(dev))
+        if lr_dev is not None:
+            assert geo_grad_ptr is None
+            with torch.cuda.device(dev):
+                _lib.check(L.emap_adam_step_masked_sched(_lib.ptr(data), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
+                                                         self.n, self.n_geo, _lib.ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps),
+                                                         *tail), "adam_step_sched")
+            return
+        hyper = (float(lr_geo), float(lr_tail), float(betas[0]), float(betas[1]), float(eps))
         with torch.cuda.device(dev):
             if geo_grad_ptr is None:
                 _lib.check(L.emap_adam_step_masked(_lib.ptr(data), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
@@ -266,7 +280,8 @@ class _AdamGroups:
 
     def step(self):
         t, (g0, g1) = self._t, self.param_groups
-        t._adam.step(t.flat.data, t.flat.grad, g0["lr"], g1["lr"], g0["betas"], g0["eps"])
+        # with a schedule the two learning rates are the device words of emap_train_schedule: param_groups[*]["lr"] are not read
+        t._adam.step(t.flat.data, t.flat.grad, g0["lr"], g1["lr"], g0["betas"], g0["eps"], lr_dev=t._sched)
 
 
 class Trainer:
@@ -277,7 +292,10 @@ class Trainer:
 
     def __init__(self, renderer, lr_geo: float = 1e-4, lr: float = 5e-4, edge_weight: float = 1.0, igr_weight: float = 0.1,
                  igr_ns_weight: float = 0.0, group=None, eikonal_sync: str = "exact", fused_adam: Optional[bool] = None,
-                 native_tail: Optional[bool] = None, allreduce: str = "rccl"):
+                 native_tail: Optional[bool] = None, allreduce: str = "rccl", schedule=None, start_iter: int = 0):
+        """schedule (emap_amd.TrainSchedule; None: nothing changes): the step evaluates the reference's per-iteration schedules on the
+        device from its own iteration counter, which starts at `start_iter` (see iter_step / set_iter_step).  Then
+        ``optimizer.param_groups[*]["lr"]`` are not read, and ``rays`` must not carry cos_anneal_ratio / flip_saturation."""
         assert eikonal_sync in ("exact", "exact_lagged", "local")
         # only "exact_lagged" uses the rank-indexed maxima slots of the bucket's tail: "exact" / "local" run on any number of ranks
         assert eikonal_sync != "exact_lagged" or _world(group) <= self.MAX_RANKS, \
@@ -340,12 +358,63 @@ class Trainer:
         self._oneshot = None
         if allreduce == "oneshot" and _world(group) > 1:
             self._oneshot = OneShotAllReduce(self.flat.grad.numel(), dev, group)
+        # the reference's per-step schedules on the device: the iteration counter (every rank keeps its own, identical one) and the four
+        # numbers emap_train_schedule writes at the top of every step [lr_geo, lr, cos_anneal_ratio, flip_saturation]
+        self.schedule = schedule
+        self._iter = self._sched = None
+        if schedule is not None:
+            if int(start_iter) < 0:
+                raise ValueError(f"Trainer: start_iter must be >= 0 (got {start_iter})")
+            self._iter = torch.full((1,), int(start_iter), dtype=torch.int64, device=dev)
+            self._sched = torch.zeros(4, device=dev)
+
+    # ---- the scheduled step (schedule=TrainSchedule(...)) ----
+    @property
+    def iter_step(self) -> int:
+        """The iteration the NEXT step runs at - the reference's iter_step (runner_udf.py:170).  Reads the device counter: synchronises."""
+        if self._iter is None:
+            raise RuntimeError("Trainer.iter_step: this trainer has no schedule")
+        return int(self._iter.item())
+
+    def set_iter_step(self, k: int):
+        """Write the device iteration counter (resuming from a checkpoint's iter_step).  A captured graph reads the buffer, so a write
+        between replays takes effect without re-capturing."""
+        if self._iter is None:
+            raise RuntimeError("Trainer.set_iter_step: this trainer has no schedule")
+        if int(k) < 0:
+            raise ValueError(f"Trainer.set_iter_step: the iteration must be >= 0 (got {k})")
+        self._iter.fill_(int(k))
+
+    def _check_scheduled(self, rays):
+        """The scheduled step has ONE source for the two render scalars - the device schedule - and runs on the native tail only."""
+        for k in ("cos_anneal_ratio", "flip_saturation"):
+            if k in rays:
+                raise ValueError(f"Trainer: rays['{k}'] given to a trainer with a schedule - the schedule on the device is the only source "
+                                 "of cos_anneal_ratio / flip_saturation")
+        if not self.native_tail:
+            raise RuntimeError("Trainer: schedule= needs the native tail (emap_train_schedule and the *_sched entry points are HIP kernels; "
+                               "there is no CPU fallback)")
+
+    @staticmethod
+    def sampler_batch(sampler, batch_size: int, importance_sample: bool = False):
+        """-> (rays, true_edge) of one training batch from a DeviceRaySampler, image ``image_perm[counter % n_images]``: what
+        runner_udf.py:70-90 hands to render(), with the jitter draw of the same launch as rays['t_rand']."""
+        if sampler.near is None or sampler.far is None:
+            raise ValueError("Trainer.sampler_batch: the sampler has no near / far (DeviceRaySampler(..., near=, far=) or from_meta)")
+        smp = sampler.gen_random_rays_patches_at(-1, batch_size, importance_sample)
+        rays = {"rays_o": smp["rays"]["rays_o"], "rays_d": smp["rays"]["rays_v"], "near": float(sampler.near), "far": float(sampler.far),
+                "depth_scale": smp["depth_scale"], "t_rand": smp["t_rand"]}
+        return rays, smp["rays"]["edge"]
 
     # ---- the two HIP stages; the CPU tests substitute oracle implementations for them ----
     def _forward(self, rays):
         r = self.r
-        call = r._prepare(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], rays.get("depth_scale"), rays.get("cos_anneal_ratio"),
-                          rays.get("perturb_overwrite", -1), rays.get("background_rgb"), rays.get("flip_saturation", 0.0), rays.get("t_rand"))
+        car, fs = rays.get("cos_anneal_ratio"), rays.get("flip_saturation", 0.0)
+        if self._sched is not None:
+            car, fs = 1.0, 0.0        # place holders (the annealed cosine is on): the kernels read both from self._sched
+        call = r._prepare(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], rays.get("depth_scale"), car,
+                          rays.get("perturb_overwrite", -1), rays.get("background_rgb"), fs, rays.get("t_rand"))
+        call["sched"] = self._sched   # the backward of this call reads it from here as well
         v = r._render_hip(call)
         return call, v, v["edge"], v["scalars"]
 
@@ -399,13 +468,21 @@ class Trainer:
     # The native step is written as four device phases separated by the (at most three) collectives, so that it can run eagerly, be
     # captured whole in one hipGraph (one rank) or be captured phase by phase with the collectives launched between the replays
     # (any backend, also gloo whose collectives are host code): capture(segmented=True).
-    def _phases(self, rays, true_edge, n_rays_global):
-        """-> (the step's record, its four phases): what _run_phases runs, or capture() records one by one."""
+    def _phases(self, rays, true_edge, n_rays_global, batch=None):
+        """-> (the step's record, its four phases): what _run_phases runs, or capture() records one by one.  `batch` (a callable ->
+        (rays, true_edge), in place of the two): the first phase draws its own batch (capture(sampler=...))."""
         S = _Step()
-        return S, [lambda: self._ph_forward(S, rays, true_edge, n_rays_global), lambda: self._ph_composite_bwd(S),
+        return S, [lambda: self._ph_forward(S, rays, true_edge, n_rays_global, batch), lambda: self._ph_composite_bwd(S),
                    lambda: self._ph_mlp_bwd(S), lambda: self._ph_update(S)]
 
-    def _ph_forward(self, S, rays, true_edge, n_rays_global):
+    def _ph_forward(self, S, rays, true_edge, n_rays_global, batch=None):
+        if self._sched is not None:      # this iteration's four scheduled numbers, then the counter moves on
+            dev = self._sched.device
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().emap_train_schedule(_lib.ptr(self._iter), *self.schedule.c_args(), _lib.ptr(self._sched),
+                                                          _lib.stream_ptr(dev)), "train_schedule")
+        if batch is not None:
+            rays, true_edge = batch()
         S.call, S.v, edge, S.scalars = self._forward(rays)
         dev = edge.device
         n_local = edge.numel()
@@ -492,14 +569,16 @@ class Trainer:
             return [stats, (2, grad)]
         return [stats, (1, ar(lambda S: self.r.bwd_absmax(S.call), dist.ReduceOp.MAX)), (2, grad)]
 
-    def _step_native(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int]):
+    def _step_native(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int], batch=None):
         coll = self._collectives()
-        S, phases = self._phases(rays, true_edge, n_rays_global)
+        S, phases = self._phases(rays, true_edge, n_rays_global, batch)
         return _run_phases(phases, coll, S)
 
     def step(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int] = None):
         """One optimizer step on this rank's rays.  Returns the device tensor [loss, edge_loss] of the GLOBAL batch (no host
         synchronisation happens here)."""
+        if self._sched is not None:
+            self._check_scheduled(rays)
         if self.native_tail:
             self.refresh_trainable_mask()
             return self._step_native(rays, true_edge, n_rays_global)
@@ -541,8 +620,19 @@ class Trainer:
         self.last_stats = torch.stack(_loss_from_stats(stats, n_glob, self.edge_weight, self.igr_weight, self.igr_ns_weight))
         return self.last_stats
 
-    def capture(self, rays: Dict, true_edge: torch.Tensor, n_rays_global: Optional[int] = None, warmup: int = 3,
-                segmented: Optional[bool] = None):
+    def _train_state(self):
+        """Every device buffer a step changes besides its outputs (capture() with a schedule rolls its warm-up steps back)."""
+        a = self._adam
+        return [self.flat.data, a.m, a.v, a.t, a.spare_t, a.tail_step, self._lag, self._iter]
+
+    def _sampled_step(self, batch, n_rays_global=None):
+        """step() on a batch the first phase draws itself (`batch`: -> (rays, true_edge)), after the schedule launch"""
+        self.refresh_trainable_mask()
+        return self._step_native(None, None, n_rays_global, batch)
+
+    def capture(self, rays: Optional[Dict] = None, true_edge: Optional[torch.Tensor] = None, n_rays_global: Optional[int] = None,
+                warmup: int = 3, segmented: Optional[bool] = None, sampler=None, batch_size: Optional[int] = None,
+                importance_sample: bool = False):
         """Capture one whole step (pack -> render forward -> statistics -> HIP backward -> [all-reduce] -> Adam) for this batch
         shape and return ``replay(rays=None, true_edge=None) -> [loss, edge_loss]`` (device tensor, static).  New rays / targets
         are copied into the static buffers before the replay.  `warmup` real steps are taken first (workspaces, function
@@ -550,7 +640,30 @@ class Trainer:
 
         One rank: ONE hipGraph.  Several ranks (`segmented`, default then): one hipGraph per device phase and the collectives
         launched between the replays - nothing about the transport is assumed (works with RCCL and with gloo, whose collectives
-        are host code and cannot be captured); `segmented=False` puts the collectives inside one graph (RCCL only)."""
+        are host code and cannot be captured); `segmented=False` puts the collectives inside one graph (RCCL only).
+
+        With a schedule the captured step begins with emap_train_schedule and follows the schedules from the device iteration counter.
+        The warm-up steps (and the step a segmented capture takes) are then ROLLED BACK: parameters, Adam state and the counters are
+        what they were before the call, so the first replay is iteration iter_step, exactly as the first eager step() would have been.
+
+        `sampler` (a DeviceRaySampler with near / far; `batch_size` rays, `importance_sample` as runner_udf.py:71-75) in place of
+        `rays` / `true_edge`, with a schedule: the sampler's launch - pixel draw, rays, true_edge, t_rand, image
+        image_perm[counter % n_images] - is the graph's second node, and ``replay()`` takes no arguments: one replay is one complete
+        reference iteration.  The captured region is one linear chain on one stream."""
+        batch = None
+        if sampler is not None:
+            if rays is not None or true_edge is not None:
+                raise ValueError("Trainer.capture: pass either rays / true_edge or sampler=, not both")
+            if self._sched is None:
+                raise ValueError("Trainer.capture(sampler=...) needs a trainer with a schedule (cos_anneal_ratio / flip_saturation must come "
+                                 "from the device too)")
+            if batch_size is None or int(batch_size) <= 0:
+                raise ValueError("Trainer.capture(sampler=...): batch_size must be given")
+            batch = lambda: self.sampler_batch(sampler, int(batch_size), importance_sample)
+        elif rays is None or true_edge is None:
+            raise ValueError("Trainer.capture: rays and true_edge (or sampler=) must be given")
+        if self._sched is not None:
+            self._check_scheduled(rays or {})
         if not self.native_tail:
             if segmented:
                 raise ValueError("Trainer.capture(segmented=True) needs the native tail (native_tail=True): the per-phase graphs are the "
@@ -558,17 +671,24 @@ class Trainer:
             segmented = False
         if segmented is None:
             segmented = _world(self.group) > 1
-        if rays.get("t_rand") is None and (rays.get("perturb_overwrite", -1) != 0) and self.r.perturb > 0:
+        if batch is None and rays.get("t_rand") is None and (rays.get("perturb_overwrite", -1) != 0) and self.r.perturb > 0:
             raise ValueError("Trainer.capture: pass rays['t_rand'] explicitly (the reference's CPU-generator jitter draw plus its "
                              "host-to-device copy cannot be part of a device graph)")
         dev = self.flat.data.device
-        static = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in rays.items()}
-        te = true_edge.detach().clone()
+        static = te = None
+        if batch is None:
+            static = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else v) for k, v in rays.items()}
+            te = true_edge.detach().clone()
+        one_step = (lambda: self.step(static, te, n_rays_global)) if batch is None else (lambda: self._sampled_step(batch, n_rays_global))
+        saved = None
+        if self._sched is not None:      # the warm-up is rolled back (see above)
+            saved = [(t, t.clone()) for t in self._train_state() + ([sampler._counter] if sampler is not None else [])]
+            lag_valid = self._lag_valid
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(warmup, 1)):
-                self.step(static, te, n_rays_global)
+                one_step()
         torch.cuda.current_stream(dev).wait_stream(side)
         graphs, outs = [], []
 
@@ -580,18 +700,27 @@ class Trainer:
             return g
 
         if not segmented:
-            captured(lambda: self.step(static, te, n_rays_global))
+            captured(one_step)
             coll, S = [], None
         else:
             # capture does not execute: every phase is replayed as soon as it is captured and its collectives run, so that this pass is
             # one real step and the next phase is captured on real data
             coll = self._collectives()
-            S, phases = self._phases(static, te, n_rays_global)
+            S, phases = self._phases(static, te, n_rays_global, batch)
             _run_phases([lambda ph=ph: captured(ph).replay() for ph in phases], coll, S)
         out = outs[-1]
         keep = self.r.live_buffers()
+        if saved is not None:
+            for t, was in saved:
+                t.copy_(was)
+            self._lag_valid = lag_valid
+            self.r.udf_network.invalidate_packed()
 
         def replay(rays: Optional[Dict] = None, true_edge: Optional[torch.Tensor] = None):
+            if batch is not None and (rays is not None or true_edge is not None):
+                raise ValueError("replay: this graph draws its own batch (capture(sampler=...)); it takes no arguments")
+            if rays is not None and self._sched is not None:
+                self._check_scheduled(rays)
             if self.native_tail:
                 self.refresh_trainable_mask()     # a set_trainable() between replays reaches the captured Adam through its mask buffer
             if rays is not None:

@@ -279,10 +279,15 @@ class UDFRendererBlending:
             for k in names:
                 setattr(co, k, v[k].data_ptr())
             packed = net.packed(call["prec_name"])
-            _lib.check(L.emap_render_fwd(C.byref(cfg), _lib.ptr(packed), prec, C.byref(p), _lib.ptr(call["ro"]), _lib.ptr(call["rd"]),
-                                         _lib.ptr(call["near"]), _lib.ptr(call["far"]), _lib.ptr(call["t_rand"]), _lib.ptr(call["ds"]),
-                                         _lib.ptr(v["z_vals"]), _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), C.byref(co), _lib.ptr(ws),
-                                         ws.numel(), _lib.ptr(self._err), _lib.stream_ptr(dev)), "render_fwd")
+            args = (C.byref(cfg), _lib.ptr(packed), prec, C.byref(p), _lib.ptr(call["ro"]), _lib.ptr(call["rd"]),
+                    _lib.ptr(call["near"]), _lib.ptr(call["far"]), _lib.ptr(call["t_rand"]), _lib.ptr(call["ds"]),
+                    _lib.ptr(v["z_vals"]), _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), C.byref(co), _lib.ptr(ws),
+                    ws.numel(), _lib.ptr(self._err), _lib.stream_ptr(dev))
+            # call["sched"]: the device words of emap_train_schedule - cos_anneal_ratio / flip_saturation are read from them, not from p
+            if call.get("sched") is None:
+                _lib.check(L.emap_render_fwd(*args), "render_fwd")
+            else:
+                _lib.check(L.emap_render_fwd_sched(*args, _lib.ptr(call["sched"])), "render_fwd_sched")
         v["_ws"] = ws
         return v
 
@@ -334,12 +339,15 @@ class UDFRendererBlending:
                 nbv = self._bws_bytes[nbk] = nb.value
             lim = net.backward_workspace_limit
             ws = _workspace(self._bws, (N, S, prec), nbv if lim is None else min(nbv, int(lim)), dev)
-            _lib.check(L.emap_render_bwd_staged(C.byref(cfg), _lib.ptr(packed), prec, C.byref(p),
-                                                _lib.ptr(call["ro"]), _lib.ptr(call["rd"]), _lib.ptr(call["ds"]), _lib.ptr(v["z_vals"]),
-                                                _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), _lib.ptr(v.get("_sd", v["_ws"])), C.byref(cg), C.byref(pg),
-                                                _lib.ptr(ws), ws.numel() if lim is None else min(ws.numel(), int(lim)), _lib.ptr(self._err),
-                                                _lib.stream_ptr(dev), int(stages)),
-                       "render_bwd")
+            args = (C.byref(cfg), _lib.ptr(packed), prec, C.byref(p),
+                    _lib.ptr(call["ro"]), _lib.ptr(call["rd"]), _lib.ptr(call["ds"]), _lib.ptr(v["z_vals"]),
+                    _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), _lib.ptr(v.get("_sd", v["_ws"])), C.byref(cg), C.byref(pg),
+                    _lib.ptr(ws), ws.numel() if lim is None else min(ws.numel(), int(lim)), _lib.ptr(self._err),
+                    _lib.stream_ptr(dev), int(stages))
+            if call.get("sched") is None:
+                _lib.check(L.emap_render_bwd_staged(*args), "render_bwd")
+            else:      # the forward's device-fed scalars (_render_hip)
+                _lib.check(L.emap_render_bwd_staged_sched(*args, _lib.ptr(call["sched"])), "render_bwd_sched")
         return flat
 
     def bwd_absmax(self, call):

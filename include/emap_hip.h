@@ -397,6 +397,43 @@ int emap_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 int emap_adam_step_masked(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, int64_t n, int64_t n_geo,
                           float lr_geo, float lr, double beta1, double beta2, float eps, const float* tail_mask, float* tail_step, void* stream);
 
+/* ---- per-step schedules on the device (src/runner/runner_base.py:128-180, src/runner/runner_udf.py:64-68,102,107) ----------------
+ * Added functions only (no struct or signature of ABI 12 changes).
+ * The runner changes four numbers every iteration - the learning rates of its two Adam groups, cos_anneal_ratio and flip_saturation.
+ * Passed by value they are baked into a captured graph's kernel arguments; these calls keep them in device memory instead.
+ * emap_train_schedule : one launch of one thread.  Reads it = *iter_dev (int64: the reference's iter_step at the top of the loop body),
+ *                       writes sched_dev (>= 4 floats) and stores it + 1 to *iter_dev:
+ *                         [0] lr of the geometry group: learning_rate_geo * factor_geo(it) (update_learning_rate_geo, :143-160); with
+ *                             same_lr != 0 it is [1] and the geometry schedule is not applied (runner_udf.py:64-65)
+ *                         [1] lr of the other groups: learning_rate * factor(it) (update_learning_rate, :128-141)
+ *                         [2] cos_anneal_ratio: 1 when anneal_end == 0, else min(1, it / anneal_end) (:162-166)
+ *                         [3] flip_saturation: 0 below flip_start (10000 in the reference), flip_saturation_max (0.9) below
+ *                             end_iter * 0.5, else 1 (:171-180)
+ *                       Every expression is evaluated in double, in the reference's order of operations (python floats and numpy doubles
+ *                       there), and rounded to fp32 once, on the store.  EMAP_E_INVALID before any launch: a NULL pointer, end_iter <= 0,
+ *                       end_iter <= warm_up_end (the reference would divide by zero), a negative warm_up_end / fix_geo_end / anneal_end.
+ * emap_render_fwd_sched, emap_render_bwd_staged_sched : emap_render_fwd / emap_render_bwd_staged whose compositing kernels (the separate
+ *                       launch and the fused tail of the value + grad_x kernel; the compositing adjoint) use sched_dev[2] / sched_dev[3]
+ *                       in place of p->cos_anneal_ratio / p->flip_saturation - one uniform load per wave, nothing per sample.
+ *                       p->has_cos_anneal must be 1 and sched_dev not NULL, else EMAP_E_INVALID.  Same results, bit for bit, as the by-value
+ *                       call with the same two numbers in p.
+ * emap_adam_step_masked_sched : emap_adam_step_masked with lr_geo / lr read from lr_dev[0] / lr_dev[1] (sched_dev itself). */
+int emap_train_schedule(int64_t* iter_dev, int64_t end_iter, double warm_up_end, double fix_geo_end, double anneal_end, double learning_rate,
+                        double learning_rate_geo, double learning_rate_alpha, int same_lr, int64_t flip_start, double flip_saturation_max,
+                        float* sched_dev, void* stream);
+int emap_render_fwd_sched(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p,
+                          const float* rays_o, const float* rays_d, const float* near, const float* far,
+                          const float* t_rand, const float* depth_scale, float* z_vals, float* udf, float* grad3,
+                          const EmapCompositeOut* out, void* workspace, size_t workspace_bytes, int32_t* err_flags,
+                          void* stream, const float* sched_dev);
+int emap_render_bwd_staged_sched(const EmapNetConfig* cfg, const void* packed, int prec, const EmapRenderParams* p, const float* rays_o,
+                                 const float* rays_d, const float* depth_scale, const float* z_vals, const float* udf, const float* grad3,
+                                 const float* sample_dist_dev, const EmapCompositeGrads* g, const EmapParamGrads* out, void* workspace,
+                                 size_t workspace_bytes, int32_t* err_flags, void* stream, int stages, const float* sched_dev);
+int emap_adam_step_masked_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* step_dev, int64_t n, int64_t n_geo,
+                                const float* lr_dev, double beta1, double beta2, float eps, const float* tail_mask, float* tail_step,
+                                void* stream);
+
 /* ---- dense-grid extraction (SURVEY par. 8 f2) ----------------------------------------------------
  * emap_null_direction : `_, _, vh = torch.linalg.svd(grad_ld); F.normalize(vh[:, -1, :])` of get_udf_normals_grid /
  *                       get_udf_normals_slow (src/edge_extraction/extract_pointcloud.py:86-88, 177-179): per point the unit

@@ -2,7 +2,11 @@
 """BASELINE config C5 in miniature: the reference's training loop (src/runner/runner_udf.py:79-168 with the schedules of
 runner_base.py:128-180, time axis compressed) on a multi-view consistent synthetic wire frame, entirely on the HIP path
 (device ray sampler -> render forward -> HIP backward -> fused Adam).  Prints one JSON line: loss / PSNR trajectory, PSNR of a
-held-out view, the learned UDF on and off the wire frame, wall time.  One GPU; `--steps 4000` takes ~10 s."""
+held-out view, the learned UDF on and off the wire frame, wall time.  One GPU; `--steps 4000` takes ~10 s.
+
+`--graph` trains through the captured loop instead: the schedules are evaluated on the device (Trainer(schedule=...)) and the ray
+sampler is part of the graph, so an iteration is one graph replay with no per-step host work.  (Its jitter comes from the sampler's own
+draw, not from torch.rand: the trajectory differs from the default run's in the random numbers only.)"""
 import argparse
 import json
 import math
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--precision", default="f16x3")
     ap.add_argument("--views", type=int, default=16)
     ap.add_argument("--res", type=int, default=200)
+    ap.add_argument("--graph", action="store_true", help="train through Trainer.capture(sampler=...): schedules and ray draw inside one hipGraph")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -45,21 +50,10 @@ def main():
     # igr_weight 0.1, igr_ns_weight 0, edge_weight 1 - the iteration axis scaled by steps / 50000
     lr, lr_geo, alpha, end_iter = 5e-4, 1e-4, 0.05, a.steps
     warm_up_end, anneal_end, flip_start = max(1, end_iter // 50), max(1, end_iter // 5), end_iter // 5
-    t = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.0)
-
-    def lr_factor(it):                                    # runner_base.py:128-141
-        if it < warm_up_end:
-            return it / warm_up_end
-        prog = (it - warm_up_end) / (end_iter - warm_up_end)
-        return (math.cos(math.pi * prog) + 1.0) * 0.5 * (1 - alpha) + alpha
-
-    def lr_geo_factor(it):                                # :143-160 (fix_geo_end = 0)
-        if it < warm_up_end * 2:
-            return it / (warm_up_end * 2)
-        if it < end_iter * 0.5:
-            return 1.0
-        prog = (it - end_iter * 0.5) / (end_iter * 0.5)
-        return (math.cos(math.pi * prog) + 1.0) * 0.5 * (1 - alpha) + alpha
+    sched = emap_amd.TrainSchedule(end_iter=end_iter, warm_up_end=warm_up_end, fix_geo_end=0, anneal_end=anneal_end, learning_rate=lr,
+                                   learning_rate_geo=lr_geo, learning_rate_alpha=alpha, flip_start=flip_start)
+    t = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.0, schedule=sched if a.graph else None)
+    lr_factor, lr_geo_factor = sched.factor, sched.factor_geo      # runner_base.py:128-141, :143-160 (fix_geo_end = 0)
 
     def view_psnr(idx):
         s = sampler.gen_random_rays_patches_at(idx, a.res * a.res, pixels=torch.stack(torch.meshgrid(
@@ -87,7 +81,16 @@ def main():
     t0 = time.perf_counter()
     acc = torch.zeros(2, device=dev)
     every = max(1, a.steps // 20)
+    # --graph: schedules, ray draw and step are one hipGraph; the default: the schedules on the host, every step eager
+    replay = t.capture(sampler=sampler, batch_size=a.rays, importance_sample=True) if a.graph else None
     for it in range(a.steps):
+        if replay is not None:
+            acc += replay()
+            if (it + 1) % every == 0:
+                m = (acc / every).tolist()
+                acc.zero_()
+                log.append({"step": it + 1, "loss": m[0], "edge_loss": m[1], "psnr_batch": 10 * math.log10(1.0 / max(m[1], 1e-12))})
+            continue
         t.optimizer.param_groups[0]["lr"] = lr_geo * lr_geo_factor(it)
         for g_ in t.optimizer.param_groups[1:]:
             g_["lr"] = lr * lr_factor(it)
@@ -111,7 +114,7 @@ def main():
     print(json.dumps({
         "what": "training loop of runner_udf.py on a synthetic wire frame (13 segments, %d views %dx%d, view %d held out), HIP path only"
                 % (a.views, a.res, a.res, held_out),
-        "steps": a.steps, "rays_per_step": a.rays, "precision": a.precision, "wall_s": wall, "ms_per_step_incl_python": wall / a.steps * 1e3,
+        "graph": bool(a.graph), "steps": a.steps, "rays_per_step": a.rays, "precision": a.precision, "wall_s": wall, "ms_per_step_incl_python": wall / a.steps * 1e3,
         "held_out_view_psnr_db": {"before": psnr0[0], "after": psnr1[0]}, "train_view_psnr_db_after": psnr_train[0],
         "mean_udf_on_wireframe": {"before": u0[0], "after": u1[0]}, "mean_udf_away_from_it": {"before": u0[1], "after": u1[1]},
         "variance": float(devn.variance), "beta": float(bet.beta), "gamma": float(bet.gamma),
