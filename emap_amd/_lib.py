@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 
 import torch
 
@@ -79,90 +80,108 @@ class RayBatch(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("rays_o", "rays_v", "edge", "depth_scale", "ndc_uv", "p_cam", "pixels", "img_idx", "t_rand")]
 
 
-# every symbol include/emap_hip.h declares: name -> (restype, argtypes)
+# every symbol include/emap_hip.h declares: name -> (restype, argtypes).  _RC marks an int that is a return code (0 = success): those
+# symbols, and only those, also appear in the checked view api()
 _P = C.c_void_p
+_RC = "rc"
 SYMBOLS = {
     "emap_abi_version": (C.c_int, []),
     "emap_last_error": (C.c_char_p, []),
     "emap_set_grad_mode": (C.c_int, [C.c_int]),
     "emap_set_fused_sampling": (C.c_int, [C.c_int]),
     "emap_set_fused_composite": (C.c_int, [C.c_int]),
-    "emap_packed_bytes": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.POINTER(C.c_size_t)]),
-    "emap_pack_weights": (C.c_int, [C.POINTER(NetConfig), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, C.c_int, _P]),
-    "emap_udf_fwd": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P]),
-    "emap_udf_scratch_bytes": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
-    "emap_udf_fwd_grad": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
-    "emap_embed": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
-    "emap_null_direction": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P]),
-    "emap_lattice_points": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
-    "emap_compact_workspace_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
-    "emap_compact_append": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_int, _P, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
-    "emap_jitter_points": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
-    "emap_shift_points": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
-    "emap_sample_pdf": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
-    "emap_sample_pdf_u": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
-    "emap_upsample_step": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
+    "emap_packed_bytes": (_RC, [C.POINTER(NetConfig), C.c_int, C.POINTER(C.c_size_t)]),
+    "emap_pack_weights": (_RC, [C.POINTER(NetConfig), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, C.c_int, _P]),
+    "emap_udf_fwd": (_RC, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P]),
+    "emap_udf_scratch_bytes": (_RC, [C.POINTER(NetConfig), C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
+    "emap_udf_fwd_grad": (_RC, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P, _P, C.c_size_t, _P]),
+    "emap_embed": (_RC, [_P, C.c_int64, C.c_int, _P, _P]),
+    "emap_null_direction": (_RC, [_P, C.c_int64, C.c_int, _P, _P]),
+    "emap_lattice_points": (_RC, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "emap_compact_workspace_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "emap_compact_append": (_RC, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_int, _P, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "emap_jitter_points": (_RC, [_P, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
+    "emap_shift_points": (_RC, [_P, _P, _P, C.c_int64, _P]),
+    "emap_sample_pdf": (_RC, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "emap_sample_pdf_u": (_RC, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "emap_upsample_step": (_RC, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
                                      _P, _P, _P, _P]),
-    "emap_upsample_step_plain": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
-    "emap_merge_sorted": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
-    "emap_composite_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
+    "emap_upsample_step_plain": (_RC, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "emap_merge_sorted": (_RC, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "emap_composite_fwd": (_RC, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                      C.POINTER(CompositeOut), _P, _P, _P]),
-    "emap_composite_fwd_p": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(RenderParams),
+    "emap_composite_fwd_p": (_RC, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(RenderParams),
                                        C.POINTER(CompositeOut), _P, _P, _P]),
-    "emap_render_workspace_bytes": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
-    "emap_render_fwd": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P,
+    "emap_render_workspace_bytes": (_RC, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
+    "emap_render_fwd": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P,
                                   _P, _P, _P, C.POINTER(CompositeOut), _P, C.c_size_t, _P, _P]),
-    "emap_composite_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(RenderParams),
+    "emap_composite_bwd": (_RC, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(RenderParams),
                                      C.POINTER(CompositeGrads), _P, _P, _P, _P]),
-    "emap_udf_vjp_workspace_bytes": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
-    "emap_udf_vjp": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P, C.POINTER(ParamGrads), _P, C.c_size_t,
+    "emap_udf_vjp_workspace_bytes": (_RC, [C.POINTER(NetConfig), C.c_int, C.c_int64, C.POINTER(C.c_size_t)]),
+    "emap_udf_vjp": (_RC, [C.POINTER(NetConfig), _P, C.c_int, _P, C.c_int64, _P, _P, C.POINTER(ParamGrads), _P, C.c_size_t,
                                _P, _P]),
-    "emap_render_bwd_workspace_bytes": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
-    "emap_render_bwd": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
+    "emap_render_bwd_workspace_bytes": (_RC, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
+    "emap_render_bwd": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
                                   C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P]),
-    "emap_render_bwd_absmax_offset": (C.c_int, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
-    "emap_render_bwd_staged": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
+    "emap_render_bwd_absmax_offset": (_RC, [C.POINTER(NetConfig), C.c_int, C.POINTER(RenderParams), C.POINTER(C.c_size_t)]),
+    "emap_render_bwd_staged": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
                                          C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P, C.c_int]),
-    "emap_sample_rays": (C.c_int, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(RayBatch), _P]),
-    "emap_gen_rays_count": (C.c_int, [C.POINTER(RayDataset), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "emap_gen_rays_at": (C.c_int, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
-    "emap_train_stats": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
-    "emap_train_loss": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, _P, _P]),
-    "emap_adam_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P]),
-    "emap_adam_step_masked": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
-    "emap_train_schedule": (C.c_int, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int64,
+    "emap_sample_rays": (_RC, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(RayBatch), _P]),
+    "emap_gen_rays_count": (_RC, [C.POINTER(RayDataset), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "emap_gen_rays_at": (_RC, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
+    "emap_train_stats": (_RC, [_P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "emap_train_loss": (_RC, [_P, C.c_float, C.c_float, C.c_float, _P, _P]),
+    "emap_adam_step": (_RC, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P]),
+    "emap_adam_step_masked": (_RC, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
+    "emap_train_schedule": (_RC, [_P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int64,
                                       C.c_double, _P, _P]),
-    "emap_render_fwd_sched": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P,
+    "emap_render_fwd_sched": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P,
                                         _P, _P, _P, C.POINTER(CompositeOut), _P, C.c_size_t, _P, _P, _P]),
-    "emap_render_bwd_staged_sched": (C.c_int, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
+    "emap_render_bwd_staged_sched": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
                                                C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P, C.c_int, _P]),
-    "emap_adam_step_masked_sched": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
-    "emap_ar_local_bytes": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t)]),
-    "emap_ar_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p), _P]),
-    "emap_ar_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
-    "emap_ar_close": (C.c_int, [_P]),
-    "emap_ar_free": (C.c_int, [_P]),
-    "emap_ar_allreduce_sum": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, _P]),
-    "emap_ar_error": (C.c_int, [_P, C.POINTER(C.c_int)]),
-    "emap_ar_set_timeout_ms": (C.c_int, [C.c_int64]),
-    "emap_profile_enable": (C.c_int, [C.c_int]),
-    "emap_profile_read": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int)]),
-    "emap_profile_read_kernel": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
-    "emap_profile_read_clock": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
+    "emap_adam_step_masked_sched": (_RC, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
+    "emap_ar_local_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
+    "emap_ar_alloc": (_RC, [C.c_size_t, C.POINTER(C.c_void_p), _P]),
+    "emap_ar_open": (_RC, [_P, C.POINTER(C.c_void_p)]),
+    "emap_ar_close": (_RC, [_P]),
+    "emap_ar_free": (_RC, [_P]),
+    "emap_ar_allreduce_sum": (_RC, [_P, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, _P]),
+    "emap_ar_error": (_RC, [_P, C.POINTER(C.c_int)]),
+    "emap_ar_set_timeout_ms": (_RC, [C.c_int64]),
+    "emap_profile_enable": (_RC, [C.c_int]),
+    "emap_profile_read": (_RC, [C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "emap_profile_read_kernel": (_RC, [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "emap_profile_read_clock": (_RC, [C.c_int, C.POINTER(C.c_float)]),
     "emap_linspace_host": (None, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float)]),
 }
 
-_lib = None
+_lib = _api = None
 
 
 class EmapLibraryError(RuntimeError):
     pass
 
 
+class _Ptr:
+    """argtype of the void* parameters of the checked view: None, an int, a c_void_p, a ctypes array, or anything with .data_ptr()
+    (a tensor).  Only the address is taken: device, dtype and layout are the call site's business (require_cuda, f32c)."""
+
+    @classmethod
+    def from_param(cls, v):
+        dp = getattr(v, "data_ptr", None)
+        return C.c_void_p.from_param(v) if dp is None else C.c_void_p(dp())
+
+
+def _errcheck(rc, fn, args):
+    if rc != 0:
+        check(rc, fn.__name__[5:])
+    return rc
+
+
 def lib():
-    """Load (once) and return the bound library.  Raises EmapLibraryError if it is not built."""
-    global _lib
+    """Load (once) and return the bound library: raw ctypes functions that return the rc.  Raises EmapLibraryError if it is not built."""
+    global _lib, _api
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -174,17 +193,36 @@ def lib():
         l = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise EmapLibraryError(f"cannot load {LIB_PATH}: {e}") from e
+    a = types.SimpleNamespace()
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(l, name)
         except AttributeError as e:
             raise EmapLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype = res
+        fn.restype = C.c_int if res is _RC else res
         fn.argtypes = args
+        if res is _RC:
+            ck = l[name]            # indexing makes a function object of its own; the attribute above is the cached raw one
+            ck.restype, ck.argtypes, ck.errcheck = C.c_int, [_Ptr if t is _P else t for t in args], _errcheck
+            setattr(a, name[5:], ck)
     if l.emap_abi_version() != ABI_VERSION:
         raise EmapLibraryError("libemap_hip.so ABI version mismatch")
-    _lib = l
+    _lib, _api = l, a
     return l
+
+
+def api():
+    """The checked view of lib(): one entry per rc-returning symbol, named without ``emap_`` (``api().render_fwd``).  A call raises
+    what check() raises when the rc is not 0; void* parameters take tensors (_Ptr) and struct parameters take the struct itself.
+    Package code calls the library through this view; lib() is for code that looks at return codes."""
+    return _api if _api is not None else lib() and _api
+
+
+def size_of(query: str, *args) -> int:
+    """The value of a size or offset query - a checked symbol whose last parameter is a size_t*: size_of("packed_bytes", cfg, prec)."""
+    n = C.c_size_t()
+    getattr(api(), query)(*args, n)
+    return n.value
 
 
 def check(rc: int, what: str = ""):

@@ -93,29 +93,67 @@ class ParamLayout:
         return out
 
 
-_WS_MAX_ENTRIES = 8            # distinct launch shapes per cache (training batch, validation chunk, ...): far fewer in practice
+_WS_MAX_ENTRIES = 8            # distinct launch shapes per workspace pool (training batch, validation chunk, ...): far fewer in practice
 _WS_BUDGET_BYTES = 24 << 30    # ... and their total size: the backward's preferred workspace is ~17 KiB per point (8.8 GB at 4096 x 128)
+_CONST_MAX_ENTRIES = 16
 
 
-def _workspace(cache: dict, key, nbytes: int, dev) -> torch.Tensor:
-    """Cached scratch buffer for one launch shape.  The cache keeps one buffer PER KEY and never moves one that is still big enough:
-    a captured hipGraph (UDFRendererBlending.capture, Trainer.capture) has the device pointers of the buffers of ITS shape baked in,
-    so a render of another shape in between (validation.render_image between replays of a training graph) must not evict them.
-    Entries are dropped least-recently-used first once the cache holds more than _WS_MAX_ENTRIES shapes OR more than
-    _WS_BUDGET_BYTES (a caller with a varying point count - UdfFn on ragged extraction batches - would otherwise pin one multi-GB
-    backward workspace per size).  Dropping an entry only drops the CACHE's reference: a captured graph holds its own
-    (``live_buffers``), so its buffers stay where they are.  ``UDFNetwork.backward_workspace_limit`` caps a single workspace."""
-    key = (key, str(dev))
-    ws = cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        cache.pop(key, None)
-        while cache and (len(cache) >= _WS_MAX_ENTRIES or sum(b.numel() for b in cache.values()) + nbytes > _WS_BUDGET_BYTES):
-            cache.pop(next(iter(cache)))
-    else:
-        cache.pop(key)          # re-insert: dict order = recency
-    cache[key] = ws
-    return ws
+class DeviceBuffers:
+    """Every cached device buffer of one owner (a renderer, a UDFNetwork), in named pools: ``pools[name][key]`` is a tensor or a tuple of
+    tensors.  A captured hipGraph (UDFRendererBlending.capture, Trainer.capture) has the device pointers of the buffers of ITS launch
+    shape baked in, so no policy here ever moves or overwrites a buffer that is still big enough, and dropping an entry only drops the
+    CACHE's reference: a graph keeps ``live()`` - everything cached at capture - for as long as it lives."""
+
+    def __init__(self):
+        self.pools = {}
+        self.sizes = {}
+
+    def live(self) -> list:
+        return [b for pool in self.pools.values() for e in pool.values() for b in (e if isinstance(e, tuple) else (e,))]
+
+    def nbytes(self, query: str, key, *args, limit=None) -> int:
+        """``_lib.size_of(query, *args)``, asked once per `key` (what of the arguments the answer depends on), and at most `limit`
+        (``UDFNetwork.backward_workspace_limit``: with less the backward runs in more, smaller chunks)."""
+        n = self.sizes.get((query, key))
+        if n is None:
+            if len(self.sizes) >= 64:       # ragged point counts: the memo stays small
+                self.sizes.clear()
+            n = self.sizes[query, key] = _lib.size_of(query, *args)
+        return n if limit is None else min(n, int(limit))
+
+    def workspace(self, name: str, key, nbytes: int, dev) -> torch.Tensor:
+        """Scratch buffer for one launch shape: one buffer PER KEY, replaced only when it is too small, so a render of another shape in
+        between (validation.render_image between replays of a training graph) does not move it.  Entries are dropped least-recently-used
+        first once the pool holds more than _WS_MAX_ENTRIES shapes OR more than _WS_BUDGET_BYTES (a caller with a varying point count -
+        UdfFn on ragged extraction batches - would otherwise pin one multi-GB backward workspace per size)."""
+        pool = self.pools.setdefault(name, {})
+        key = (key, str(dev))
+        ws = pool.pop(key, None)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            while pool and (len(pool) >= _WS_MAX_ENTRIES or sum(b.numel() for b in pool.values()) + nbytes > _WS_BUDGET_BYTES):
+                pool.pop(next(iter(pool)))
+        pool[key] = ws          # (re-)inserted last: dict order = recency
+        return ws
+
+    def constant(self, name: str, key, make):
+        """``make()`` (tensors nobody writes again), cached under `key`: bounded, oldest dropped first, never replaced in place."""
+        pool = self.pools.setdefault(name, {})
+        c = pool.get(key)
+        if c is None:
+            if len(pool) >= _CONST_MAX_ENTRIES:
+                pool.pop(next(iter(pool)))
+            c = pool[key] = make()
+        return c
+
+    def fixed(self, name: str, key, n: int, dev, dtype=torch.uint8) -> torch.Tensor:
+        """The zero-initialised buffer of exactly `n` elements under `key`, for contents that are rewritten IN PLACE (the packed weights
+        after an optimizer step, the int32 word the kernels OR their error flags into): the same tensor while size and device stay."""
+        pool = self.pools.setdefault(name, {})
+        b = pool.get(key)
+        if b is None or b.numel() != n or b.device != dev:
+            b = pool[key] = torch.zeros(n, dtype=dtype, device=dev)
+        return b
 
 
 class UdfFn(torch.autograd.Function):
@@ -148,17 +186,12 @@ class UdfFn(torch.autograd.Function):
             raise NotImplementedError("emap_amd: d/dx of grad_x udf (a second-order input gradient) is not provided by the HIP backward")
         flat = torch.empty(lay.numel, dtype=torch.float32, device=dev)
         pg, keep = lay.tables(flat)
-        L = _lib.lib()
         prec = _lib.PRECISIONS[net.precision]
         cfg = net.net_config()
-        nb = C.c_size_t()
         with _lib.on_device(xs):
-            _lib.check(L.emap_udf_vjp_workspace_bytes(C.byref(cfg), prec, P, C.byref(nb)), "udf_vjp_workspace_bytes")
-            nbytes = nb.value if net.backward_workspace_limit is None else min(nb.value, int(net.backward_workspace_limit))
-            ws = _workspace(net._vjp_ws, ("udf", P), nbytes, dev)
-            _lib.check(L.emap_udf_vjp(C.byref(cfg), _lib.ptr(net.packed()), prec, _lib.ptr(xs), P, _lib.ptr(du), _lib.ptr(dg),
-                                      C.byref(pg), _lib.ptr(ws), min(ws.numel(), nbytes), _lib.ptr(net.err_word(dev)), _lib.stream_ptr(dev)),
-                       "udf_vjp")
+            nbytes = net._devbuf.nbytes("udf_vjp_workspace_bytes", (prec, P), cfg, prec, P, limit=net.backward_workspace_limit)
+            ws = net._devbuf.workspace("vjp", ("udf", P), nbytes, dev)
+            _lib.api().udf_vjp(cfg, net.packed(), prec, xs, P, du, dg, pg, ws, nbytes, net.err_word(dev), _lib.stream_ptr(dev))
         need = [p.requires_grad for p in lay.tensors]
         dx = None
         if ctx.x_needs:
@@ -189,7 +222,7 @@ class RenderFn(torch.autograd.Function):
         # what the backward reads later must be what this forward used: the sample distance lives in a workspace the next render()
         # of this shape overwrites (other near / far), the packed weights are re-packed after an optimizer step
         v["_sd"] = v["_ws"][:4].clone()
-        ctx.packed_key = renderer.udf_network._pack_cache[_lib.PRECISIONS[call["prec_name"]]][0]
+        ctx.packed_key = renderer.udf_network.packed_key(call["prec_name"])
         return outs
 
     @staticmethod
@@ -201,7 +234,7 @@ class RenderFn(torch.autograd.Function):
                     "(differentiable outputs: edge, depth, gradient_error, gradient_error_near_surface, variance, beta, gamma)")
         r, call, v = ctx.renderer, ctx.call, ctx.v
         packed = r.udf_network.packed(call["prec_name"])
-        if r.udf_network._pack_cache[_lib.PRECISIONS[call["prec_name"]]][0] != ctx.packed_key:
+        if r.udf_network.packed_key(call["prec_name"]) != ctx.packed_key:
             raise RuntimeError("emap_amd: the UDF network's parameters changed between render() and backward() (an optimizer step or an "
                                "in-place edit in between): the gradient would be taken at other weights than the forward used")
         lay = r._layout()

@@ -7,8 +7,6 @@ and this function is not on the render path.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -33,7 +31,7 @@ class Embedder:
         x = _lib.f32c(inputs.reshape(-1, 3))
         out = torch.empty(x.shape[0], self.out_dim, device=x.device, dtype=torch.float32)
         with _lib.on_device(x):
-            _lib.check(_lib.lib().emap_embed(_lib.ptr(x), x.shape[0], self.num_freqs, _lib.ptr(out), _lib.stream_ptr(x.device)), "embed")
+            _lib.api().embed(x, x.shape[0], self.num_freqs, out, _lib.stream_ptr(x.device))
         return out.reshape(*inputs.shape[:-1], self.out_dim)
 
 

@@ -12,8 +12,6 @@ same jitter draws (one ``torch.randn((n, sampling_N, 3), device=device)`` per ``
     3x3 matrices G^T G (``emap_null_direction``): no 50x3 SVD batch.
 There is no CPU fallback: tensors must live on the GPU and libemap_hip.so must be loadable.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -29,8 +27,7 @@ def null_direction(grads: torch.Tensor) -> torch.Tensor:
     out = torch.empty(n, 3, device=g.device, dtype=torch.float32)
     if n:
         with _lib.on_device(g):
-            _lib.check(_lib.lib().emap_null_direction(_lib.ptr(g), C.c_int64(n), k, _lib.ptr(out), _lib.stream_ptr(g.device)),
-                       "null_direction")
+            _lib.api().null_direction(g, n, k, out, _lib.stream_ptr(g.device))
     return out
 
 
@@ -156,11 +153,6 @@ _SURVIVORS0 = 1 << 16    # initial capacity of the survivor buffers (points); th
 _SLOW_SAMPLING_N, _SLOW_SAMPLING_DELTA, _MAX_BATCH = 50, 0.005, 1 << 12    # what the reference's shift stage runs with (:274-281)
 
 
-def _call(name, t, *args):
-    with _lib.on_device(t):
-        _lib.check(getattr(_lib.lib(), name)(*args, _lib.stream_ptr(t.device)), name[5:])
-
-
 def lattice_points(N, first, count, device="cuda", out=None):
     """Points [first, first + count) of the N^3 lattice on [-1, 1]^3, first coordinate slowest: (count, 3), bit-identical to
     ``arange(N) * (2 / (N - 1)) + (-1)`` (the order and fp32 arithmetic of ``get_udf_normals_grid``)."""
@@ -175,7 +167,8 @@ def lattice_points(N, first, count, device="cuda", out=None):
                 and out.shape[0] >= count):
             raise ValueError(f"lattice_points: `out` must be a contiguous float32 GPU tensor of at least ({count}, 3)")
         xyz = out[:count]
-    _call("emap_lattice_points", xyz, int(N), C.c_int64(int(first)), C.c_int64(count), _lib.ptr(xyz))
+    with _lib.on_device(xyz):
+        _lib.api().lattice_points(int(N), int(first), count, xyz, _lib.stream_ptr(xyz.device))
     return xyz
 
 
@@ -187,7 +180,8 @@ def jitter_points(x, noise, delta):
     if x.shape != (n, 3) or noise.shape != (n, k, 3):
         raise ValueError(f"jitter_points: x {tuple(x.shape)} and noise {tuple(noise.shape)} do not match")
     out = torch.empty(n * k, 3, device=x.device, dtype=torch.float32)
-    _call("emap_jitter_points", x, _lib.ptr(x), _lib.ptr(noise), C.c_int64(n), k, C.c_float(delta), _lib.ptr(out))
+    with _lib.on_device(x):
+        _lib.api().jitter_points(x, noise, n, k, delta, out, _lib.stream_ptr(x.device))
     return out
 
 
@@ -199,7 +193,8 @@ def shift_points(x, df, normals):
     if x.shape != (n, 3) or normals.shape != (n, 3) or df.shape != (n,):
         raise ValueError("shift_points: x (n, 3), df (n), normals (n, 3) expected")
     out = torch.empty_like(x)
-    _call("emap_shift_points", x, _lib.ptr(x), _lib.ptr(df), _lib.ptr(normals), C.c_int64(n), _lib.ptr(out))
+    with _lib.on_device(x):
+        _lib.api().shift_points(x, df, normals, n, out, _lib.stream_ptr(x.device))
     return out
 
 
@@ -234,13 +229,12 @@ class Compactor:
             raise ValueError(f"Compactor.append: df ({n}) and xyz {tuple(xyz.shape)} must be n and (n, 3) on {self.state.device}")
         if n == 0:
             return
-        nb = C.c_size_t()
-        _lib.check(_lib.lib().emap_compact_workspace_bytes(C.c_int64(n), C.byref(nb)), "compact_workspace_bytes")
-        if self.ws is None or self.ws.numel() < nb.value:
-            self.ws = torch.empty(nb.value, dtype=torch.uint8, device=self.device)
-        _call("emap_compact_append", df, _lib.ptr(df), _lib.ptr(xyz), C.c_int64(n), C.c_int64(int(first_index)), C.c_float(threshold),
-              int(bool(inclusive)), _lib.ptr(self.xyz), _lib.ptr(self.df), _lib.ptr(self.idx), C.c_int64(self.capacity),
-              _lib.ptr(self.state), _lib.ptr(self.ws), C.c_size_t(self.ws.numel()))
+        nb = _lib.size_of("compact_workspace_bytes", n)
+        if self.ws is None or self.ws.numel() < nb:
+            self.ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        with _lib.on_device(df):
+            _lib.api().compact_append(df, xyz, n, int(first_index), threshold, int(bool(inclusive)), self.xyz, self.df, self.idx,
+                                      self.capacity, self.state, self.ws, self.ws.numel(), _lib.stream_ptr(df.device))
 
     def finish(self):
         """-> (survivors so far, calls appended so far, overflowed).  After an overflow the buffers are already larger and the error

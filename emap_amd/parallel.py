@@ -68,14 +68,11 @@ class OneShotAllReduce:
         self.group, self.device = group, torch.device(device)
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self.n_floats = int(n_floats)
-        L = _lib.lib()
-        nb = C.c_size_t()
-        _lib.check(L.emap_ar_local_bytes(self.n_floats, C.byref(nb)), "ar_local_bytes")
-        self.region_bytes = nb.value
+        self.region_bytes = _lib.size_of("ar_local_bytes", self.n_floats)
         self._own = C.c_void_p()
         handle = (C.c_ubyte * 64)()
         with torch.cuda.device(self.device):
-            _lib.check(L.emap_ar_alloc(self.region_bytes, C.byref(self._own), handle), "ar_alloc")
+            _lib.api().ar_alloc(self.region_bytes, self._own, handle)
         handles = [None] * self.world
         dist.all_gather_object(handles, bytes(handle), group=group)
         self._peers = []
@@ -86,7 +83,7 @@ class OneShotAllReduce:
                     regions[r] = self._own.value
                     continue
                 p = C.c_void_p()
-                _lib.check(L.emap_ar_open((C.c_ubyte * 64).from_buffer_copy(h), C.byref(p)), "ar_open")
+                _lib.api().ar_open((C.c_ubyte * 64).from_buffer_copy(h), p)
                 self._peers.append(p)
                 regions[r] = p.value
         self._regions = regions
@@ -97,14 +94,13 @@ class OneShotAllReduce:
         with the same number of elements, in the same order."""
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() <= self.n_floats
         with torch.cuda.device(t.device):
-            _lib.check(_lib.lib().emap_ar_allreduce_sum(_lib.ptr(t), t.numel(), self.rank, self.world, self._regions, self.region_bytes,
-                                                        _lib.stream_ptr(t.device)), "ar_allreduce_sum")
+            _lib.api().ar_allreduce_sum(t, t.numel(), self.rank, self.world, self._regions, self.region_bytes, _lib.stream_ptr(t.device))
         return t
 
     @staticmethod
     def set_timeout_ms(ms: int):
         """Bound of one peer wait inside the kernel (default 10 s; x6 for a region's first two launches).  Process-wide."""
-        _lib.check(_lib.lib().emap_ar_set_timeout_ms(int(ms)), "ar_set_timeout_ms")
+        _lib.api().ar_set_timeout_ms(int(ms))
 
     def check(self):
         """Raise if a launch gave up waiting for a peer (host read: synchronises).  Such a launch has also written NaN into its bucket
@@ -112,15 +108,15 @@ class OneShotAllReduce:
         unnoticed even where nobody calls this."""
         e = C.c_int()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().emap_ar_error(self._own, C.byref(e)), "ar_error")
+            _lib.api().ar_error(self._own, e)
         if e.value:
             raise RuntimeError("OneShotAllReduce: a peer's buffer did not arrive within the kernel's time-out (a rank died or the ranks do "
                                "not call the collective in lock step)")
 
     def close(self):
-        L = _lib.lib()
         if getattr(self, "_own", None) is None:
             return
+        L = _lib.lib()                           # the raw view: tearing down goes on whatever a call answers
         try:
             torch.cuda.synchronize(self.device)
             dist.barrier(group=self.group)       # nobody unmaps while a peer may still read
@@ -203,27 +199,23 @@ class _FlatAdam:
         n_geo geometry gradients in a buffer of the caller), those of the tail alone: two launches on disjoint ranges with the same
         arithmetic, the geometry range first (it bumps `t`), then the tail with its own step counts.  `lr_dev` (two device floats:
         geometry, tail; one launch only): the learning rates are read on the device and `lr_geo` / `lr_tail` are not used."""
-        L, dev = _lib.lib(), data.device
-        tail = (_lib.ptr(self.tail_mask), _lib.ptr(self.tail_step), _lib.stream_ptr(dev))
+        A, dev = _lib.api(), data.device
+        tail = (self.tail_mask, self.tail_step, _lib.stream_ptr(dev))
         if lr_dev is not None:
             assert geo_grad_ptr is None
             with torch.cuda.device(dev):
-                _lib.check(L.emap_adam_step_masked_sched(_lib.ptr(data), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
-                                                         self.n, self.n_geo, _lib.ptr(lr_dev), float(betas[0]), float(betas[1]), float(eps),
-                                                         *tail), "adam_step_sched")
+                A.adam_step_masked_sched(data, grad, self.m, self.v, self.t, self.n, self.n_geo, lr_dev, float(betas[0]), float(betas[1]),
+                                         float(eps), *tail)
             return
         hyper = (float(lr_geo), float(lr_tail), float(betas[0]), float(betas[1]), float(eps))
         with torch.cuda.device(dev):
             if geo_grad_ptr is None:
-                _lib.check(L.emap_adam_step_masked(_lib.ptr(data), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
-                                                   self.n, self.n_geo, *hyper, *tail), "adam_step")
+                A.adam_step_masked(data, grad, self.m, self.v, self.t, self.n, self.n_geo, *hyper, *tail)
                 return
             ng, nt = self.n_geo, self.n - self.n_geo
-            _lib.check(L.emap_adam_step(_lib.ptr(data), C.c_void_p(geo_grad_ptr), _lib.ptr(self.m), _lib.ptr(self.v), _lib.ptr(self.t),
-                                        ng, ng, *hyper, tail[2]), "adam_step")
+            A.adam_step(data, geo_grad_ptr, self.m, self.v, self.t, ng, ng, *hyper, tail[2])
             if nt > 0:
-                _lib.check(L.emap_adam_step_masked(_lib.ptr(data[ng:]), _lib.ptr(grad), _lib.ptr(self.m[ng:]), _lib.ptr(self.v[ng:]),
-                                                   _lib.ptr(self.spare_t), nt, 0, *hyper, *tail), "adam_step")
+                A.adam_step_masked(data[ng:], grad, self.m[ng:], self.v[ng:], self.spare_t, nt, 0, *hyper, *tail)
 
 
 def _loss_from_stats(stats, n_elem, edge_weight, igr_weight, igr_ns_weight):
@@ -479,8 +471,7 @@ class Trainer:
         if self._sched is not None:      # this iteration's four scheduled numbers, then the counter moves on
             dev = self._sched.device
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().emap_train_schedule(_lib.ptr(self._iter), *self.schedule.c_args(), _lib.ptr(self._sched),
-                                                          _lib.stream_ptr(dev)), "train_schedule")
+                _lib.api().train_schedule(self._iter, *self.schedule.c_args(), self._sched, _lib.stream_ptr(dev))
         if batch is not None:
             rays, true_edge = batch()
         S.call, S.v, edge, S.scalars = self._forward(rays)
@@ -492,8 +483,7 @@ class Trainer:
         assert te.numel() == n_local
         S.d_edge = torch.empty(n_local, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().emap_train_stats(_lib.ptr(edge), _lib.ptr(te), _lib.ptr(S.scalars), n_local, 2.0 * self.edge_weight / S.n_glob,
-                                                   _lib.ptr(S.d_edge), _lib.ptr(self._stats), _lib.stream_ptr(dev)), "train_stats")
+            _lib.api().train_stats(edge, te, S.scalars, n_local, 2.0 * self.edge_weight / S.n_glob, S.d_edge, self._stats, _lib.stream_ptr(dev))
 
     def _ph_composite_bwd(self, S):
         exact = S.sync == "exact"            # self._stats now holds the GLOBAL sums
@@ -548,8 +538,7 @@ class Trainer:
         stats = self._stats_slot() if S.sync == "local" else self._stats      # "local": the all-reduced bucket's tail holds the global sums
         out = torch.empty(2, device=dev)         # a fresh tensor per step: callers keep what step() returned
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().emap_train_loss(_lib.ptr(stats), self.edge_weight / S.n_glob, self.igr_weight, self.igr_ns_weight,
-                                                  _lib.ptr(out), _lib.stream_ptr(dev)), "train_loss")
+            _lib.api().train_loss(stats, self.edge_weight / S.n_glob, self.igr_weight, self.igr_ns_weight, out, _lib.stream_ptr(dev))
         self.last_stats = out
         return out
 

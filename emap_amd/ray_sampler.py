@@ -102,9 +102,8 @@ class DeviceRaySampler:
             else:                            # device pixels: clamped on the device (no host synchronisation)
                 pin = torch.stack([px[:, 0].clamp(0, self.W - 1), px[:, 1].clamp(0, self.H - 1)], -1).to(torch.int64).contiguous()
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().emap_sample_rays(C.byref(self._ds), -1 if img_idx is None else int(img_idx), N, int(bool(importance_sample)),
-                                                   self.seed, 0, _lib.ptr(self._counter), _lib.ptr(pin), C.byref(out),
-                                                   _lib.stream_ptr(dev)), "sample_rays")
+            _lib.api().sample_rays(self._ds, -1 if img_idx is None else int(img_idx), N, int(bool(importance_sample)), self.seed, 0,
+                                   self._counter, pin, out, _lib.stream_ptr(dev))
         rays = {"rays_o": rays_o, "rays_v": rays_v, "edge": edge}
         # "t_rand" is not in the reference's dict: render()'s per-ray jitter (udf_renderer_blending.py:719 draws torch.rand([N,1]) - 0.5 on the
         # host generator), from the same device draw - pass it as render(..., t_rand=sample["t_rand"]) and the step has no host draw at all
@@ -119,7 +118,7 @@ class DeviceRaySampler:
     def view_size(self, resolution_level=1):
         """-> (n, h, w): the (H // l) * (W // l) rays of a view at ``resolution_level`` l and its image size (host only)."""
         n, h, w = C.c_int64(), C.c_int(), C.c_int()
-        _lib.check(_lib.lib().emap_gen_rays_count(C.byref(self._ds), int(resolution_level), C.byref(n), C.byref(h), C.byref(w)), "gen_rays_count")
+        _lib.api().gen_rays_count(self._ds, int(resolution_level), n, h, w)
         return n.value, h.value, w.value
 
     def _view_image(self, img_idx, via_perm):
@@ -154,9 +153,8 @@ class DeviceRaySampler:
         f = out.view(-1)
         rays_o, rays_v, ds = f[:3 * count].view(count, 3), f[3 * count:6 * count].view(count, 3), f[6 * count:7 * count].view(count, 1)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().emap_gen_rays_at(C.byref(self._ds), self._view_image(img_idx, via_perm)[0], int(resolution_level),
-                                                   C.c_int64(first), C.c_int64(count), _lib.ptr(rays_o), _lib.ptr(rays_v), _lib.ptr(ds),
-                                                   _lib.stream_ptr(dev)), "gen_rays_at")
+            _lib.api().gen_rays_at(self._ds, self._view_image(img_idx, via_perm)[0], int(resolution_level), first, count,
+                                   rays_o, rays_v, ds, _lib.stream_ptr(dev))
         return rays_o, rays_v, ds
 
     def gen_rays_at(self, img_idx, resolution_level=1, via_perm=False):

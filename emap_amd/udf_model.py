@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .backward import DeviceBuffers
 from .embedder import get_embedder, embed_torch
 
 DEFAULT_PRECISION = os.environ.get("EMAP_PRECISION", "f16x3")
@@ -76,13 +77,11 @@ class UDFNetwork(nn.Module):
 
         self.activation = nn.Softplus(beta=100)
         self.relu = nn.ReLU()
-        self._pack_cache = {}
-        self._vjp_ws = {}
+        self._devbuf = DeviceBuffers()   # pools: "packed" (per precision), "vjp" (UdfFn's workspaces), "scratch", "err"
+        self._pack_keys = {}              # precision -> the parameter state its packed buffer was made from
         # upper bound in bytes on the backward's workspace (None: the library's preferred size, ~17 KiB per point up to 8.8 GB); with less
         # the backward runs in more, smaller chunks (include/emap_hip.h)
         self.backward_workspace_limit = None
-        self._scratch = {}
-        self._err = None
 
     # ---- packed weights -----------------------------------------------------------------------
     def _gvb(self):
@@ -137,15 +136,10 @@ class UDFNetwork(nn.Module):
         # (without weight_norm the g's are temporaries synthesised by _gvb: only v and b identify the state)
         ident = (gs if self.weight_norm else []) + vs + bs
         key = (prec, vs[0].device, tuple(int(t._version) for t in ident), tuple(t.data_ptr() for t in ident))
-        hit = self._pack_cache.get(prec)
-        if hit is not None and hit[0] == key:
-            return hit[1]
-        L = _lib.lib()
+        if self._pack_keys.get(prec) == key:
+            return self._devbuf.pools["packed"][prec]
         cfg = self.net_config()
-        nbytes = C.c_size_t()
-        _lib.check(L.emap_packed_bytes(C.byref(cfg), prec, C.byref(nbytes)), "packed_bytes")
-        buf = hit[1] if (hit is not None and hit[1].numel() == nbytes.value and hit[1].device == vs[0].device) else \
-            torch.empty(nbytes.value, dtype=torch.uint8, device=vs[0].device)
+        buf = self._devbuf.fixed("packed", prec, _lib.size_of("packed_bytes", cfg, prec), vs[0].device)
         n = len(vs)
         # pointer tables: cached while every source tensor is the contiguous fp32 tensor at the same address it was (the usual case: an
         # optimizer updates in place) - the re-pack after every step then costs one key comparison and one launch on the host
@@ -162,19 +156,21 @@ class UDFNetwork(nn.Module):
             same = all(k_.data_ptr() == t.data_ptr() for ks_, ts in zip(keep, (gs, vs, bs)) for k_, t in zip(ks_, ts))
             self._pack_tables = (ptrs, (ga, va, ba)) if (self.weight_norm and same) else None
         with _lib.on_device(buf):
-            _lib.check(L.emap_pack_weights(C.byref(cfg), ga, va, ba, _lib.ptr(buf), prec, _lib.stream_ptr(buf.device)), "pack_weights")
-        self._pack_cache[prec] = (key, buf)
+            _lib.api().pack_weights(cfg, ga, va, ba, buf, prec, _lib.stream_ptr(buf.device))
+        self._pack_keys[prec] = key
         return buf
+
+    def packed_key(self, precision=None):
+        """The parameter state (versions, addresses) the packed buffer of `precision` was made from: ties RenderFn's backward to its forward."""
+        return self._pack_keys.get(_lib.PRECISIONS[precision or self.precision])
 
     def invalidate_packed(self):
         """Force a re-pack on the next call (after editing parameters through ``.data`` in place).  The packed buffers are KEPT and
         re-packed in place: a captured hipGraph (RenderGraph, Trainer.capture) has their addresses baked in."""
-        self._pack_cache = {prec: (None, buf) for prec, (_, buf) in self._pack_cache.items()}
+        self._pack_keys = {}
 
     def err_word(self, dev):
-        if self._err is None or self._err.device != dev:
-            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
-        return self._err
+        return self._devbuf.fixed("err", 0, 1, dev, torch.int32)
 
     # ---- HIP evaluation -----------------------------------------------------------------------
     def _needs_autograd(self, x):
@@ -189,25 +185,16 @@ class UDFNetwork(nn.Module):
         cfg = self.net_config()
         buf = self.packed(precision)
         udf = torch.empty(P, 1, device=xs.device, dtype=torch.float32)
-        L = _lib.lib()
         if P == 0:
             return udf, (torch.empty(0, 3, device=xs.device, dtype=torch.float32) if with_grad else None)
         with _lib.on_device(xs):
             if with_grad:
                 grad = torch.empty(P, 3, device=xs.device, dtype=torch.float32)
-                nb = C.c_size_t()
-                _lib.check(L.emap_udf_scratch_bytes(C.byref(cfg), prec, P, C.byref(nb)), "udf_scratch_bytes")
-                scr = None
-                if nb.value:
-                    scr = self._scratch.get(xs.device)
-                    if scr is None or scr.numel() < nb.value:
-                        scr = torch.empty(nb.value, dtype=torch.uint8, device=xs.device)
-                        self._scratch = {xs.device: scr}
-                _lib.check(L.emap_udf_fwd_grad(C.byref(cfg), _lib.ptr(buf), prec, _lib.ptr(xs), P, _lib.ptr(udf), _lib.ptr(grad),
-                                              _lib.ptr(scr), nb.value, _lib.stream_ptr(xs.device)), "udf_fwd_grad")
+                nb = _lib.size_of("udf_scratch_bytes", cfg, prec, P)
+                scr = self._devbuf.workspace("scratch", None, nb, xs.device) if nb else None      # one buffer, grown when too small
+                _lib.api().udf_fwd_grad(cfg, buf, prec, xs, P, udf, grad, scr, nb, _lib.stream_ptr(xs.device))
                 return udf, grad
-            _lib.check(L.emap_udf_fwd(C.byref(cfg), _lib.ptr(buf), prec, _lib.ptr(xs), P, _lib.ptr(udf),
-                                     _lib.stream_ptr(xs.device)), "udf_fwd")
+            _lib.api().udf_fwd(cfg, buf, prec, xs, P, udf, _lib.stream_ptr(xs.device))
         return udf, None
 
     # ---- reference interface ------------------------------------------------------------------

@@ -13,12 +13,10 @@ construction.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from .backward import ParamLayout, RenderFn, _workspace
+from .backward import DeviceBuffers, ParamLayout, RenderFn
 
 _PER_SAMPLE = ("weights", "alpha", "mid_z", "dists", "inside_sphere", "gradient_mag")
 
@@ -32,12 +30,10 @@ def sample_pdf(bins, weights, n_samples, det=False):
     out = torch.empty(N, n_samples, device=b.device, dtype=torch.float32)
     with _lib.on_device(b):
         if det:
-            _lib.check(_lib.lib().emap_sample_pdf(_lib.ptr(b), _lib.ptr(w), N, n, n_samples, _lib.ptr(out), None, None,
-                                                  _lib.stream_ptr(b.device)), "sample_pdf")
+            _lib.api().sample_pdf(b, w, N, n, n_samples, out, None, None, _lib.stream_ptr(b.device))
         else:
             u = torch.rand([N, n_samples]).to(b.device).contiguous()
-            _lib.check(_lib.lib().emap_sample_pdf_u(_lib.ptr(b), _lib.ptr(w), _lib.ptr(u), N, n, n_samples, _lib.ptr(out), None, None,
-                                                    _lib.stream_ptr(b.device)), "sample_pdf_u")
+            _lib.api().sample_pdf_u(b, w, u, N, n, n_samples, out, None, None, _lib.stream_ptr(b.device))
     return out
 
 
@@ -119,13 +115,9 @@ class UDFRendererBlending:
         self.host_mirror_scalars = False  # variance / beta / gamma of the render dict answer host reads from a pinned copy made BEFORE the forward
         self.direct_param_grads = False   # RenderFn.backward installs its flat gradient buffer's views as .grad itself (no 32 AccumulateGrad clones)
         self._mirror = None
-        self._ws = {}
-        self._ws_pool = {}
-        self._bws = {}
-        self._bws_bytes = {}
-        self._err = None
+        self._devbuf = DeviceBuffers()   # pools: "render", "backward" (workspaces), "scratch" (reduced mode), "nearfar", "err"
+        self._jitter = None               # ring of pinned host buffers (_jitter_draw)
         self._lay = None
-        self._const = {}
 
     # ---- helpers ------------------------------------------------------------------------------
     @property
@@ -164,14 +156,18 @@ class UDFRendererBlending:
         p.render_mode = self.render_mode
         return p
 
+    def _err_word(self, dev):
+        return self._devbuf.fixed("err", 0, 1, dev, torch.int32)
+
     def error_flags(self) -> int:
         """Device error word (NaN in sample_pdf / gradient_error). Reading it synchronises: call it lazily."""
-        return 0 if self._err is None else int(self._err.item())
+        e = self._devbuf.pools.get("err", {}).get(0)
+        return 0 if e is None else int(e.item())
 
     def check_errors(self):
         f = self.error_flags()
         if f:
-            self._err.zero_()
+            self._devbuf.pools["err"][0].zero_()
             raise RuntimeError(f"emap_amd render: non-finite values detected on device (flags={f}: "
                                f"{'z_samples ' if f & _lib.F_NAN_SAMPLES else ''}{'gradient_error ' if f & _lib.F_NAN_GRADERR else ''}"
                                f"{'MLP output (fp16 range exceeded? use precision=bf16x3) ' if f & _lib.F_MLP_NONFINITE else ''})")
@@ -191,15 +187,8 @@ class UDFRendererBlending:
         prec_name = self.precision or net.precision
         ro, rd = _lib.f32c(rays_o.detach()), _lib.f32c(rays_d.detach())
         if not isinstance(near, torch.Tensor):
-            key = ("nf", N, float(near), float(far), dev)
-            nf = self._const.get(key)
-            if nf is None:
-                nf = (torch.full((N,), float(near), device=dev, dtype=torch.float32),
-                      torch.full((N,), float(far), device=dev, dtype=torch.float32))
-                if len(self._const) > 16:       # bounded; never replaces a live entry in place (a captured graph may point at it)
-                    self._const.pop(next(k for k in self._const if k not in ("_scr", "_jit")))
-                self._const[key] = nf
-            near_t, far_t = nf
+            near_t, far_t = self._devbuf.constant("nearfar", (N, float(near), float(far), dev), lambda: (
+                torch.full((N,), float(near), device=dev, dtype=torch.float32), torch.full((N,), float(far), device=dev, dtype=torch.float32)))
         else:
             near_t = _lib.f32c(near.detach().to(dev)).reshape(-1).expand(N).contiguous()
             far_t = _lib.f32c(far.detach().to(dev)).reshape(-1).expand(N).contiguous()
@@ -212,16 +201,17 @@ class UDFRendererBlending:
         ds = _lib.f32c(depth_scale.detach().to(dev)).reshape(-1) if depth_scale is not None else None
         return {"N": N, "S": self.samples_per_ray, "dev": dev, "prec_name": prec_name, "ro": ro, "rd": rd, "near": near_t,
                 "far": far_t, "t_rand": tr, "ds": ds, "reduced": reduced,
+                "shape": (N, self.n_samples, self.n_importance, self.up_sample_steps),     # what the library's workspace sizes depend on
                 "p": self._params(N, cos_anneal_ratio, flip_saturation, background_rgb)}
 
     def _jitter_draw(self, N, dev):
         """(torch.rand([N, 1]) - 0.5).to(dev) - the same values from the same CPU generator - through a small ring of pinned staging
         buffers, so that the copy is asynchronous (a pageable host-to-device copy costs ~0.12 ms of host time per step).  A slot is
         reused only after its copy has completed (event)."""
-        ring = self._const.get("_jit")
+        ring = self._jitter
         if ring is None or ring["N"] != N or ring["dev"] != dev:
-            ring = {"N": N, "dev": dev, "i": 0, "slots": [(torch.empty(N, 1).pin_memory(), torch.cuda.Event()) for _ in range(4)]}
-            self._const["_jit"] = ring
+            ring = self._jitter = {"N": N, "dev": dev, "i": 0,
+                                   "slots": [(torch.empty(N, 1).pin_memory(), torch.cuda.Event()) for _ in range(4)]}
         buf, ev = ring["slots"][ring["i"] % 4]
         if ring["i"] >= 4:
             ev.synchronize()
@@ -253,41 +243,28 @@ class UDFRendererBlending:
             v[k] = flat[off:off + n]
             off += n
         if reduced:   # the MLP's own outputs are intermediates here: a cached scratch, not a fresh allocation
-            sc = _workspace(self._const.setdefault("_scr", {}), (N, S), 4 * sum(mlp_out.values()), dev).view(torch.float32)
+            sc = self._devbuf.workspace("scratch", (N, S), 4 * sum(mlp_out.values()), dev).view(torch.float32)
             off = 0
             for k, n in mlp_out.items():
                 v[k] = sc[off:off + n]
                 off += n
         p = call["p"]
-        L = _lib.lib()
         cfg = net.net_config()
+        B = self._devbuf
         with _lib.on_device(call["ro"]):
-            key = (N, str(dev), prec)
-            ws = self._ws.get(key)
-            if ws is None:
-                nb = C.c_size_t()
-                _lib.check(L.emap_render_workspace_bytes(C.byref(cfg), prec, C.byref(p), C.byref(nb)), "render_workspace_bytes")
-                ws = _workspace(self._ws_pool, key, nb.value, dev)   # one buffer per launch shape, never evicted by another shape
-                if len(self._ws) >= 8:
-                    self._ws.pop(next(iter(self._ws)))
-                self._ws[key] = ws
-            if self._err is None or self._err.device != dev:
-                self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+            ws = B.workspace("render", (N, prec), B.nbytes("render_workspace_bytes", (call["shape"], prec), cfg, prec, p), dev)
             co = _lib.CompositeOut()
             names = ("edge", "depth", "weight_sum", "normals", "scalars") if reduced else \
                 _PER_SAMPLE + ("gradients_flip", "edge", "depth", "weight_sum", "normals", "scalars")
             for k in names:
                 setattr(co, k, v[k].data_ptr())
-            packed = net.packed(call["prec_name"])
-            args = (C.byref(cfg), _lib.ptr(packed), prec, C.byref(p), _lib.ptr(call["ro"]), _lib.ptr(call["rd"]),
-                    _lib.ptr(call["near"]), _lib.ptr(call["far"]), _lib.ptr(call["t_rand"]), _lib.ptr(call["ds"]),
-                    _lib.ptr(v["z_vals"]), _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), C.byref(co), _lib.ptr(ws),
-                    ws.numel(), _lib.ptr(self._err), _lib.stream_ptr(dev))
+            args = (cfg, net.packed(call["prec_name"]), prec, p, call["ro"], call["rd"], call["near"], call["far"], call["t_rand"],
+                    call["ds"], v["z_vals"], v["udf"], v["gradients"], co, ws, ws.numel(), self._err_word(dev), _lib.stream_ptr(dev))
             # call["sched"]: the device words of emap_train_schedule - cos_anneal_ratio / flip_saturation are read from them, not from p
             if call.get("sched") is None:
-                _lib.check(L.emap_render_fwd(*args), "render_fwd")
+                _lib.api().render_fwd(*args)
             else:
-                _lib.check(L.emap_render_fwd_sched(*args, _lib.ptr(call["sched"])), "render_fwd_sched")
+                _lib.api().render_fwd_sched(*args, call["sched"])
         v["_ws"] = ws
         return v
 
@@ -326,45 +303,34 @@ class UDFRendererBlending:
         pg, keep = lay.tables(flat)
         pg.grad_scale = float(grad_scale)
         p = call["p"]
-        L = _lib.lib()
         cfg = net.net_config()
         if packed is None:
             packed = net.packed(call["prec_name"])
         with _lib.on_device(call["ro"]):
-            nbk = (N, S, prec, self.n_samples, self.n_importance, self.up_sample_steps)
-            nbv = self._bws_bytes.get(nbk)
-            if nbv is None:
-                nb = C.c_size_t()
-                _lib.check(L.emap_render_bwd_workspace_bytes(C.byref(cfg), prec, C.byref(p), C.byref(nb)), "render_bwd_workspace_bytes")
-                nbv = self._bws_bytes[nbk] = nb.value
-            lim = net.backward_workspace_limit
-            ws = _workspace(self._bws, (N, S, prec), nbv if lim is None else min(nbv, int(lim)), dev)
-            args = (C.byref(cfg), _lib.ptr(packed), prec, C.byref(p),
-                    _lib.ptr(call["ro"]), _lib.ptr(call["rd"]), _lib.ptr(call["ds"]), _lib.ptr(v["z_vals"]),
-                    _lib.ptr(v["udf"]), _lib.ptr(v["gradients"]), _lib.ptr(v.get("_sd", v["_ws"])), C.byref(cg), C.byref(pg),
-                    _lib.ptr(ws), ws.numel() if lim is None else min(ws.numel(), int(lim)), _lib.ptr(self._err),
-                    _lib.stream_ptr(dev), int(stages))
+            ws, nbytes = self._backward_workspace(call, cfg, prec)
+            args = (cfg, packed, prec, p, call["ro"], call["rd"], call["ds"], v["z_vals"], v["udf"], v["gradients"], v.get("_sd", v["_ws"]),
+                    cg, pg, ws, nbytes, self._err_word(dev), _lib.stream_ptr(dev), int(stages))
             if call.get("sched") is None:
-                _lib.check(L.emap_render_bwd_staged(*args), "render_bwd")
+                _lib.api().render_bwd_staged(*args)
             else:      # the forward's device-fed scalars (_render_hip)
-                _lib.check(L.emap_render_bwd_staged_sched(*args, _lib.ptr(call["sched"])), "render_bwd_sched")
+                _lib.api().render_bwd_staged_sched(*args, call["sched"])
         return flat
+
+    def _backward_workspace(self, call, cfg, prec):
+        """(the backward's workspace of this launch shape, the byte count of it the library is given)."""
+        nbytes = self._devbuf.nbytes("render_bwd_workspace_bytes", (call["shape"], prec), cfg, prec, call["p"],
+                                      limit=self.udf_network.backward_workspace_limit)
+        return self._devbuf.workspace("backward", (call["N"], call["S"], prec), nbytes, call["dev"]), nbytes
 
     def bwd_absmax(self, call):
         """The two floats [max|dL/dudf|, max|dL/dgrad|] a stages=1 backward_into() left in the backward workspace, as a float32
         view of that workspace: what a data-parallel step max-reduces over its ranks before the stages=2 call, so that every rank's
         MLP backward uses the same fp16 range scale (emap_hip.h: emap_render_bwd_staged)."""
-        N, S, dev = call["N"], call["S"], call["dev"]
         prec = _lib.PRECISIONS[call["prec_name"]]
         cfg = self.udf_network.net_config()
-        p = call["p"]
-        L = _lib.lib()
-        nb, off = C.c_size_t(), C.c_size_t()
-        _lib.check(L.emap_render_bwd_workspace_bytes(C.byref(cfg), prec, C.byref(p), C.byref(nb)), "render_bwd_workspace_bytes")
-        _lib.check(L.emap_render_bwd_absmax_offset(C.byref(cfg), prec, C.byref(p), C.byref(off)), "render_bwd_absmax_offset")
-        lim = self.udf_network.backward_workspace_limit
-        ws = _workspace(self._bws, (N, S, prec), nb.value if lim is None else min(nb.value, int(lim)), dev)
-        return ws[off.value:off.value + 8].view(torch.float32)
+        ws, _ = self._backward_workspace(call, cfg, prec)
+        off = self._devbuf.nbytes("render_bwd_absmax_offset", (call["shape"], prec), cfg, prec, call["p"])
+        return ws[off:off + 8].view(torch.float32)
 
     def _trainable(self):
         if not torch.is_grad_enabled():
@@ -467,11 +433,7 @@ class UDFRendererBlending:
     def live_buffers(self):
         """Strong references to every cached device buffer the launch chain may currently point at (workspaces, near/far constants,
         reduced-mode scratch, error word, packed weights, scratch of the UDF network): a captured graph keeps this list."""
-        net = self.udf_network
-        keep = [list(self._ws.values()), list(self._ws_pool.values()), list(self._bws.values()), self._err,
-                [v for k, v in self._const.items() if k not in ("_scr", "_jit")], list(self._const.get("_scr", {}).values()),
-                [b for _, b in net._pack_cache.values()], list(net._vjp_ws.values()), list(net._scratch.values()), net._err]
-        return keep
+        return self._devbuf.live() + self.udf_network._devbuf.live()
 
     def render_reduced(self, rays_o, rays_d, near, far, depth_scale, cos_anneal_ratio=None, perturb_overwrite=-1,
                        background_rgb=None, flip_saturation=0, t_rand=None):
