@@ -24,6 +24,7 @@ PREC_F16X3E = 5    # f16x3 with f16 cross terms in both sweeps of the value+grad
 PRECISIONS = {"bf16": PREC_BF16, "bf16x3": PREC_BF16X3, "f16": PREC_F16, "f16x3": PREC_F16X3, "f16x3m": PREC_F16X3M, "f16x3e": PREC_F16X3E}
 UDF_TYPES = {"abs": 0, "square": 1, "sdf": 2}
 MAX_LIN = 12
+MAX_TRAIN_IMAGES = 1024      # EMAP_MAX_TRAIN_IMAGES: the longest list DeviceRaySampler.set_train_images takes
 MAX_SAMPLES_PER_RAY = 1024   # EMAP_MAX_SAMPLES_PER_RAY: S = n_samples + up_sample_steps * (n_importance // up_sample_steps)
 ABI_VERSION = 12   # ABI 12 removed emap_set_value_tile_mode (the 32x32 value kernel)
 
@@ -128,6 +129,8 @@ SYMBOLS = {
     "emap_render_bwd_staged": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
                                          C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P, C.c_int]),
     "emap_sample_rays": (_RC, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _P, _P, C.POINTER(RayBatch), _P]),
+    "emap_check_train_images": (_RC, [C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "emap_sample_rays_train": (_RC, [C.POINTER(RayDataset), _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_uint64, _P, _P, C.POINTER(RayBatch), _P]),
     "emap_gen_rays_count": (_RC, [C.POINTER(RayDataset), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "emap_gen_rays_at": (_RC, [C.POINTER(RayDataset), C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "emap_train_stats": (_RC, [_P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),

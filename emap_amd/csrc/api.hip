@@ -658,6 +658,13 @@ int emap_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int impor
     return launch_sample_rays(ds, img_idx, batch, importance, seed, offset, counter_dev, pixels_in, out, static_cast<hipStream_t>(stream));
 }
 
+int emap_check_train_images(const int32_t* images, int n_train, int n_images) { return check_train_images(images, n_train, n_images); }
+int emap_sample_rays_train(const EmapRayDataset* ds, const int32_t* train_images, int n_train, int32_t* perm, int64_t* epoch_tag, int batch,
+                           int importance, uint64_t seed, uint64_t* counter_dev, const int64_t* pixels_in, const EmapRayBatch* out, void* stream) {
+    return launch_sample_rays_train(ds, train_images, n_train, perm, epoch_tag, batch, importance, seed, counter_dev, pixels_in, out,
+                                    static_cast<hipStream_t>(stream));
+}
+
 int emap_gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w) {
     return gen_rays_count(ds, resolution_level, n, h, w);
 }

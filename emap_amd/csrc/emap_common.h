@@ -337,6 +337,9 @@ void linspace_host(float start, float end, int steps, float* out);
 // rays.hip
 int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset, uint64_t* counter,
                        const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st);
+int check_train_images(const int32_t* images, int n_train, int n_images);
+int launch_sample_rays_train(const EmapRayDataset* ds, const int32_t* train_images, int n_train, int32_t* perm, int64_t* epoch_tag, int batch,
+                             int importance, uint64_t seed, uint64_t* counter, const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st);
 int gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w);
 int launch_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
                        float* depth_scale, hipStream_t st);

@@ -40,9 +40,19 @@ struct Philox {
 // uniform integer in [0, n) from 32 random bits (multiply-shift; bias < n / 2^32)
 __device__ __forceinline__ int rand_below(uint32_t r, int n) { return (int)(((uint64_t)r * (uint64_t)n) >> 32); }
 
+// The training list of emap_sample_rays_train: position step % n of perm, which holds epoch step / n's order of `images` (null: perm is
+// fixed).  `tag` is the epoch perm was computed for.
+struct EpochArgs {
+    const int32_t* images;
+    int32_t* perm;
+    int64_t* tag;
+    int32_t n;               // 0: the launch is emap_sample_rays' (ds.image_perm, step % n_images)
+};
+
 struct RayArgs {
     EmapRayDataset ds;
     EmapRayBatch out;
+    EpochArgs ep;
     const int64_t* pixels_in;
     const uint64_t* counter;
     uint64_t* bump;          // the counter again when THIS launch increments it (single-workgroup launches), else null
@@ -52,11 +62,45 @@ struct RayArgs {
 
 __device__ __forceinline__ void sample_ray(const RayArgs& a, uint64_t step, int i);
 
+// The image order of epoch e = step / n, by ONE workgroup (every thread of it calls this): perm[j] = images[sigma(j)], sigma the stable
+// argsort of the n keys Philox(seed, stream 2^63 | e, index i) words 0 (high) and 1 (low) - a stream the ray draws (stream = step < 2^63)
+// never reach.  One lane per image (strided where the workgroup is smaller), rank = number of smaller keys.  Nothing happens while the
+// buffer's tag is e already, so a step inside an epoch pays one load; a counter written from outside (resume, a capture's rollback)
+// makes the tag differ and the order follows.
+__device__ __forceinline__ void reshuffle_epoch(const EpochArgs& t, uint64_t seed, uint64_t step) {
+    __shared__ uint64_t keys[EMAP_MAX_TRAIN_IMAGES];
+    const uint64_t e = step / (uint64_t)t.n;
+    if (*t.tag == (int64_t)e) return;                           // uniform; the tag is written behind two barriers below
+    for (int i = threadIdx.x; i < t.n; i += blockDim.x) {
+        uint32_t r[4];
+        Philox::gen(seed, 0x8000000000000000ull | e, (uint64_t)i, r);
+        keys[i] = ((uint64_t)r[0] << 32) | r[1];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < t.n; i += blockDim.x) {
+        const uint64_t k = keys[i];
+        int rank = 0;
+        for (int j = 0; j < t.n; ++j) {
+            const uint64_t kj = keys[j];
+            rank += (kj < k || (kj == k && j < i)) ? 1 : 0;
+        }
+        t.perm[rank] = t.images[i];
+    }
+    __syncthreads();                                            // perm is complete (and visible to the workgroup) from here on
+    if (threadIdx.x == 0) *t.tag = (int64_t)e;
+}
+
+// batch > 1024 only: the order is brought up to date by a launch of its own, ahead of the many-workgroup sample kernel
+__global__ __launch_bounds__(1024) void reshuffle_epoch_kernel(const EpochArgs t, const uint64_t* counter, uint64_t seed) {
+    reshuffle_epoch(t, seed, *counter);
+}
+
 // batch <= 1024: ONE workgroup, which also increments the step counter once every lane has read it (a second launch for that cost 4.8 us of
 // a 6 us job); larger batches: 256-thread workgroups and bump_counter_kernel behind them
 __global__ __launch_bounds__(1024) void sample_rays_kernel(const RayArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t step = a.counter ? *a.counter : a.offset;
+    if (a.ep.images && a.bump) reshuffle_epoch(a.ep, a.seed, step);      // (a.bump: this is the single workgroup)
     if (i < a.batch) sample_ray(a, step, i);
     if (a.bump) {
         __syncthreads();
@@ -66,7 +110,10 @@ __global__ __launch_bounds__(1024) void sample_rays_kernel(const RayArgs a) {
 
 __device__ __forceinline__ void sample_ray(const RayArgs& a, uint64_t step, int i) {
     int img = a.img_idx;
-    if (img < 0) img = a.ds.image_perm ? a.ds.image_perm[step % (uint64_t)a.ds.n_images] : (int)(step % (uint64_t)a.ds.n_images);
+    if (img < 0) {
+        if (a.ep.n > 0) img = a.ep.perm[step % (uint64_t)a.ep.n];
+        else img = a.ds.image_perm ? a.ds.image_perm[step % (uint64_t)a.ds.n_images] : (int)(step % (uint64_t)a.ds.n_images);
+    }
     const int H = a.ds.H, W = a.ds.W, HW = H * W;
     int px, py;
     uint32_t r[4];
@@ -117,7 +164,7 @@ __device__ __forceinline__ void sample_ray(const RayArgs& a, uint64_t step, int 
 
 __global__ void bump_counter_kernel(uint64_t* c) { *c += 1; }
 
-int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
+static int sample_rays(const EmapRayDataset* ds, const EpochArgs& ep, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
                        uint64_t* counter, const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st) {
     if (!ds || !out) { set_error("sample_rays: null pointer"); return EMAP_E_INVALID; }
     if (!ds->edges || !ds->kinv || !ds->pose || ds->n_images < 1 || ds->H < 2 || ds->W < 2) { set_error("sample_rays: incomplete dataset"); return EMAP_E_INVALID; }
@@ -125,16 +172,48 @@ int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int imp
     if (importance && !pixels_in && (!ds->pixel_order || !ds->n_edge || !ds->density)) { set_error("sample_rays: importance sampling needs pixel_order / n_edge / density"); return EMAP_E_INVALID; }
     if (batch <= 0) return EMAP_OK;
     RayArgs a;
-    a.ds = *ds; a.out = *out; a.pixels_in = pixels_in; a.counter = counter; a.seed = seed; a.offset = offset;
+    a.ds = *ds; a.out = *out; a.ep = ep; a.pixels_in = pixels_in; a.counter = counter; a.seed = seed; a.offset = offset;
     a.img_idx = img_idx; a.batch = batch; a.importance = importance;
     const bool one_wg = batch <= 1024;
     a.bump = one_wg ? counter : nullptr;
     if (one_wg) hipLaunchKernelGGL(sample_rays_kernel, dim3(1), dim3((batch + 63) / 64 * 64), 0, st, a);
     else {
+        if (ep.images) hipLaunchKernelGGL(reshuffle_epoch_kernel, dim3(1), dim3(1024), 0, st, ep, counter, seed);
         hipLaunchKernelGGL(sample_rays_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, a);
         if (counter) hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, st, counter);
     }
     return check_launch("sample_rays");
+}
+
+int launch_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
+                       uint64_t* counter, const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st) {
+    return sample_rays(ds, EpochArgs{nullptr, nullptr, nullptr, 0}, img_idx, batch, importance, seed, offset, counter, pixels_in, out, st);
+}
+
+// ---- a training list with a new order every epoch (runner_udf.py:46, 249-250) ----
+int check_train_images(const int32_t* images, int n_train, int n_images) {
+    if (!images) { set_error("check_train_images: null list"); return EMAP_E_INVALID; }
+    if (n_images < 1) { set_error("check_train_images: n_images must be >= 1 (got %d)", n_images); return EMAP_E_INVALID; }
+    if (n_train <= 0) { set_error("check_train_images: the list is empty (n_train = %d)", n_train); return EMAP_E_INVALID; }
+    if (n_train > EMAP_MAX_TRAIN_IMAGES) { set_error("check_train_images: %d images, at most %d", n_train, EMAP_MAX_TRAIN_IMAGES); return EMAP_E_INVALID; }
+    for (int i = 0; i < n_train; ++i) {
+        if (images[i] < 0 || images[i] >= n_images) { set_error("check_train_images: entry %d is image %d, outside [0, %d)", i, images[i], n_images); return EMAP_E_INVALID; }
+        for (int j = 0; j < i; ++j)
+            if (images[j] == images[i]) { set_error("check_train_images: image %d appears twice (entries %d and %d)", images[i], j, i); return EMAP_E_INVALID; }
+    }
+    return EMAP_OK;
+}
+
+int launch_sample_rays_train(const EmapRayDataset* ds, const int32_t* train_images, int n_train, int32_t* perm, int64_t* epoch_tag, int batch,
+                             int importance, uint64_t seed, uint64_t* counter, const int64_t* pixels_in, const EmapRayBatch* out, hipStream_t st) {
+    if (!ds || !out || !perm || !counter) { set_error("sample_rays_train: null pointer (ds, out, perm and counter_dev are required)"); return EMAP_E_INVALID; }
+    if (train_images && !epoch_tag) { set_error("sample_rays_train: train_images without epoch_tag"); return EMAP_E_INVALID; }
+    if (n_train <= 0) { set_error("sample_rays_train: n_train must be >= 1 (got %d)", n_train); return EMAP_E_INVALID; }
+    if (n_train > EMAP_MAX_TRAIN_IMAGES || n_train > ds->n_images) {
+        set_error("sample_rays_train: n_train %d above the limit (%d, and the %d images of the dataset)", n_train, EMAP_MAX_TRAIN_IMAGES, ds->n_images);
+        return EMAP_E_INVALID;
+    }
+    return sample_rays(ds, EpochArgs{train_images, perm, epoch_tag, n_train}, -1, batch, importance, seed, 0, counter, pixels_in, out, st);
 }
 
 // ---- full-image rays: Dataset.gen_rays_at (dataset.py:137-167) ----------------------------------------------------------------------

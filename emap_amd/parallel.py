@@ -29,6 +29,10 @@ the two learning rates, cos_anneal_ratio, flip_saturation) on the device: every 
 evaluates them from a device iteration counter, and the render, the backward and Adam read them from device memory.  A captured step
 then follows the schedules, and with ``capture(sampler=...)`` the ray draw is in the graph too: one replay is one whole iteration of
 runner_udf.py:63-170 with no per-step host work.
+
+``Trainer.state_dict / load_state_dict`` (``save_checkpoint / load_checkpoint``) write and read the reference's checkpoint
+(runner_udf.py:252-275: the three modules, the optimizer in torch.optim.Adam's layout, iter_step) plus one ``emap_native`` entry; a
+load writes every buffer in place, so a captured step goes on from it.
 """
 from __future__ import annotations
 
@@ -389,8 +393,8 @@ class Trainer:
 
     @staticmethod
     def sampler_batch(sampler, batch_size: int, importance_sample: bool = False):
-        """-> (rays, true_edge) of one training batch from a DeviceRaySampler, image ``image_perm[counter % n_images]``: what
-        runner_udf.py:70-90 hands to render(), with the jitter draw of the same launch as rays['t_rand']."""
+        """-> (rays, true_edge) of one training batch from a DeviceRaySampler, image ``image_perm[counter % n_images]`` (or, after
+        ``sampler.set_train_images``, the counter's position in its epoch's order of the training list): what runner_udf.py:70-90 hands to render(), with the jitter draw of the same launch as rays['t_rand']."""
         if sampler.near is None or sampler.far is None:
             raise ValueError("Trainer.sampler_batch: the sampler has no near / far (DeviceRaySampler(..., near=, far=) or from_meta)")
         smp = sampler.gen_random_rays_patches_at(-1, batch_size, importance_sample)
@@ -726,6 +730,210 @@ class Trainer:
         replay.segmented = bool(segmented)
         replay._keep = keep
         return replay
+
+
+    # ---- checkpoints: the reference's dict (runner_udf.py:269-275) plus one namespaced extra ----
+    CKPT_VERSION = 1
+    _CKPT_KEYS = ("udf_network_fine", "variance_network_fine", "beta_network", "optimizer", "iter_step")
+
+    def _ckpt_modules(self):
+        r = self.r
+        return {"udf_network_fine": r.udf_network, "variance_network_fine": r.deviation_network, "beta_network": r.beta_network}
+
+    def _ckpt_params(self):
+        """The parameters in the order of the reference's optimizer (runner_base.py:106-117): group 0 the UDF network's, group 1 variance,
+        second_variance, beta, gamma, zeta (group 2 is empty)."""
+        m = self._ckpt_modules()
+        return list(m["udf_network_fine"].parameters()), list(m["variance_network_fine"].parameters()) + list(m["beta_network"].parameters())
+
+    def _adam_state(self):
+        """-> (m, v: flat moments, the geometry range's step count, [the step count of every tail element]).  The native tail keeps
+        exactly this (_FlatAdam).  The torch tail (CPU tests) has one step count for the three scalars: an element carries it while its
+        parameter is trainable, 0 otherwise.  Reads step counters: a host synchronisation."""
+        n, s0 = self.flat.numel, self.flat.span(self.scalars)[0]
+        if self.native_tail:
+            a = self._adam
+            return a.m, a.v, float(a.t.item()), a.tail_step[:n - s0].tolist()
+        m, v, steps = torch.zeros(n, device=self.flat.data.device), torch.zeros(n, device=self.flat.data.device), []
+        for p, (a, b) in ((self.p_geo, (0, s0)), (self.p_sc, (s0, n))):
+            st = self.optimizer.state.get(p)
+            steps.append(float(st["step"]) if st else 0.0)
+            if st:
+                m[a:b], v[a:b] = st["exp_avg"], st["exp_avg_sq"]
+        return m, v, steps[0], [steps[1] if f else 0.0 for f, p in zip(self._scalar_flags(), self.scalars) for _ in range(p.numel())]
+
+    def state_dict(self, sampler=None) -> dict:
+        """A checkpoint in the reference's layout (runner_udf.py:269-275) - ``Runner_UDF.load_checkpoint`` reads it - plus ``emap_native``:
+
+          udf_network_fine, variance_network_fine, beta_network   the modules' state_dict(), cloned
+          optimizer    what torch.optim.Adam built as in runner_base.py:110-117 over the modules returns from state_dict(): per-parameter
+                       step / exp_avg / exp_avg_sq cut from the flat moments (a parameter that never stepped - second_variance, zeta, a
+                       frozen variance - has no entry, as in torch); group lr = the schedule's value at the last step taken, or
+                       param_groups[*]["lr"] without a schedule
+          iter_step    int: the device schedule counter; without a schedule the geometry range's step count
+          emap_native  {version, eikonal_sync, lag, lag_valid[, sampler: ``sampler.state_dict()``]}
+
+        Nothing in it aliases a live buffer.  Reading the counters synchronises with the device: this is off the step path.  Every rank
+        of a data-parallel run returns the same dict."""
+        out = {k: {n: t.detach().clone() for n, t in mod.state_dict().items()} for k, mod in self._ckpt_modules().items()}
+        m, v, t_geo, tail = self._adam_state()
+        s0 = self.flat.span(self.scalars)[0]
+        it = int(self._iter.item()) if self._iter is not None else int(t_geo)
+        g = self.optimizer.param_groups
+        lr_geo, lr = g[0]["lr"], g[1]["lr"]
+        if self.schedule is not None and it > 0:
+            lr_geo, lr = self.schedule.values(it - 1)[:2]
+        geo, rest = self._ckpt_params()
+        # the skeleton (groups, their keys, the parameter numbering) is a stock Adam's of the installed torch: its load_state_dict accepts it
+        skel = torch.optim.Adam([{"params": geo, "lr": float(lr_geo)}, {"params": rest}, {"params": []}], lr=float(lr),
+                                betas=tuple(g[0]["betas"]), eps=g[0]["eps"])
+        for p in geo + rest:
+            off = self.flat.offsets.get(id(p))
+            step = 0.0 if off is None else (t_geo if off < s0 else tail[off - s0])
+            if step > 0:
+                k = p.numel()
+                skel.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m[off:off + k].view(p.shape).clone(),
+                                 "exp_avg_sq": v[off:off + k].view(p.shape).clone()}
+        out["optimizer"] = skel.state_dict()
+        out["iter_step"] = it
+        out["emap_native"] = {"version": self.CKPT_VERSION, "eikonal_sync": self.eikonal_sync, "lag": self._lag.detach().clone(),
+                              "lag_valid": bool(self._lag_valid)}
+        if sampler is not None:
+            out["emap_native"]["sampler"] = sampler.state_dict()
+        return out
+
+    def _check_ckpt(self, ckpt, sampler):
+        """Everything load_state_dict can refuse, before it writes: -> (m, v, t_geo, tail steps, lag, lag_valid, group lrs / betas / eps,
+        the sampler's state or None).  ValueError names the key."""
+        E = lambda key, why: ValueError(f"Trainer.load_state_dict: '{key}' {why}")
+        for k in self._CKPT_KEYS:
+            if k not in ckpt:
+                raise E(k, "is missing")
+        for k, mod in self._ckpt_modules().items():
+            for name, t in mod.state_dict().items():
+                if name not in ckpt[k]:
+                    raise E(f"{k}.{name}", "is missing")
+                if tuple(ckpt[k][name].shape) != tuple(t.shape):
+                    raise E(f"{k}.{name}", f"has shape {tuple(ckpt[k][name].shape)}, the module's is {tuple(t.shape)}")
+            extra = set(ckpt[k]) - set(mod.state_dict())
+            if extra:
+                raise E(f"{k}.{sorted(extra)[0]}", "is not a key of the module")
+        opt = ckpt["optimizer"]
+        for k in ("state", "param_groups"):
+            if k not in opt:
+                raise E(f"optimizer.{k}", "is missing")
+        geo, rest = self._ckpt_params()
+        ids = [i for grp in opt["param_groups"] for i in grp["params"]]
+        live = [grp for grp in opt["param_groups"] if len(grp["params"])]
+        if len(ids) != len(geo) + len(rest) or len(live) != 2 or len(live[0]["params"]) != len(geo):
+            raise E("optimizer.param_groups", f"must hold {len(geo)} + {len(rest)} parameters in two non-empty groups (runner_base.py:110-117)")
+        n, s0 = self.flat.numel, self.flat.span(self.scalars)[0]
+        dev = self.flat.data.device
+        m, v, tail, geo_steps = torch.zeros(n, device=dev), torch.zeros(n, device=dev), [0.0] * (n - s0), set()
+        for i, p in zip(ids, geo + rest):
+            st = opt["state"].get(i)
+            if st:
+                for k in ("step", "exp_avg", "exp_avg_sq"):
+                    if k not in st:
+                        raise E(f"optimizer.state[{i}].{k}", "is missing")
+                    if k != "step" and tuple(st[k].shape) != tuple(p.shape):
+                        raise E(f"optimizer.state[{i}].{k}", f"has shape {tuple(st[k].shape)}, the parameter's is {tuple(p.shape)}")
+            step = float(st["step"]) if st else 0.0
+            off = self.flat.offsets.get(id(p))
+            if off is None:               # second_variance, zeta: not trained here; a reference checkpoint has no state for them either
+                continue
+            k = p.numel()
+            if st:
+                m[off:off + k] = st["exp_avg"].reshape(-1).to(dev, torch.float32)
+                v[off:off + k] = st["exp_avg_sq"].reshape(-1).to(dev, torch.float32)
+            if off < s0:
+                geo_steps.add(step)
+            else:
+                tail[off - s0:off - s0 + k] = [step] * k
+        if len(geo_steps) > 1:
+            raise E("optimizer.state[*].step", f"of the UDF network's parameters disagree ({sorted(geo_steps)}): they step together here")
+        if not self.native_tail and len({x for x in tail if x > 0}) > 1:
+            raise E("optimizer.state[*].step", "of variance / beta / gamma disagree: the torch tail keeps one step count for the three")
+        it = ckpt["iter_step"]
+        if isinstance(it, bool) or not isinstance(it, int) or it < 0:
+            raise E("iter_step", f"must be an int >= 0 (got {it!r})")
+        nat = ckpt.get("emap_native")
+        lag, lag_valid, smp = torch.zeros(2, device=dev), False, None
+        if nat is not None:           # (a checkpoint the reference wrote has none: the native extras start afresh)
+            if "version" not in nat:
+                raise E("emap_native.version", "is missing")
+            if int(nat["version"]) > self.CKPT_VERSION:
+                raise E("emap_native.version", f"is {nat['version']}: written by a later format than this build's {self.CKPT_VERSION}")
+            for k in ("lag", "lag_valid"):
+                if k not in nat:
+                    raise E(f"emap_native.{k}", "is missing")
+            if tuple(nat["lag"].shape) != (2,):
+                raise E("emap_native.lag", f"has shape {tuple(nat['lag'].shape)}, not (2,)")
+            lag, lag_valid, smp = nat["lag"].to(dev, torch.float32), bool(nat["lag_valid"]), nat.get("sampler")
+        if sampler is not None and smp is not None:
+            sampler.check_state_dict(smp)
+        groups = [(float(grp["lr"]), tuple(grp["betas"]), float(grp["eps"])) for grp in live]
+        return m, v, (geo_steps.pop() if geo_steps else 0.0), tail, lag, lag_valid, groups, smp
+
+    @torch.no_grad()
+    def load_state_dict(self, ckpt, sampler=None):
+        """Resume from `ckpt` - state_dict()'s, or one the reference wrote (no ``emap_native``: the native extras start at their initial
+        values, a parameter without optimizer state gets zero moments and step 0, and `sampler`'s counter becomes iter_step, the position
+        the runner's ``image_perm[iter_step % len]`` is at).  Everything is validated first (ValueError naming the key: a missing key, a
+        shape mismatch, geometry parameters whose step counts disagree, an emap_native.version from the future) and a failed load leaves
+        every buffer as it was.  Then every buffer is written IN PLACE - parameters through the modules' own load_state_dict (the views of
+        the flat buffer survive), the moments and step counts, the schedule counter, the lagged maxima, the sampler's counter and list -
+        so a replay captured before the load goes on from the loaded state without re-capture, and a capture after it rolls its warm-up
+        back onto the loaded state.  Without a schedule the group learning rates (betas, eps) are restored as torch restores them; with
+        one the schedule is their only source."""
+        m, v, t_geo, tail, lag, lag_valid, groups, smp = self._check_ckpt(ckpt, sampler)
+        for k, mod in self._ckpt_modules().items():
+            mod.load_state_dict(ckpt[k])
+        n, s0 = self.flat.numel, self.flat.span(self.scalars)[0]
+        if self.native_tail:
+            a = self._adam
+            a.m.copy_(m); a.v.copy_(v); a.t.fill_(t_geo)
+            a.tail_step[:n - s0].copy_(torch.tensor(tail))
+        else:
+            t_tail = max(tail) if tail else 0.0
+            for p, (lo, hi), step in ((self.p_geo, (0, s0), t_geo), (self.p_sc, (s0, n), t_tail)):
+                st = self.optimizer.state.get(p)
+                if not st:
+                    if step <= 0:
+                        continue
+                    grp = self.optimizer.param_groups[0]
+                    on_dev = grp.get("capturable") or grp.get("fused")
+                    st = self.optimizer.state[p] = {"step": torch.zeros((), dtype=torch.float32, device=p.device if on_dev else "cpu"),
+                                                    "exp_avg": torch.zeros_like(p.data), "exp_avg_sq": torch.zeros_like(p.data)}
+                st["step"].fill_(step)
+                st["exp_avg"].copy_(m[lo:hi])
+                st["exp_avg_sq"].copy_(v[lo:hi])
+        if self._iter is not None:
+            self._iter.fill_(int(ckpt["iter_step"]))
+        else:
+            for grp, (lr, betas, eps) in zip(self.optimizer.param_groups, groups):
+                grp["lr"], grp["betas"], grp["eps"] = lr, betas, eps
+        self._lag.copy_(lag)
+        self._lag_valid = lag_valid
+        if sampler is not None:
+            if smp is not None:
+                sampler.load_state_dict(smp)
+            else:
+                sampler._counter.fill_(int(ckpt["iter_step"]))
+        self.r.udf_network.invalidate_packed()
+
+    def save_checkpoint(self, path, sampler=None):
+        """torch.save(state_dict(sampler), path).  Every rank of a data-parallel run calls it (state_dict() is the same on all of them)
+        and rank 0 writes."""
+        ckpt = self.state_dict(sampler)
+        if _world(self.group) == 1 or dist.get_rank(self.group) == 0:
+            torch.save(ckpt, path)
+
+    def load_checkpoint(self, path, sampler=None):
+        """load_state_dict(torch.load(path, map_location=<the trainer's device>), sampler); returns the checkpoint's dict."""
+        ckpt = torch.load(path, map_location=self.flat.data.device)
+        self.load_state_dict(ckpt, sampler)
+        return ckpt
 
 
 class FusedAdam(torch.optim.Optimizer):

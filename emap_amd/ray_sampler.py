@@ -14,6 +14,10 @@ caller (dataset.py:133-135) - image decoding is outside the hot path and stays w
 ``gen_rays_at`` / ``rays_at_flat`` are the rays of a whole validation view with the interface of ``Dataset.gen_rays_at``
 (dataset.py:137-167), from the same device-resident K^-1 and poses (``emap_gen_rays_at``: one launch, 28 B written per ray).
 
+``set_train_images`` walks a list of training images in a new order every epoch (the runner's ``torch.randperm`` per epoch,
+runner_udf.py:249-250), re-derived on the device from the step counter; ``state_dict`` / ``load_state_dict`` are the sampler's part of a
+checkpoint (``Trainer.save_checkpoint(path, sampler)``).
+
 The host RNG streams (torch CPU generator, python ``random``) cannot be reproduced on a device: the draw is a
 Philox4x32-10 stream keyed by ``seed``; the deterministic part (rays of given pixels) and the sampling distribution are what
 the parity tests pin.
@@ -56,6 +60,9 @@ class DeviceRaySampler:
         self._kinv = self.intrinsics_all_inv[:, :3, :3].contiguous().to(dev)
         self._pose = P.contiguous().to(dev)
         self._perm, self._perm_host = None, None
+        # set_train_images: [0, cap) the list, [cap, 2 cap) the current epoch's order of it (csrc/rays.hip), and the epoch that order is of.
+        # Allocated once: a captured graph holds their addresses
+        self._train, self._reshuffle, self._train_buf, self._epoch_tag = None, True, None, None
         self._counter = torch.zeros(1, dtype=torch.int64, device=dev)   # device-resident step counter (uint64 bits)
         self._ds = _lib.RayDataset(self._edges.data_ptr(), self._order.data_ptr(), self._n_edge.data_ptr(), self._density.data_ptr(),
                                    self._kinv.data_ptr(), self._pose.data_ptr(), None, self.n_images, self.H, self.W, 0)
@@ -70,11 +77,72 @@ class DeviceRaySampler:
         return cls(edges, K, P, device=device, seed=seed, near=box["near"], far=box["far"])
 
     def set_image_perm(self, perm):
-        """The runner's ``image_perm`` (runner_udf.py:79-82): with it ``img_idx=None`` walks the permutation on the device."""
+        """The runner's ``image_perm`` (runner_udf.py:79-82): with it ``img_idx=None`` walks the permutation on the device.  The list must
+        have ``n_images`` entries (the kernel indexes it with ``step % n_images``); a shorter training list is ``set_train_images``."""
         perm = torch.as_tensor(perm, dtype=torch.int32).contiguous()
         self._perm_host = perm.cpu().tolist()
         self._perm = perm.to(self.device)
         self._ds.image_perm = self._perm.data_ptr()
+
+    def set_train_images(self, images=None, reshuffle=True):
+        """The images ``img_idx=None`` trains on (default: all), in a new order every epoch like the runner's ``torch.randperm`` per epoch
+        (runner_udf.py:46, 249-250).  ``images``: distinct image ids, at most ``_lib.MAX_TRAIN_IMAGES``; fewer than ``n_images`` holds views
+        out.  With L = len(images), step s of the device counter draws from position s % L of the order of epoch e = s // L,
+        ``perm_e[j] = images[sigma_e(j)]`` with sigma_e the stable argsort of the L 64-bit keys (word 0 << 32 | word 1) of
+        Philox4x32-10(key seed, stream 2**63 | e, index i) - a pure function of (seed, e, images): the counter is the whole state, and any
+        sampler with the same seed and list walks the same order.  The sample kernel recomputes the order on the device whenever the
+        counter has left the epoch its buffer holds (no host work per step; follows a counter written by a resume or a capture's
+        rollback).  ``reshuffle=False``: every epoch walks ``images`` in the order given.
+
+        The buffers are written in place, so a graph captured with a list of the same length follows a new list; L itself is a launch
+        argument: capture again after changing it.  ``set_image_perm`` is not used while a training list is set."""
+        imgs = list(range(self.n_images)) if images is None else [int(i) for i in images]
+        L = _lib.lib()
+        if L.emap_check_train_images((C.c_int32 * max(len(imgs), 1))(*imgs), len(imgs), self.n_images) != 0:
+            raise ValueError("DeviceRaySampler.set_train_images: " + L.emap_last_error().decode("utf-8", "replace"))
+        cap = min(self.n_images, _lib.MAX_TRAIN_IMAGES)
+        if self._train_buf is None:
+            self._train_buf = torch.zeros(2 * cap, dtype=torch.int32, device=self.device)
+            self._epoch_tag = torch.full((1,), -1, dtype=torch.int64, device=self.device)
+        lst = torch.tensor(imgs, dtype=torch.int32)
+        self._train_buf[:len(imgs)].copy_(lst)
+        self._train_buf[cap:cap + len(imgs)].copy_(lst)
+        self._epoch_tag.fill_(-1)
+        self._train, self._reshuffle = imgs, bool(reshuffle)
+
+    # ---- the sampler's part of a checkpoint (Trainer.state_dict(sampler=...)); host only ----
+    def state_dict(self):
+        """seed, the device step counter (read: synchronises), the training list and its reshuffle flag, n_images - all of the sampler's
+        state: the image order is a function of these (set_train_images)."""
+        return {"seed": self.seed, "counter": int(self._counter.item()), "train_images": None if self._train is None else list(self._train),
+                "reshuffle": bool(self._reshuffle), "n_images": self.n_images}
+
+    def check_state_dict(self, state):
+        """Raise ValueError (naming the key) where load_state_dict would; changes nothing."""
+        for k in ("seed", "counter", "train_images", "reshuffle", "n_images"):
+            if k not in state:
+                raise ValueError(f"DeviceRaySampler.load_state_dict: missing key '{k}'")
+        if int(state["n_images"]) != self.n_images:
+            raise ValueError(f"DeviceRaySampler.load_state_dict: 'n_images' is {state['n_images']}, this sampler has {self.n_images}")
+        if int(state["counter"]) < 0:
+            raise ValueError(f"DeviceRaySampler.load_state_dict: 'counter' is negative ({state['counter']})")
+        imgs = state["train_images"]
+        if imgs is not None:
+            imgs = [int(i) for i in imgs]
+            L = _lib.lib()
+            if L.emap_check_train_images((C.c_int32 * max(len(imgs), 1))(*imgs), len(imgs), self.n_images) != 0:
+                raise ValueError("DeviceRaySampler.load_state_dict: 'train_images': " + L.emap_last_error().decode("utf-8", "replace"))
+
+    def load_state_dict(self, state):
+        """In place: the counter's and the training list's buffers keep their addresses, so a captured graph goes on from the loaded
+        state (the seed and the list's length are launch arguments: a graph captured with other ones must be captured again)."""
+        self.check_state_dict(state)
+        self.seed = int(state["seed"])
+        if state["train_images"] is None:
+            self._train = None
+        else:
+            self.set_train_images(state["train_images"], state["reshuffle"])
+        self._counter.fill_(int(state["counter"]))
 
     def gen_random_rays_patches_at(self, img_idx, batch_size, importance_sample=False, pixels=None):
         """-> the reference's ``sample`` dict (dataset.py:288-305), every tensor on the device.  img_idx=None: the image is
@@ -102,8 +170,14 @@ class DeviceRaySampler:
             else:                            # device pixels: clamped on the device (no host synchronisation)
                 pin = torch.stack([px[:, 0].clamp(0, self.W - 1), px[:, 1].clamp(0, self.H - 1)], -1).to(torch.int64).contiguous()
         with torch.cuda.device(dev):
-            _lib.api().sample_rays(self._ds, -1 if img_idx is None else int(img_idx), N, int(bool(importance_sample)), self.seed, 0,
-                                   self._counter, pin, out, _lib.stream_ptr(dev))
+            if self._train is not None and (img_idx is None or int(img_idx) < 0):
+                cap = self._train_buf.numel() // 2
+                _lib.api().sample_rays_train(self._ds, self._train_buf if self._reshuffle else None, len(self._train), self._train_buf[cap:],
+                                             self._epoch_tag, N, int(bool(importance_sample)), self.seed, self._counter, pin, out,
+                                             _lib.stream_ptr(dev))
+            else:
+                _lib.api().sample_rays(self._ds, -1 if img_idx is None else int(img_idx), N, int(bool(importance_sample)), self.seed, 0,
+                                       self._counter, pin, out, _lib.stream_ptr(dev))
         rays = {"rays_o": rays_o, "rays_v": rays_v, "edge": edge}
         # "t_rand" is not in the reference's dict: render()'s per-ray jitter (udf_renderer_blending.py:719 draws torch.rand([N,1]) - 0.5 on the
         # host generator), from the same device draw - pass it as render(..., t_rand=sample["t_rand"]) and the step has no host draw at all
@@ -129,6 +203,9 @@ class DeviceRaySampler:
             if not 0 <= img_idx < self.n_images:
                 raise IndexError(f"DeviceRaySampler: image {img_idx} out of range ({self.n_images} images)")
             return img_idx, img_idx
+        if self._train is not None:
+            raise ValueError("DeviceRaySampler: via_perm addresses set_image_perm's list; with set_train_images active a position is "
+                             "ambiguous (it depends on the epoch) - pass the image id")
         k = img_idx % self.n_images
         return -1 - k, (k if self._perm_host is None else self._perm_host[k])
 

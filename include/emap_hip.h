@@ -353,6 +353,28 @@ typedef struct EmapRayBatch {
 int emap_sample_rays(const EmapRayDataset* ds, int img_idx, int batch, int importance, uint64_t seed, uint64_t offset,
                      uint64_t* counter_dev, const int64_t* pixels_in, const EmapRayBatch* out, void* stream);
 
+/* ---- a training list that is reshuffled every epoch (src/runner/runner_udf.py:46, 249-250: a new torch.randperm per epoch) ------
+ * Added functions only (no struct or signature of ABI 12 changes; ds->image_perm and ds->reserved are not read on this path).
+ * emap_sample_rays_train : emap_sample_rays with img_idx < 0 over a list of n_train <= EMAP_MAX_TRAIN_IMAGES distinct images, which may be
+ *                          shorter than n_images (held-out views): step s = *counter_dev draws from perm[s % n_train], and perm holds the order
+ *                          of epoch e = s / n_train:
+ *                            perm[j] = train_images[sigma_e(j)],  sigma_e = the stable argsort of the keys k_i, i in [0, n_train),
+ *                            k_i = (w0 << 32) | w1 of Philox4x32-10(key = seed, stream = 2^63 | e, index = i)
+ *                          - a pure function of (seed, e, train_images); the ray draws use stream = s < 2^63 and never meet it.  The
+ *                          kernel recomputes perm (n_train int32, device) whenever *epoch_tag (int64, device) differs from e and then
+ *                          writes e there: initialise the tag to -1; a counter written from outside is followed at the next launch.  Up to
+ *                          1024 rays this is a prologue of the sample kernel's one workgroup, above a launch of one workgroup ahead of it.
+ *                          train_images == NULL: perm is read as it is (a fixed order) and epoch_tag is not used.
+ *                          counter_dev is required.  The list's entries index the dataset on the device: check them first with
+ * emap_check_train_images: host only, launches nothing: the list (HOST memory) has 1 .. EMAP_MAX_TRAIN_IMAGES entries, each in [0, n_images),
+ *                          no entry twice.
+ * Both fail with EMAP_E_INVALID (text in emap_last_error) before any launch: a NULL pointer, n_train <= 0, n_train above the limit (or above
+ * ds->n_images), and for the check an entry out of range or repeated. */
+#define EMAP_MAX_TRAIN_IMAGES 1024
+int emap_check_train_images(const int32_t* images, int n_train, int n_images);
+int emap_sample_rays_train(const EmapRayDataset* ds, const int32_t* train_images, int n_train, int32_t* perm, int64_t* epoch_tag, int batch,
+                           int importance, uint64_t seed, uint64_t* counter_dev, const int64_t* pixels_in, const EmapRayBatch* out, void* stream);
+
 /* ---- full-image rays: Dataset.gen_rays_at (src/dataset/dataset.py:137-167) -------------------------------------------------
  * Added functions only (no struct or signature of ABI 12 changes).
  * emap_gen_rays_count : n = (H // l) * (W // l) rays, h = H // l, w = W // l of a view at resolution_level l (any of the three may be

@@ -7,6 +7,8 @@ rounds so that drift of the shared host hits all of them alike:
 
   scheduled     captured step with the schedule on the device (capture(rays, true_edge), fixed rays)
   iteration     the same with the ray sampler inside the graph (capture(sampler=...)): one replay = one whole reference iteration
+  reshuffle     `iteration` with sampler.set_train_images(): the image order is re-derived on the device at every epoch boundary
+  parent_iter   `iteration` on the checkout of the parent commit (`--parent-tree DIR`; skipped without it)
   by_value      captured step of THIS build with the four numbers baked in (schedule=None)
   parent        captured step of a checkout of the parent commit with its own library built (`--parent-tree DIR`; skipped without it)
   eager_host    the eager loop scripts/train_synthetic.py runs by default: schedules on the host, sampler launch, torch.rand jitter, step()
@@ -25,7 +27,9 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-VARIANTS = ("scheduled", "iteration", "by_value", "parent", "eager_host")
+VARIANTS = ("scheduled", "iteration", "reshuffle", "parent_iter", "by_value", "parent", "eager_host")
+ITERATION = ("iteration", "reshuffle", "parent_iter")
+IN_PARENT = ("parent", "parent_iter")
 
 
 def worker(a):
@@ -47,15 +51,17 @@ def worker(a):
     near, far = float(meta["scene_box"]["near"]), float(meta["scene_box"]["far"])
     N = a.rays
     sched = None
-    if a.worker in ("scheduled", "iteration", "eager_host"):
+    if a.worker in ("scheduled", "eager_host") + ITERATION:
         sched = emap_amd.TrainSchedule()          # ABC.conf: 50 000 iterations - the timed window stays in the warm-up branch
-    on_device = {"schedule": sched} if a.worker in ("scheduled", "iteration") else {}      # (the parent's Trainer has no such argument)
+    on_device = {"schedule": sched} if a.worker in ("scheduled",) + ITERATION else {}      # (the parent's Trainer has no such argument)
     tr = Trainer(r, lr_geo=1e-4, lr=5e-4, igr_weight=0.1, **on_device)
     smp = sampler.gen_random_rays_patches_at(None, N, importance_sample=True)
     rays = {"rays_o": smp["rays"]["rays_o"], "rays_d": smp["rays"]["rays_v"], "near": near, "far": far, "depth_scale": smp["depth_scale"],
             "t_rand": torch.rand(N, 1, device=dev) - 0.5}
     te = smp["rays"]["edge"]
-    if a.worker == "iteration":
+    if a.worker == "reshuffle":
+        sampler.set_train_images()
+    if a.worker in ITERATION:
         one = tr.capture(sampler=sampler, batch_size=N, importance_sample=True)
     elif a.worker == "eager_host":
         it = [0]
@@ -97,18 +103,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--only", help="comma-separated subset of the variants")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.worker:
         return worker(a)
-    variants = [v for v in VARIANTS if v != "parent" or a.parent_tree]
+    ap_only = a.only.split(",") if a.only else VARIANTS
+    variants = [v for v in VARIANTS if v in ap_only and (v not in IN_PARENT or a.parent_tree)]
     res = {v: [] for v in variants}
     for rnd in range(a.rounds):
         for v in variants:
             cmd = [sys.executable, os.path.abspath(__file__), "--worker", v, "--rays", str(a.rays), "--steps", str(a.steps), "--warmup", str(a.warmup),
                    "--repeats", str(a.repeats)]
             env = dict(os.environ)
-            if v == "parent":
+            if v in IN_PARENT:
                 cmd += ["--tree", os.path.abspath(a.parent_tree)]
                 env.pop("EMAP_HIP_LIB", None)
             p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
@@ -124,10 +132,13 @@ def main():
     for v in variants:
         x = res[v]
         lines.append(f"{v:12s} {statistics.median(x):9.4f} {min(x):9.4f} {max(x):9.4f}   {' '.join('%.4f' % q for q in x)}")
-    base = "parent" if "parent" in res else "by_value"
-    d = statistics.median(res["scheduled"]) - statistics.median(res[base])
-    spread = max(max(res[v]) - min(res[v]) for v in ("scheduled", base))
-    lines.append(f"scheduled - {base}: {d * 1e3:+.1f} us per step; run-to-run spread of the two (max - min of the round medians): {spread * 1e3:.1f} us")
+    for new, bases in (("scheduled", ("parent", "by_value")), ("reshuffle", ("parent_iter", "iteration"))):
+        base = next((b for b in bases if b in res), None)
+        if new not in res or base is None:
+            continue
+        d = statistics.median(res[new]) - statistics.median(res[base])
+        spread = max(max(res[v]) - min(res[v]) for v in (new, base))
+        lines.append(f"{new} - {base}: {d * 1e3:+.1f} us per step; run-to-run spread of the two (max - min of the round medians): {spread * 1e3:.1f} us")
     text = "\n".join(lines)
     print(text)
     if a.out:

@@ -6,7 +6,11 @@ held-out view, the learned UDF on and off the wire frame, wall time.  One GPU; `
 
 `--graph` trains through the captured loop instead: the schedules are evaluated on the device (Trainer(schedule=...)) and the ray
 sampler is part of the graph, so an iteration is one graph replay with no per-step host work.  (Its jitter comes from the sampler's own
-draw, not from torch.rand: the trajectory differs from the default run's in the random numbers only.)"""
+draw, not from torch.rand: the trajectory differs from the default run's in the random numbers only.)
+
+The training views (all but the held-out one) are walked in a new order every epoch (DeviceRaySampler.set_train_images).  `--save PATH`
+writes a checkpoint in the reference's layout at the end (`--save-every K`: also every K steps) and `--resume PATH` continues from one:
+the run goes on at the checkpoint's iteration, up to `--steps`."""
 import argparse
 import json
 import math
@@ -32,6 +36,9 @@ def main():
     ap.add_argument("--views", type=int, default=16)
     ap.add_argument("--res", type=int, default=200)
     ap.add_argument("--graph", action="store_true", help="train through Trainer.capture(sampler=...): schedules and ray draw inside one hipGraph")
+    ap.add_argument("--save", metavar="PATH", help="write Trainer.save_checkpoint(PATH, sampler) at the end of the run")
+    ap.add_argument("--save-every", type=int, default=0, metavar="K", help="with --save: also after every K steps")
+    ap.add_argument("--resume", metavar="PATH", help="Trainer.load_checkpoint(PATH, sampler) before the first step")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -44,7 +51,7 @@ def main():
     meta, edges = synthetic.make_wireframe_scene(n_images=a.views, H=a.res, W=a.res)
     sampler = emap_amd.DeviceRaySampler.from_meta(meta, edges, device=dev, seed=5)
     held_out = 0
-    sampler.set_image_perm([i for i in range(a.views) if i != held_out])
+    sampler.set_train_images([i for i in range(a.views) if i != held_out])
     near, far = float(meta["scene_box"]["near"]), float(meta["scene_box"]["far"])
     # ABC.conf: learning_rate 5e-4, learning_rate_geo 1e-4, alpha 0.05, end_iter 50000, warm_up_end 1000, anneal_end 10000,
     # igr_weight 0.1, igr_ns_weight 0, edge_weight 1 - the iteration axis scaled by steps / 50000
@@ -54,6 +61,9 @@ def main():
                                    learning_rate_geo=lr_geo, learning_rate_alpha=alpha, flip_start=flip_start)
     t = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.0, schedule=sched if a.graph else None)
     lr_factor, lr_geo_factor = sched.factor, sched.factor_geo      # runner_base.py:128-141, :143-160 (fix_geo_end = 0)
+    first = 0
+    if a.resume:                   # parameters, Adam state, the iteration and the sampler's counter (hence the image order), in place
+        first = int(t.load_checkpoint(a.resume, sampler)["iter_step"])
 
     def view_psnr(idx):
         s = sampler.gen_random_rays_patches_at(idx, a.res * a.res, pixels=torch.stack(torch.meshgrid(
@@ -83,7 +93,9 @@ def main():
     every = max(1, a.steps // 20)
     # --graph: schedules, ray draw and step are one hipGraph; the default: the schedules on the host, every step eager
     replay = t.capture(sampler=sampler, batch_size=a.rays, importance_sample=True) if a.graph else None
-    for it in range(a.steps):
+    for it in range(first, a.steps):
+        if a.save and a.save_every > 0 and it > first and it % a.save_every == 0:
+            t.save_checkpoint(a.save, sampler)
         if replay is not None:
             acc += replay()
             if (it + 1) % every == 0:
@@ -108,13 +120,15 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     r.check_errors()
+    if a.save:
+        t.save_checkpoint(a.save, sampler)
     psnr1 = view_psnr(held_out)
     psnr_train = view_psnr(1)
     u1 = udf_on_off()
     print(json.dumps({
         "what": "training loop of runner_udf.py on a synthetic wire frame (13 segments, %d views %dx%d, view %d held out), HIP path only"
                 % (a.views, a.res, a.res, held_out),
-        "graph": bool(a.graph), "steps": a.steps, "rays_per_step": a.rays, "precision": a.precision, "wall_s": wall, "ms_per_step_incl_python": wall / a.steps * 1e3,
+        "graph": bool(a.graph), "steps": a.steps, "rays_per_step": a.rays, "precision": a.precision, "wall_s": wall, "ms_per_step_incl_python": wall / max(a.steps - first, 1) * 1e3, "first_step": first,
         "held_out_view_psnr_db": {"before": psnr0[0], "after": psnr1[0]}, "train_view_psnr_db_after": psnr_train[0],
         "mean_udf_on_wireframe": {"before": u0[0], "after": u1[0]}, "mean_udf_away_from_it": {"before": u0[1], "after": u1[1]},
         "variance": float(devn.variance), "beta": float(bet.beta), "gamma": float(bet.gamma),
