@@ -9,6 +9,7 @@ from .udf_model import UDFNetwork, SingleVarianceNetwork, BetaNetwork, Rendering
 from .udf_renderer_blending import UDFRendererBlending, sample_pdf  # noqa: F401
 from .ray_sampler import DeviceRaySampler  # noqa: F401
 from .schedule import TrainSchedule  # noqa: F401
+from .monitor import TrainMonitor  # noqa: F401
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
-           "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule"]
+           "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor"]

@@ -33,6 +33,15 @@ RENDER_UNBIASED = 0
 RENDER_UNBIASED_NORMCOS = 1
 RENDER_PLAIN = 2
 
+# the record of emap_train_monitor (EMAP_MON_* of include/emap_hip.h): float64 fields at fixed indices - the first MON_ROW of them are the
+# per-step fields (one ring row), the rest the running ones
+MON_NAMES = ("iter_step", "loss", "edge_loss", "eikonal_loss", "eikonal_ns_loss", "psnr", "variance", "beta", "gamma", "udf_min", "udf_mean",
+             "weight_sum", "lr_geo", "lr", "cos_anneal_ratio", "flip_saturation",
+             "steps", "window_n", "window_sum", "loss_avg", "windows", "nonfinite_steps", "first_nonfinite_iter")
+MON_ROW = 16
+MON_FIELDS = len(MON_NAMES)
+MON = {k: i for i, k in enumerate(MON_NAMES)}
+
 F_NAN_SAMPLES = 1
 F_NAN_GRADERR = 2
 F_MLP_NONFINITE = 4
@@ -144,6 +153,9 @@ SYMBOLS = {
     "emap_render_bwd_staged_sched": (_RC, [C.POINTER(NetConfig), _P, C.c_int, C.POINTER(RenderParams), _P, _P, _P, _P, _P, _P, _P,
                                                C.POINTER(CompositeGrads), C.POINTER(ParamGrads), _P, C.c_size_t, _P, _P, C.c_int, _P]),
     "emap_adam_step_masked_sched": (_RC, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_double, C.c_double, C.c_float, _P, _P, _P]),
+    "emap_train_monitor_workspace_bytes": (_RC, [C.c_int, C.POINTER(C.c_size_t)]),
+    "emap_train_monitor": (_RC, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_int64, C.c_int, C.c_int,
+                                     _P, _P, _P, _P, C.c_size_t, _P]),
     "emap_ar_local_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
     "emap_ar_alloc": (_RC, [C.c_size_t, C.POINTER(C.c_void_p), _P]),
     "emap_ar_open": (_RC, [_P, C.POINTER(C.c_void_p)]),

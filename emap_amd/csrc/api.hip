@@ -702,6 +702,18 @@ int emap_train_schedule(int64_t* iter_dev, int64_t end_iter, double warm_up_end,
     return launch_train_schedule(iter_dev, end_iter, warm_up_end, fix_geo_end, anneal_end, learning_rate, learning_rate_geo, learning_rate_alpha,
                                  same_lr, flip_start, flip_saturation_max, sched_dev, static_cast<hipStream_t>(stream));
 }
+int emap_train_monitor_workspace_bytes(int N, size_t* bytes) {
+    if (!bytes) { set_error("train_monitor_workspace_bytes: bytes is null"); return EMAP_E_INVALID; }
+    if (N <= 0) { set_error("train_monitor_workspace_bytes: N must be > 0 (got %d)", N); return EMAP_E_INVALID; }
+    *bytes = train_monitor_workspace_bytes(N);
+    return EMAP_OK;
+}
+int emap_train_monitor(const float* udf, const float* weight_sum, int N, int S, const float* stats5, const float* scalars, const float* sched_dev,
+                       const int64_t* iter_dev, float w_over_n, float igr_weight, float igr_ns_weight, int64_t n_glob, int window, int history_rows,
+                       double* record, double* ring, float* loss_out2, void* workspace, size_t workspace_bytes, void* stream) {
+    return launch_train_monitor(udf, weight_sum, N, S, stats5, scalars, sched_dev, iter_dev, w_over_n, igr_weight, igr_ns_weight, n_glob, window,
+                                history_rows, record, ring, loss_out2, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
 
 int emap_null_direction(const float* grads, int64_t n, int k, float* dir, void* stream) {
     if (n < 0) { set_error("null_direction: negative n"); return EMAP_E_INVALID; }

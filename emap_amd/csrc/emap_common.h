@@ -353,6 +353,11 @@ int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64
 int launch_train_schedule(int64_t* iter, int64_t end_iter, double warm_up_end, double fix_geo_end, double anneal_end, double learning_rate,
                           double learning_rate_geo, double learning_rate_alpha, int same_lr, int64_t flip_start, double flip_saturation_max,
                           float* sched, hipStream_t st);
+// the training monitor: one launch; its finishing workgroup also writes launch_train_loss's two numbers to loss_out (may be null)
+size_t train_monitor_workspace_bytes(int N);
+int launch_train_monitor(const float* udf, const float* weight_sum, int N, int S, const float* stats, const float* scalars, const float* sched,
+                         const int64_t* iter, float w_over_n, float igr, float igr_ns, int64_t n_glob, int window, int history_rows, double* record,
+                         double* ring, float* loss_out, void* workspace, size_t workspace_bytes, hipStream_t st);
 // wgrad.hip: the training backward's weight-gradient GEMMs
 WgradPlan plan_wgrad(const NetLayout& L, const VjpLayout& V, int wg_budget);
 int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hipStream_t st);

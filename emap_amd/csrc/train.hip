@@ -9,6 +9,9 @@
 //                        parameter / gradient buffers; the step counter is a device word (graph-capturable)
 //   train_schedule_kernel : the four numbers the runner changes every iteration (runner_base.py:128-180) from a device iteration counter,
 //                        so that a captured step follows the schedules: the *_sched entry points read them from device memory
+//   train_monitor_kernel : what the runner reports about a step (runner_udf.py:110-134, :172-237) and its 500-iteration loss_avg (:135,
+//                        :239-241) as one record of doubles plus a history ring; its finishing workgroup writes train_loss_kernel's two
+//                        numbers as well, so a monitored step has as many launches as an unmonitored one
 #include "emap_common.h"
 #include <type_traits>
 
@@ -34,10 +37,18 @@ __global__ __launch_bounds__(256) void train_stats_kernel(const float* edge, con
     }
 }
 
+// [loss, edge_loss]: the ONE statement of the expression - train_loss_kernel and the monitor's finishing thread both store its two results.
+// Every rounding is spelled out, so that the two kernels agree bit for bit by construction and not by what the compiler chooses to contract:
+// contraction is off, and the one fused multiply-add is written - loss = fma(stats[4], w_over_n, ge) + ge_ns, the form this expression has
+// always been compiled to (edge_loss itself is the rounded product).
+__device__ __forceinline__ void train_loss_pair(const float* stats, float w_over_n, float igr, float igr_ns, float* out) {
+#pragma clang fp contract(off)
+    const float ge = igr * stats[2] / (stats[0] + 1e-5f), ge_ns = igr_ns * stats[3] / (stats[1] + 1e-5f);
+    out[0] = __builtin_fmaf(stats[4], w_over_n, ge) + ge_ns;
+    out[1] = stats[4] * w_over_n;
+}
 __global__ void train_loss_kernel(const float* stats, float w_over_n, float igr, float igr_ns, float* out) {
-    const float edge_loss = stats[4] * w_over_n;
-    out[0] = edge_loss + igr * stats[2] / (stats[0] + 1e-5f) + igr_ns * stats[3] / (stats[1] + 1e-5f);
-    out[1] = edge_loss;
+    train_loss_pair(stats, w_over_n, igr, igr_ns, out);
 }
 
 // torch.optim.Adam (amsgrad=False, weight_decay=0, maximize=False), the arithmetic of torch's fused kernel:
@@ -139,6 +150,106 @@ __global__ void train_schedule_kernel(long long* iter, long long end_iter, doubl
     *iter = it_i + 1;
 }
 
+
+// ---- the training monitor (include/emap_hip.h "training monitor") -------------------------------------------------------------------
+// A wave per ray, MON_WAVES rays per workgroup pass, at most MON_MAX_WG workgroups striding the rays: lanes stride the S samples of a ray
+// (fp32 minimum, exact; the sum in double), the waves of a workgroup add their rays up in double in a fixed order, thread 0 stores the
+// workgroup's three partial sums [sum of per-ray minima, sum of udf, sum of weight_sum] and draws a ticket.  The grid is a function of N
+// alone and no floating-point atomic is involved: the result is the same bits on every run.
+// No workgroup waits for another: the one that draws the last ticket finishes - it adds the partials in index order, forms the record and
+// the ring row, and clears the ticket for the next launch.  Publication is thread 0's alone: its plain stores, ONE agent-scope release
+// before the ticket add, and in the finisher ONE agent-scope acquire after it (relaxed atomics alone would order nothing between the
+// partial stores of one workgroup and the finisher's loads of them: ADVICE r6, second finding).
+constexpr int MON_WAVES = 4;
+constexpr int MON_MAX_WG = 64;
+constexpr int MON_PART = 3;
+constexpr size_t MON_HDR = 64;        // workspace: [0, 4) the ticket, [MON_HDR, ...) MON_PART doubles per workgroup
+static int mon_grid(int N) { const int g = N / MON_WAVES + (N % MON_WAVES != 0); return g < MON_MAX_WG ? g : MON_MAX_WG; }
+size_t train_monitor_workspace_bytes(int N) { return MON_HDR + (size_t)mon_grid(N) * MON_PART * sizeof(double); }
+
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }      // torch.min: a NaN wins
+
+__global__ __launch_bounds__(64 * MON_WAVES) void train_monitor_kernel(
+    const float* udf, const float* weight_sum, int N, int S, const float* stats, const float* scalars, const float* sched, const long long* iter,
+    float w_over_n, float igr, float igr_ns, long long n_glob, int window, int history_rows, double* rec, double* ring, float* loss_out,
+    unsigned* ticket, double* part) {
+    __shared__ double red[MON_WAVES][MON_PART];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double s_min = 0.0, s_udf = 0.0, s_ws = 0.0;
+    for (long long r = blockIdx.x * MON_WAVES + wave; r < N; r += gridDim.x * MON_WAVES) {
+        const float* u = udf + (size_t)r * S;
+        float m = INFINITY;
+        double a = 0.0;
+        for (int s = lane; s < S; s += 64) { const float x = u[s]; m = nan_min(m, x); a += (double)x; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { m = nan_min(m, __shfl_xor(m, off)); a += __shfl_xor(a, off); }
+        s_min += (double)m; s_udf += a; s_ws += (double)weight_sum[r];
+    }
+    if (lane == 0) { red[wave][0] = s_min; red[wave][1] = s_udf; red[wave][2] = s_ws; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < MON_PART; ++k) {
+        double p = red[0][k];
+        for (int w = 1; w < MON_WAVES; ++w) p += red[w][k];
+        part[blockIdx.x * MON_PART + k] = p;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gridDim.x - 1) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    double t[MON_PART] = {0.0, 0.0, 0.0};
+    for (unsigned b = 0; b < gridDim.x; ++b)
+        for (int k = 0; k < MON_PART; ++k) t[k] += part[b * MON_PART + k];
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // the next launch is behind this one in stream order
+
+    float le[2];
+    train_loss_pair(stats, w_over_n, igr, igr_ns, le);
+    if (loss_out) { loss_out[0] = le[0]; loss_out[1] = le[1]; }
+    const long long it = *iter;                                                       // runner_udf.py:170 has happened (emap_train_schedule)
+    const double n = (double)N;
+    double row[EMAP_MON_ROW];
+    row[EMAP_MON_ITER_STEP] = (double)it;
+    row[EMAP_MON_LOSS] = (double)le[0];                                               // :158-162
+    row[EMAP_MON_EDGE_LOSS] = (double)le[1];                                          // :124-130
+    row[EMAP_MON_EIKONAL_LOSS] = (double)igr * (double)stats[2] / ((double)stats[0] + 1e-5);        // :174-178
+    row[EMAP_MON_EIKONAL_NS_LOSS] = (double)igr_ns * (double)stats[3] / ((double)stats[1] + 1e-5);  // :179-183
+    row[EMAP_MON_PSNR] = 20.0 * log10(1.0 / sqrt((double)stats[4] / ((double)n_glob + 1e-5)));      // :92-94, :132-134 (mask of ones)
+    row[EMAP_MON_VARIANCE] = (double)scalars[8];                                      // :114-116, :184-185
+    row[EMAP_MON_BETA] = (double)scalars[9];
+    row[EMAP_MON_GAMMA] = (double)scalars[10];
+    row[EMAP_MON_UDF_MIN] = t[0] / n;                                                 // :122
+    row[EMAP_MON_UDF_MEAN] = t[1] / (n * (double)S);                                  // :229
+    row[EMAP_MON_WEIGHT_SUM] = t[2] / (n + 1e-5);                                     // :226-227
+    row[EMAP_MON_LR_GEO] = (double)sched[0];                                          // :206-212
+    row[EMAP_MON_LR] = (double)sched[1];
+    row[EMAP_MON_COS_ANNEAL_RATIO] = (double)sched[2];
+    row[EMAP_MON_FLIP_SATURATION] = (double)sched[3];
+    // the running fields; a record whose `steps` is 0 is an empty one whatever else it holds
+    const bool fresh = !(rec[EMAP_MON_STEPS] > 0.0);
+    double win_n = fresh ? 0.0 : rec[EMAP_MON_WINDOW_N], win_sum = fresh ? 0.0 : rec[EMAP_MON_WINDOW_SUM];
+    double loss_avg = fresh ? (double)NAN : rec[EMAP_MON_LOSS_AVG], windows = fresh ? 0.0 : rec[EMAP_MON_WINDOWS];
+    double nonfinite = fresh ? 0.0 : rec[EMAP_MON_NONFINITE_STEPS], first_bad = fresh ? -1.0 : rec[EMAP_MON_FIRST_NONFINITE_ITER];
+    const double steps = fresh ? 1.0 : rec[EMAP_MON_STEPS] + 1.0;
+    win_n += 1.0; win_sum += (double)le[1];                                           // :135 loss_list.append(edge_loss)
+    if (it > 0 && it % window == 0) {                                                 // :239-241
+        loss_avg = win_sum / win_n; windows += 1.0; win_n = 0.0; win_sum = 0.0;
+    }
+    if (!isfinite(le[0])) {
+        if (nonfinite == 0.0) first_bad = (double)it;
+        nonfinite += 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < EMAP_MON_ROW; ++k) rec[k] = row[k];
+    rec[EMAP_MON_STEPS] = steps; rec[EMAP_MON_WINDOW_N] = win_n; rec[EMAP_MON_WINDOW_SUM] = win_sum; rec[EMAP_MON_LOSS_AVG] = loss_avg;
+    rec[EMAP_MON_WINDOWS] = windows; rec[EMAP_MON_NONFINITE_STEPS] = nonfinite; rec[EMAP_MON_FIRST_NONFINITE_ITER] = first_bad;
+    if (history_rows > 0) {
+        long long slot = (it - 1) % history_rows;
+        if (slot < 0) slot += history_rows;
+        double* dst = ring + slot * EMAP_MON_ROW;
+#pragma unroll
+        for (int k = 0; k < EMAP_MON_ROW; ++k) dst[k] = row[k];
+    }
+}
+
 int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
                        hipStream_t st) {
     if (!edge || !true_edge || !scalars || !stats || N < 0) { set_error("train_stats: null pointer"); return EMAP_E_INVALID; }
@@ -182,6 +293,29 @@ int launch_train_schedule(int64_t* iter, int64_t end_iter, double warm_up_end, d
                        fix_geo_end, anneal_end, learning_rate, learning_rate_geo, learning_rate_alpha, same_lr, (long long)flip_start,
                        flip_saturation_max, sched);
     return check_launch("train_schedule");
+}
+
+int launch_train_monitor(const float* udf, const float* weight_sum, int N, int S, const float* stats, const float* scalars, const float* sched,
+                         const int64_t* iter, float w_over_n, float igr, float igr_ns, int64_t n_glob, int window, int history_rows, double* record,
+                         double* ring, float* loss_out, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const struct { const void* p; const char* name; } ptrs[] = {{udf, "udf"}, {weight_sum, "weight_sum"}, {stats, "stats5"}, {scalars, "scalars"},
+        {sched, "sched_dev"}, {iter, "iter_dev"}, {record, "record"}, {workspace, "workspace"}};
+    for (const auto& a : ptrs)
+        if (!a.p) { set_error("train_monitor: %s is null", a.name); return EMAP_E_INVALID; }
+    if (N <= 0) { set_error("train_monitor: N must be > 0 (got %d)", N); return EMAP_E_INVALID; }
+    if (S <= 0) { set_error("train_monitor: S must be > 0 (got %d)", S); return EMAP_E_INVALID; }
+    if (n_glob <= 0) { set_error("train_monitor: n_glob must be > 0 (got %lld)", (long long)n_glob); return EMAP_E_INVALID; }
+    if (window <= 0) { set_error("train_monitor: window must be > 0 (got %d)", window); return EMAP_E_INVALID; }
+    if (history_rows < 0) { set_error("train_monitor: history_rows must be >= 0 (got %d)", history_rows); return EMAP_E_INVALID; }
+    if (history_rows > 0 && !ring) { set_error("train_monitor: ring is null with history_rows = %d", history_rows); return EMAP_E_INVALID; }
+    const size_t need = train_monitor_workspace_bytes(N);
+    if (workspace_bytes < need) { set_error("train_monitor: workspace %zu < %zu bytes (emap_train_monitor_workspace_bytes)", workspace_bytes, need); return EMAP_E_WORKSPACE; }
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) { set_error("train_monitor: workspace must be 8-byte aligned"); return EMAP_E_INVALID; }
+    char* ws = static_cast<char*>(workspace);
+    hipLaunchKernelGGL(train_monitor_kernel, dim3(mon_grid(N)), dim3(64 * MON_WAVES), 0, st, udf, weight_sum, N, S, stats, scalars, sched,
+                       reinterpret_cast<const long long*>(iter), w_over_n, igr, igr_ns, (long long)n_glob, window, history_rows, record, ring, loss_out,
+                       reinterpret_cast<unsigned*>(ws), reinterpret_cast<double*>(ws + MON_HDR));
+    return check_launch("train_monitor");
 }
 
 }  // namespace emap

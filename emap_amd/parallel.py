@@ -30,6 +30,10 @@ evaluates them from a device iteration counter, and the render, the backward and
 then follows the schedules, and with ``capture(sampler=...)`` the ray draw is in the graph too: one replay is one whole iteration of
 runner_udf.py:63-170 with no per-step host work.
 
+``Trainer(..., monitor=TrainMonitor(...))`` (emap_amd/monitor.py) also keeps what the runner reports about an iteration and its
+500-iteration loss average (runner_udf.py:110-135, :172-244) on the device - one launch at the end of the step, in place of
+emap_train_loss - and ``fit()`` drives a loop with the runner's report / save-best / validate cadence on top of it.
+
 ``Trainer.state_dict / load_state_dict`` (``save_checkpoint / load_checkpoint``) write and read the reference's checkpoint
 (runner_udf.py:252-275: the three modules, the optimizer in torch.optim.Adam's layout, iter_step) plus one ``emap_native`` entry; a
 load writes every buffer in place, so a captured step goes on from it.
@@ -288,10 +292,20 @@ class Trainer:
 
     def __init__(self, renderer, lr_geo: float = 1e-4, lr: float = 5e-4, edge_weight: float = 1.0, igr_weight: float = 0.1,
                  igr_ns_weight: float = 0.0, group=None, eikonal_sync: str = "exact", fused_adam: Optional[bool] = None,
-                 native_tail: Optional[bool] = None, allreduce: str = "rccl", schedule=None, start_iter: int = 0):
+                 native_tail: Optional[bool] = None, allreduce: str = "rccl", schedule=None, start_iter: int = 0, monitor=None):
         """schedule (emap_amd.TrainSchedule; None: nothing changes): the step evaluates the reference's per-iteration schedules on the
         device from its own iteration counter, which starts at `start_iter` (see iter_step / set_iter_step).  Then
-        ``optimizer.param_groups[*]["lr"]`` are not read, and ``rays`` must not carry cos_anneal_ratio / flip_saturation."""
+        ``optimizer.param_groups[*]["lr"]`` are not read, and ``rays`` must not carry cos_anneal_ratio / flip_saturation.
+
+        monitor (emap_amd.TrainMonitor; None: nothing new is enqueued): every step ends with emap_train_monitor, which writes the
+        runner's per-iteration quantities and its running loss average into the monitor's device buffers and the step's
+        [loss, edge_loss] with them.  Needs `schedule`: the monitor reads the iteration counter and the learning rates from it.
+        On several ranks loss / edge_loss / psnr / the eikonal terms are the global batch's, udf_min / udf_mean / weight_sum the
+        rank's own rays'.  Checkpoints do not carry the monitor.  (``native_tail=False``, the CPU tests: the eager step evaluates the
+        schedule on the host, TrainSchedule.values, and feeds the monitor through TrainMonitor.update_host.)"""
+        if monitor is not None and schedule is None:
+            raise ValueError("Trainer: monitor= needs schedule= (the monitor takes the iteration number and the learning rates from the "
+                             "schedule's device words; without a schedule the trainer has neither)")
         assert eikonal_sync in ("exact", "exact_lagged", "local")
         # only "exact_lagged" uses the rank-indexed maxima slots of the bucket's tail: "exact" / "local" run on any number of ranks
         assert eikonal_sync != "exact_lagged" or _world(group) <= self.MAX_RANKS, \
@@ -363,6 +377,9 @@ class Trainer:
                 raise ValueError(f"Trainer: start_iter must be >= 0 (got {start_iter})")
             self._iter = torch.full((1,), int(start_iter), dtype=torch.int64, device=dev)
             self._sched = torch.zeros(4, device=dev)
+        self.monitor = monitor
+        if monitor is not None:
+            monitor.bind(dev)
 
     # ---- the scheduled step (schedule=TrainSchedule(...)) ----
     @property
@@ -374,20 +391,24 @@ class Trainer:
 
     def set_iter_step(self, k: int):
         """Write the device iteration counter (resuming from a checkpoint's iter_step).  A captured graph reads the buffer, so a write
-        between replays takes effect without re-capturing."""
+        between replays takes effect without re-capturing.  A monitor is reset(): its window and its rows belong to the iterations before."""
         if self._iter is None:
             raise RuntimeError("Trainer.set_iter_step: this trainer has no schedule")
         if int(k) < 0:
             raise ValueError(f"Trainer.set_iter_step: the iteration must be >= 0 (got {k})")
         self._iter.fill_(int(k))
+        if self.monitor is not None:
+            self.monitor.reset()
 
-    def _check_scheduled(self, rays):
-        """The scheduled step has ONE source for the two render scalars - the device schedule - and runs on the native tail only."""
+    def _check_scheduled(self, rays, capturing: bool = False):
+        """The scheduled step has ONE source for the two render scalars - the device schedule - and runs on the native tail only.  (The
+        one exception is the monitored torch tail of the CPU tests, whose eager step evaluates the schedule on the host: the monitor
+        needs the iteration number and the learning rates from somewhere.)"""
         for k in ("cos_anneal_ratio", "flip_saturation"):
             if k in rays:
                 raise ValueError(f"Trainer: rays['{k}'] given to a trainer with a schedule - the schedule on the device is the only source "
                                  "of cos_anneal_ratio / flip_saturation")
-        if not self.native_tail:
+        if not self.native_tail and (capturing or self.monitor is None):
             raise RuntimeError("Trainer: schedule= needs the native tail (emap_train_schedule and the *_sched entry points are HIP kernels; "
                                "there is no CPU fallback)")
 
@@ -541,8 +562,13 @@ class Trainer:
         self.r.udf_network.invalidate_packed()   # the flat update does not bump the per-parameter version counters
         stats = self._stats_slot() if S.sync == "local" else self._stats      # "local": the all-reduced bucket's tail holds the global sums
         out = torch.empty(2, device=dev)         # a fresh tensor per step: callers keep what step() returned
-        with torch.cuda.device(dev):
-            _lib.api().train_loss(stats, self.edge_weight / S.n_glob, self.igr_weight, self.igr_ns_weight, out, _lib.stream_ptr(dev))
+        weights = (self.edge_weight / S.n_glob, self.igr_weight, self.igr_ns_weight)
+        if self.monitor is None:
+            with torch.cuda.device(dev):
+                _lib.api().train_loss(stats, *weights, out, _lib.stream_ptr(dev))
+        else:                                    # the same two numbers, and the runner's report of this iteration (runner_udf.py:110-135, :172-241)
+            self.monitor.launch(S.v["udf"], S.v["weight_sum"], S.call["N"], S.call["S"], stats, S.scalars, self._sched, self._iter, *weights,
+                                S.n_glob, out)
         self.last_stats = out
         return out
 
@@ -576,6 +602,11 @@ class Trainer:
             self.refresh_trainable_mask()
             return self._step_native(rays, true_edge, n_rays_global)
         # the torch tail (the CPU tests): the native phases' arithmetic in element-wise torch ops, torch.optim.Adam, collectives in line
+        if self._sched is not None:      # (monitored: _check_scheduled) emap_train_schedule on the host: the four numbers, then the counter moves on
+            vals = self.schedule.values(int(self._iter.item()))
+            self._sched.copy_(torch.tensor(vals, dtype=torch.float32))
+            self.optimizer.param_groups[0]["lr"], self.optimizer.param_groups[1]["lr"] = vals[0], vals[1]
+            self._iter += 1
         sync = self._sync()
         call, v, edge, scalars = self._forward(rays)
         n_local = edge.numel()
@@ -611,12 +642,15 @@ class Trainer:
                     st[k][frozen] = 0.0
         self.r.udf_network.invalidate_packed()   # the flat update does not bump the per-parameter version counters
         self.last_stats = torch.stack(_loss_from_stats(stats, n_glob, self.edge_weight, self.igr_weight, self.igr_ns_weight))
+        if self.monitor is not None:
+            self.monitor.update_host(v["udf"].reshape(n_local, -1), v["weight_sum"], stats, scalars, self._sched, int(self._iter.item()),
+                                     self.edge_weight / n_glob, self.igr_weight, self.igr_ns_weight, n_glob, loss_pair=self.last_stats)
         return self.last_stats
 
     def _train_state(self):
         """Every device buffer a step changes besides its outputs (capture() with a schedule rolls its warm-up steps back)."""
         a = self._adam
-        return [self.flat.data, a.m, a.v, a.t, a.spare_t, a.tail_step, self._lag, self._iter]
+        return [self.flat.data, a.m, a.v, a.t, a.spare_t, a.tail_step, self._lag, self._iter] + (self.monitor.buffers() if self.monitor else [])
 
     def _sampled_step(self, batch, n_rays_global=None):
         """step() on a batch the first phase draws itself (`batch`: -> (rays, true_edge)), after the schedule launch"""
@@ -638,6 +672,8 @@ class Trainer:
         With a schedule the captured step begins with emap_train_schedule and follows the schedules from the device iteration counter.
         The warm-up steps (and the step a segmented capture takes) are then ROLLED BACK: parameters, Adam state and the counters are
         what they were before the call, so the first replay is iteration iter_step, exactly as the first eager step() would have been.
+        A monitor is rolled back with them: after capture() it holds what it held before (steps == 0 for a new one) and the first
+        replay writes the row of iteration iter_step + 1.
 
         `sampler` (a DeviceRaySampler with near / far; `batch_size` rays, `importance_sample` as runner_udf.py:71-75) in place of
         `rays` / `true_edge`, with a schedule: the sampler's launch - pixel draw, rays, true_edge, t_rand, image
@@ -656,7 +692,7 @@ class Trainer:
         elif rays is None or true_edge is None:
             raise ValueError("Trainer.capture: rays and true_edge (or sampler=) must be given")
         if self._sched is not None:
-            self._check_scheduled(rays or {})
+            self._check_scheduled(rays or {}, capturing=True)
         if not self.native_tail:
             if segmented:
                 raise ValueError("Trainer.capture(segmented=True) needs the native tail (native_tail=True): the per-phase graphs are the "
@@ -676,7 +712,7 @@ class Trainer:
         saved = None
         if self._sched is not None:      # the warm-up is rolled back (see above)
             saved = [(t, t.clone()) for t in self._train_state() + ([sampler._counter] if sampler is not None else [])]
-            lag_valid = self._lag_valid
+            lag_valid, mon_host = self._lag_valid, self.monitor.host_state() if self.monitor is not None else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -707,6 +743,8 @@ class Trainer:
             for t, was in saved:
                 t.copy_(was)
             self._lag_valid = lag_valid
+            if self.monitor is not None:
+                self.monitor.set_host_state(mon_host)
             self.r.udf_network.invalidate_packed()
 
         def replay(rays: Optional[Dict] = None, true_edge: Optional[torch.Tensor] = None):
@@ -884,7 +922,7 @@ class Trainer:
         every buffer as it was.  Then every buffer is written IN PLACE - parameters through the modules' own load_state_dict (the views of
         the flat buffer survive), the moments and step counts, the schedule counter, the lagged maxima, the sampler's counter and list -
         so a replay captured before the load goes on from the loaded state without re-capture, and a capture after it rolls its warm-up
-        back onto the loaded state.  Without a schedule the group learning rates (betas, eps) are restored as torch restores them; with
+        back onto the loaded state.  A monitor is reset() (checkpoints do not carry it).  Without a schedule the group learning rates (betas, eps) are restored as torch restores them; with
         one the schedule is their only source."""
         m, v, t_geo, tail, lag, lag_valid, groups, smp = self._check_ckpt(ckpt, sampler)
         for k, mod in self._ckpt_modules().items():
@@ -920,6 +958,8 @@ class Trainer:
                 sampler.load_state_dict(smp)
             else:
                 sampler._counter.fill_(int(ckpt["iter_step"]))
+        if self.monitor is not None:     # checkpoints do not carry it: a resumed reference run starts with an empty loss_list too (runner_udf.py:53-54)
+            self.monitor.reset()
         self.r.udf_network.invalidate_packed()
 
     def save_checkpoint(self, path, sampler=None):
@@ -934,6 +974,59 @@ class Trainer:
         ckpt = torch.load(path, map_location=self.flat.data.device)
         self.load_state_dict(ckpt, sampler)
         return ckpt
+
+
+class FitReports(list):
+    """What fit() returns: the reports it handed to `on_report`, in order; ``best_loss`` after the last iteration and ``saved``, the
+    iterations at which the best checkpoint was written."""
+    best_loss = 1.0
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.saved = []
+
+
+def fit(trainer, step, n_steps: int, monitor, report_freq: int = 1000, save_freq: int = 1000, val_freq: int = 0, best_path=None, sampler=None,
+        on_report=None, on_validate=None, best_loss: float = 1.0) -> FitReports:
+    """The cadence of the reference's loop (runner_udf.py:188-247) around `n_steps` calls of ``step()`` - a replay of
+    ``trainer.capture(sampler=...)`` or any callable that takes one iteration of a trainer built with ``monitor=monitor``.
+
+      every `report_freq` iterations (:188)   ONE ``monitor.read_rows()`` - record and unread rows from one device-to-host copy - and
+                                              ``trainer.check_errors()``; the report
+                                              ``{"iter_step", "record", "rows", "best_loss"}`` is appended to the result and handed
+                                              to `on_report`
+      iter_step % save_freq == 0 (:243-244)   if a loss window has closed and ``loss_avg < best_loss``: ``best_loss = loss_avg`` and
+                                              ``trainer.save_checkpoint(best_path, sampler)`` - save_checkpoint's rule (:277-285).  The
+                                              reference raises NameError at a save point before the first window closes; here that
+                                              point is skipped.  Uses the report's record when the iteration has one, else one read().
+      every `val_freq` iterations (:246)      ``on_validate(iter_step)``
+
+    A frequency of 0 (or `best_path` None for the save rule) turns its line off.  There is no other host read: the iteration numbers
+    are counted on the host from ``trainer.iter_step``, read once before the first step.  `best_loss` starts at the reference's 1.0
+    (:54), or at what a previous call returned.  On several ranks every rank calls fit() with the same arguments (the record's loss
+    fields are the global batch's, so all ranks decide alike; save_checkpoint writes on rank 0)."""
+    it = trainer.iter_step
+    reports = FitReports()
+    reports.best_loss = float(best_loss)
+    for _ in range(int(n_steps)):
+        step()
+        it += 1
+        rec = None
+        if report_freq > 0 and it % report_freq == 0:
+            rec, rows = monitor.read_rows()
+            trainer.check_errors()
+            reports.append({"iter_step": it, "record": rec, "rows": rows, "best_loss": reports.best_loss})
+            if on_report is not None:
+                on_report(reports[-1])
+        if save_freq > 0 and best_path is not None and it % save_freq == 0:
+            rec = monitor.read() if rec is None else rec
+            if rec["windows"] > 0 and rec["loss_avg"] < reports.best_loss:
+                reports.best_loss = rec["loss_avg"]
+                trainer.save_checkpoint(best_path, sampler)
+                reports.saved.append(it)
+        if val_freq > 0 and on_validate is not None and it % val_freq == 0:
+            on_validate(it)
+    return reports
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -456,6 +456,58 @@ int emap_adam_step_masked_sched(float* params, const float* grads, float* exp_av
                                 const float* lr_dev, double beta1, double beta2, float eps, const float* tail_mask, float* tail_step,
                                 void* stream);
 
+/* ---- training monitor (src/runner/runner_udf.py:110-135, :172-244) -------------------------------------------------------------
+ * Added functions only (no struct or signature of ABI 12 changes).
+ * What the runner reports about an iteration - the quantities of :110-134, the tensorboard rows of :172-186, the report text of :188-237 -
+ * and the 500-iteration loss_avg its ckpt_best rule is built on (:135, :239-244), kept on the device so that a captured step needs no host
+ * read per iteration: ONE launch after the update, one device-to-host copy of `record` whenever the loop wants to report.
+ * emap_train_monitor : inputs on the device: udf (N, S) and weight_sum (N) of the step's forward, stats5 (emap_train_stats' five numbers,
+ *                      globally summed where the step sums them), scalars (the forward's), sched_dev (emap_train_schedule's four floats),
+ *                      iter_dev (int64, ALREADY incremented by emap_train_schedule: the reference's iter_step after :170).  By value:
+ *                      w_over_n / igr_weight / igr_ns_weight as emap_train_loss takes them, n_glob (rays of the global batch), window (500 in
+ *                      the reference), history_rows.  Outputs:
+ *                        record : EMAP_MON_FIELDS doubles.  [0, EMAP_MON_ROW) the per-step fields, every sum taken in double and every
+ *                                 result rounded once:
+ *                                   ITER_STEP        *iter_dev                                                             :170
+ *                                   LOSS, EDGE_LOSS  emap_train_loss's out2, bit for bit (fp32 values)                      :124-130, :158-162
+ *                                   EIKONAL_LOSS     igr_weight * stats5[2] / (stats5[0] + 1e-5)                           :174-178
+ *                                   EIKONAL_NS_LOSS  igr_ns_weight * stats5[3] / (stats5[1] + 1e-5)                        :179-183
+ *                                   PSNR             20 log10(1 / sqrt(stats5[4] / (n_glob + 1e-5)))   (the mask is ones)  :92-94, :132-134
+ *                                   VARIANCE, BETA, GAMMA   scalars[8], [9], [10]: the render dict's entries               :114-116, :184-185
+ *                                   UDF_MIN          mean over the rays of the per-ray minimum of udf (a NaN wins, as torch) :122
+ *                                   UDF_MEAN         mean of the N * S udf                                                  :229
+ *                                   WEIGHT_SUM       sum(weight_sum) / (N + 1e-5)   (weight_sum_fg_bg is the same tensor)  :226-227
+ *                                   LR_GEO, LR, COS_ANNEAL_RATIO, FLIP_SATURATION   sched_dev[0..3]                        :206-212, :237
+ *                                 then the running fields: STEPS (monitored steps), WINDOW_N / WINDOW_SUM (edge_loss is appended every
+ *                                 step, :135), LOSS_AVG (NaN until a window closes), WINDOWS (closed windows), NONFINITE_STEPS and
+ *                                 FIRST_NONFINITE_ITER (-1 until it happens): steps whose LOSS is not finite.  A window closes when
+ *                                 iter_step % window == 0 && iter_step > 0, after this step's append: LOSS_AVG = WINDOW_SUM / WINDOW_N and
+ *                                 both are cleared (:239-241).  A record with STEPS == 0 (a zeroed one) is an empty monitor.
+ *                        ring   : history_rows rows of EMAP_MON_ROW doubles; this step's per-step fields go to row
+ *                                 (iter_step - 1) % history_rows.  NULL with history_rows == 0.
+ *                        loss_out2 (may be NULL): [loss, edge_loss] exactly as emap_train_loss writes them - a monitored step calls this
+ *                                 INSTEAD of emap_train_loss and keeps its launch count.
+ *                      workspace: emap_train_monitor_workspace_bytes(N) bytes, 8-byte aligned, zeroed ONCE by the caller before the first
+ *                      call; every call leaves its ticket word zero again.  Several workgroups (a wave per ray); per-workgroup partial sums
+ *                      are added in index order by the workgroup that arrives last (one agent-scope release before its ticket, one acquire
+ *                      after it): no floating-point atomics, no workgroup waits for another, and the record is the same bits on every run.
+ *                      EMAP_E_INVALID before any launch, with the argument named in emap_last_error(): a NULL pointer, N <= 0, S <= 0,
+ *                      n_glob <= 0, window <= 0, history_rows < 0 (or > 0 without ring); EMAP_E_WORKSPACE: workspace_bytes too small.
+ * emap_train_monitor_workspace_bytes : host only. */
+enum {
+    EMAP_MON_ITER_STEP = 0, EMAP_MON_LOSS, EMAP_MON_EDGE_LOSS, EMAP_MON_EIKONAL_LOSS, EMAP_MON_EIKONAL_NS_LOSS, EMAP_MON_PSNR,
+    EMAP_MON_VARIANCE, EMAP_MON_BETA, EMAP_MON_GAMMA, EMAP_MON_UDF_MIN, EMAP_MON_UDF_MEAN, EMAP_MON_WEIGHT_SUM, EMAP_MON_LR_GEO,
+    EMAP_MON_LR, EMAP_MON_COS_ANNEAL_RATIO, EMAP_MON_FLIP_SATURATION,
+    EMAP_MON_ROW,                                   /* = 16: the per-step fields, one ring row */
+    EMAP_MON_STEPS = EMAP_MON_ROW, EMAP_MON_WINDOW_N, EMAP_MON_WINDOW_SUM, EMAP_MON_LOSS_AVG, EMAP_MON_WINDOWS, EMAP_MON_NONFINITE_STEPS,
+    EMAP_MON_FIRST_NONFINITE_ITER,
+    EMAP_MON_FIELDS                                 /* = 23 */
+};
+int emap_train_monitor_workspace_bytes(int N, size_t* bytes);
+int emap_train_monitor(const float* udf, const float* weight_sum, int N, int S, const float* stats5, const float* scalars, const float* sched_dev,
+                       const int64_t* iter_dev, float w_over_n, float igr_weight, float igr_ns_weight, int64_t n_glob, int window, int history_rows,
+                       double* record, double* ring, float* loss_out2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- dense-grid extraction (SURVEY par. 8 f2) ----------------------------------------------------
  * emap_null_direction : `_, _, vh = torch.linalg.svd(grad_ld); F.normalize(vh[:, -1, :])` of get_udf_normals_grid /
  *                       get_udf_normals_slow (src/edge_extraction/extract_pointcloud.py:86-88, 177-179): per point the unit

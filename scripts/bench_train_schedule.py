@@ -8,6 +8,7 @@ rounds so that drift of the shared host hits all of them alike:
   scheduled     captured step with the schedule on the device (capture(rays, true_edge), fixed rays)
   iteration     the same with the ray sampler inside the graph (capture(sampler=...)): one replay = one whole reference iteration
   reshuffle     `iteration` with sampler.set_train_images(): the image order is re-derived on the device at every epoch boundary
+  monitor       `iteration` with a TrainMonitor (Trainer(monitor=...)): the step ends with emap_train_monitor in place of emap_train_loss
   parent_iter   `iteration` on the checkout of the parent commit (`--parent-tree DIR`; skipped without it)
   by_value      captured step of THIS build with the four numbers baked in (schedule=None)
   parent        captured step of a checkout of the parent commit with its own library built (`--parent-tree DIR`; skipped without it)
@@ -27,8 +28,8 @@ import sys
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-VARIANTS = ("scheduled", "iteration", "reshuffle", "parent_iter", "by_value", "parent", "eager_host")
-ITERATION = ("iteration", "reshuffle", "parent_iter")
+VARIANTS = ("scheduled", "iteration", "reshuffle", "monitor", "parent_iter", "by_value", "parent", "eager_host")
+ITERATION = ("iteration", "reshuffle", "monitor", "parent_iter")
 IN_PARENT = ("parent", "parent_iter")
 
 
@@ -54,6 +55,8 @@ def worker(a):
     if a.worker in ("scheduled", "eager_host") + ITERATION:
         sched = emap_amd.TrainSchedule()          # ABC.conf: 50 000 iterations - the timed window stays in the warm-up branch
     on_device = {"schedule": sched} if a.worker in ("scheduled",) + ITERATION else {}      # (the parent's Trainer has no such argument)
+    if a.worker == "monitor":
+        on_device["monitor"] = emap_amd.TrainMonitor()
     tr = Trainer(r, lr_geo=1e-4, lr=5e-4, igr_weight=0.1, **on_device)
     smp = sampler.gen_random_rays_patches_at(None, N, importance_sample=True)
     rays = {"rays_o": smp["rays"]["rays_o"], "rays_d": smp["rays"]["rays_v"], "near": near, "far": far, "depth_scale": smp["depth_scale"],
@@ -90,6 +93,9 @@ def worker(a):
         ms.append((time.perf_counter() - t0) / a.steps * 1e3)
     tr.check_errors()
     assert bool(torch.isfinite(out).all())
+    if a.worker == "monitor":
+        rec = tr.monitor.read()
+        assert rec["steps"] == a.warmup + a.steps * a.repeats and rec["nonfinite_steps"] == 0, rec
     print(json.dumps({"variant": a.worker, "ms_per_step": statistics.median(ms), "repeats_ms": ms}))
 
 
@@ -132,7 +138,8 @@ def main():
     for v in variants:
         x = res[v]
         lines.append(f"{v:12s} {statistics.median(x):9.4f} {min(x):9.4f} {max(x):9.4f}   {' '.join('%.4f' % q for q in x)}")
-    for new, bases in (("scheduled", ("parent", "by_value")), ("reshuffle", ("parent_iter", "iteration"))):
+    for new, bases in (("scheduled", ("parent", "by_value")), ("reshuffle", ("parent_iter", "iteration")), ("iteration", ("parent_iter",)),
+                       ("monitor", ("parent_iter", "iteration"))):
         base = next((b for b in bases if b in res), None)
         if new not in res or base is None:
             continue

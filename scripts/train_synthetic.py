@@ -10,7 +10,13 @@ draw, not from torch.rand: the trajectory differs from the default run's in the 
 
 The training views (all but the held-out one) are walked in a new order every epoch (DeviceRaySampler.set_train_images).  `--save PATH`
 writes a checkpoint in the reference's layout at the end (`--save-every K`: also every K steps) and `--resume PATH` continues from one:
-the run goes on at the checkpoint's iteration, up to `--steps`."""
+the run goes on at the checkpoint's iteration, up to `--steps`.
+
+`--monitor` trains through emap_amd.parallel.fit with a TrainMonitor (schedules on the device; with `--graph` the captured loop, else
+eager steps on the sampler's batches): the host reads the device once per report, every trajectory entry of the JSON line carries the
+monitor's rows of ALL the iterations since the previous report ("rows", one list per iteration in the order of "monitor"."columns": loss,
+psnr, udf_min, weight_sum, variance / beta / gamma, the learning rates, ...) and `--best PATH` is written by the runner's
+ckpt_best rule (runner_udf.py:243-244, :277-285) on the monitor's 500-iteration loss average (`--window`)."""
 import argparse
 import json
 import math
@@ -39,6 +45,9 @@ def main():
     ap.add_argument("--save", metavar="PATH", help="write Trainer.save_checkpoint(PATH, sampler) at the end of the run")
     ap.add_argument("--save-every", type=int, default=0, metavar="K", help="with --save: also after every K steps")
     ap.add_argument("--resume", metavar="PATH", help="Trainer.load_checkpoint(PATH, sampler) before the first step")
+    ap.add_argument("--monitor", action="store_true", help="train through parallel.fit with a TrainMonitor: one host read per report")
+    ap.add_argument("--best", metavar="PATH", help="with --monitor: the checkpoint of the best window average of the edge loss")
+    ap.add_argument("--window", type=int, default=500, help="with --monitor: iterations per loss average (the reference's 500)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -59,7 +68,10 @@ def main():
     warm_up_end, anneal_end, flip_start = max(1, end_iter // 50), max(1, end_iter // 5), end_iter // 5
     sched = emap_amd.TrainSchedule(end_iter=end_iter, warm_up_end=warm_up_end, fix_geo_end=0, anneal_end=anneal_end, learning_rate=lr,
                                    learning_rate_geo=lr_geo, learning_rate_alpha=alpha, flip_start=flip_start)
-    t = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.0, schedule=sched if a.graph else None)
+    every = max(1, a.steps // 20)
+    mon = emap_amd.TrainMonitor(window=a.window, history=every) if a.monitor else None
+    t = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=1.0, igr_weight=0.1, igr_ns_weight=0.0, schedule=sched if a.graph or a.monitor else None,
+                monitor=mon)
     lr_factor, lr_geo_factor = sched.factor, sched.factor_geo      # runner_base.py:128-141, :143-160 (fix_geo_end = 0)
     first = 0
     if a.resume:                   # parameters, Adam state, the iteration and the sampler's counter (hence the image order), in place
@@ -90,10 +102,24 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     acc = torch.zeros(2, device=dev)
-    every = max(1, a.steps // 20)
     # --graph: schedules, ray draw and step are one hipGraph; the default: the schedules on the host, every step eager
     replay = t.capture(sampler=sampler, batch_size=a.rays, importance_sample=True) if a.graph else None
-    for it in range(first, a.steps):
+    fit_out = None
+    if mon is not None:            # the runner's cadence on the device monitor: report, save-best and (here: no) validation points
+        step = replay if replay is not None else (lambda: t.step(*Trainer.sampler_batch(sampler, a.rays, True)))
+
+        def on_report(rep):
+            rows, rec = rep["rows"], rep["record"]
+            mean = lambda k: float(rows[:, emap_amd.TrainMonitor.COLUMNS.index(k)].mean())
+            log.append({"step": rep["iter_step"], "loss": mean("loss"), "edge_loss": mean("edge_loss"),
+                        "psnr_batch": 10 * math.log10(1.0 / max(mean("edge_loss"), 1e-12)), "loss_avg": rec["loss_avg"],
+                        "best_loss": rep["best_loss"], "rows_dropped": int(rows.dropped), "rows": rows.tolist()})
+            if a.save and a.save_every > 0 and rep["iter_step"] % a.save_every == 0:
+                t.save_checkpoint(a.save, sampler)
+
+        fit_out = emap_amd.parallel.fit(t, step, a.steps - first, mon, report_freq=every, save_freq=every, best_path=a.best, sampler=sampler,
+                                        on_report=on_report)
+    for it in (range(first, a.steps) if mon is None else ()):
         if a.save and a.save_every > 0 and it > first and it % a.save_every == 0:
             t.save_checkpoint(a.save, sampler)
         if replay is not None:
@@ -132,6 +158,7 @@ def main():
         "held_out_view_psnr_db": {"before": psnr0[0], "after": psnr1[0]}, "train_view_psnr_db_after": psnr_train[0],
         "mean_udf_on_wireframe": {"before": u0[0], "after": u1[0]}, "mean_udf_away_from_it": {"before": u0[1], "after": u1[1]},
         "variance": float(devn.variance), "beta": float(bet.beta), "gamma": float(bet.gamma),
+        **({"monitor": {"columns": list(emap_amd.TrainMonitor.COLUMNS), "record": mon.read(), "best_loss": fit_out.best_loss, "best_saved_at": fit_out.saved}} if mon is not None else {}),
         "trajectory": log}))
 
 
