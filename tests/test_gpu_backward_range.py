@@ -25,9 +25,9 @@ Tolerances: TOL[prec] of tests/test_gpu_backward.py against the mirror (relative
 promises), 1e-6 where a power-of-two scaling must commute exactly, and ulp arguments stated at the assertion.  No bound in this file was
 taken from what the kernels returned.
 
-Left out: precision modes f16x3e and f16x3m.  TOL has no entry for them and the project states no bound for emap_udf_vjp against the
-mirror in those modes (f16x3e's 1e-4 is stated for the render backward on the reference's own samples, tests/test_gpu_round6.py; f16x3m
-runs f16x3's backward kernels, include/emap_hip.h).
+Left out: precision modes f16x3e and f16x3m over the magnitudes.  emap_udf_vjp in those modes is held against the mirror at one magnitude by
+tests/test_gpu_param_grads.py (TOL["f16x3m"] = f16x3's, it runs f16x3's backward kernels, include/emap_hip.h; TOL["f16x3e"] = the 1e-4 the
+project states for that mode), which also holds accumulate = 1 and weight_norm = 0 - grad_scale here is tested with accumulate = 0 only.
 
 All inputs are finite except the single NaN / inf case of test 3, whose behaviour absmax_kernel defines ("do not poison the scale (they
 poison the result, as in autograd)").
