@@ -1,7 +1,8 @@
-// composite_dev.inc - render_core's tail (udf_renderer_blending.py:435-455,463-677) for ONE ray on one 64-lane wave, shared by
-// composite_kernel (sampler.hip: one workgroup per ray) and by the value + grad_x kernel's fused tail (udf_mlp_rev32.inc, COMP: the
-// workgroup that completes a ray's last tile composites it - BASELINE config C2's "fused MLP + composite").  Included inside namespace emap,
-// after sampler_dev.inc.
+// composite_dev.inc - render_core's tail (udf_renderer_blending.py:435-455,463-677) for ONE ray on one 64-lane wave.  composite_forward is the
+// tail up to the transmittance, written once: composite_ray (forward + outputs: composite_kernel in sampler.hip, one workgroup per ray, and the
+// value + grad_x kernel's fused tail in udf_mlp_rev32.inc, COMP: the workgroup that completes a ray's last tile composites it - BASELINE config
+// C2's "fused MLP + composite") and composite_bwd_kernel (forward + adjoint, sampler.hip) both run it.  Included inside namespace emap, after
+// sampler_dev.inc.
 #pragma once
 
 // COH: udf / grad_x were written by OTHER workgroups of the running kernel (possibly behind another XCD's L2) with agent-scope stores
@@ -12,113 +13,150 @@ __device__ __forceinline__ float comp_ld(const float* p) {
     else return *p;
 }
 
-// Round 5: the ray lives in registers (lane l = samples [l C, (l+1) C), C = 1, 2 or 4), one burst of loads, neighbours over DPP, no LDS and
-// no barriers - see composite_bwd_kernel.  Same expressions and the same scan chunks as the LDS version of rounds 1-4.
-// MODE (compile time, EmapRenderParams.render_mode): EMAP_RENDER_UNBIASED (use_unbias_render=True, :479-549), EMAP_RENDER_UNBIASED_NORMCOS
-// (the same with use_norm_grad_for_cosine=True: true_cos from the normalised gradient, :479-480) or EMAP_RENDER_PLAIN (use_unbias_render=False,
-// :551-559: alpha = alpha_occ, gradients_flip = gradients, :635-639).  composite_kernel (sampler.hip) runs every mode with COH = false; the fused
-// tail of udf_mlp_rev32.inc runs the default mode with COH = true.
-template <int C, bool COH, int MODE = EMAP_RENDER_UNBIASED>
-__device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int ray, const int lane) {
-    const int S = a.S;
-    const size_t rb = (size_t)ray * S;
+// inv_s / beta / gamma (udf_model.py:226-227,259-263 + udf_renderer_blending.py:466-472) and cos_anneal_ratio / flip_saturation of this
+// launch: by value, or from the raw device parameters x = exp(10 p) (then x_* holds them before the clips: the adjoint's reduction passes a
+// gradient on only where clipped == x) and from the schedule kernel's device words where the caller fed them (uniform loads).
+struct RenderScalars { float inv_s, beta, gamma, car, flip_sat, x_var, x_beta, x_gamma; };
+__device__ __forceinline__ RenderScalars render_scalars(const CompositeCore& a) {
+    RenderScalars s{a.inv_s, a.beta, a.gamma, a.sched ? a.sched[2] : a.car, a.sched ? a.sched[3] : a.flip_sat, 0.f, 0.f, 0.f};
+    if (a.var_p) {
+        s.x_var = expf(FMUL(a.var_p[0], 10.0f)); s.x_beta = expf(FMUL(a.beta_p[0], 10.0f)); s.x_gamma = expf(FMUL(a.gamma_p[0], 10.0f));
+        s.inv_s = clipf(s.x_var, 1e-6f, 1e6f);
+        s.beta = clipf(clipf(s.x_beta, 0.0f, FDIV(1.0f, a.beta_min)), 1e-6f, 1e6f);
+        s.gamma = clipf(s.x_gamma, 1e-6f, 1e6f);
+    }
+    return s;
+}
+
+// One ray of render_core's tail up to the transmittance, in registers: lane l holds the C = 1, 2, 4 (8, 16: S > 256) consecutive samples
+// [l C, (l+1) C) (the chunking wave_scan uses), every input is fetched by one burst of loads at the top, neighbours (z, true_cos of sample
+// e+1) come over the DPP network, the two prefix products are fp64 wave scans.  No LDS, no barriers.  ok / last: the sample exists / is the
+// ray's last one (lanes past the end hold copies of it).
+// ADJ: what only the adjoint (sampler.hip:composite_bwd_kernel) reads - ain (the visibility factor before its clip), vp, ap, am and, for
+// C <= 4 (KEEP), the pieces of occ_opacity, sdf2alpha_keep and norm_cos per sample; for C >= 8 they do not all stay in registers and the
+// adjoint evaluates them again.  Without ADJ nothing is stored there.
+template <int C, bool ADJ>
+struct RayForward {
+    static constexpr bool KEEP = ADJ && C <= 4;
+    static constexpr int CA = ADJ ? C : 1, CK = KEEP ? C : 1;
     float z[C + 1], u[C], gx[C], gy[C], gz[C], tc[C + 1];
     bool ok[C], last[C];
+    float ox, oy, oz, dx, dy, dz;
+    RenderScalars s;
+    float dists[C], av[C], vpr[C], alpha[C], om[C], T[C];   // vpr: the raw (unclipped) visibility product of av; T: transmittance, of om
+    float ain[CA], vp[CA], ap[CA], am[CA];
+    OccOpacity oc[CK];
+    Sdf2AlphaKeep kp[CK], km[CK];
+    float gi[CK];
+};
+
+// MODE (compile time, EmapRenderParams.render_mode): EMAP_RENDER_UNBIASED (use_unbias_render=True, :479-549), EMAP_RENDER_UNBIASED_NORMCOS
+// (the same with use_norm_grad_for_cosine=True: true_cos from the normalised gradient, :479-480) or EMAP_RENDER_PLAIN (use_unbias_render=False,
+// :551-559: alpha = alpha_occ, gradients_flip = gradients, :635-639).  composite_kernel and composite_bwd_kernel (sampler.hip) run every mode
+// with COH = false; the fused tail of udf_mlp_rev32.inc runs the default mode with COH = true.
+template <int C, bool COH, int MODE, bool ADJ>
+__device__ __forceinline__ RayForward<C, ADJ> composite_forward(const CompositeCore& a, const int ray, const int lane) {
+    constexpr bool KEEP = RayForward<C, ADJ>::KEEP;
+    RayForward<C, ADJ> f;
+    const int S = a.S;
+    const size_t rb = (size_t)ray * S;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         const int e = lane * C + i;
-        ok[i] = e < S; last[i] = !(e < S - 1);
-        const size_t q = rb + (ok[i] ? e : S - 1);
-        z[i] = a.z[q]; u[i] = comp_ld<COH>(a.udf + q);
-        gx[i] = comp_ld<COH>(a.grad + 3 * q); gy[i] = comp_ld<COH>(a.grad + 3 * q + 1); gz[i] = comp_ld<COH>(a.grad + 3 * q + 2);
+        f.ok[i] = e < S; f.last[i] = !(e < S - 1);
+        const size_t q = rb + (f.ok[i] ? e : S - 1);
+        f.z[i] = a.z[q]; f.u[i] = comp_ld<COH>(a.udf + q);
+        f.gx[i] = comp_ld<COH>(a.grad + 3 * q); f.gy[i] = comp_ld<COH>(a.grad + 3 * q + 1); f.gz[i] = comp_ld<COH>(a.grad + 3 * q + 2);
     }
-    const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
-    const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
+    f.ox = a.rays_o[3 * ray]; f.oy = a.rays_o[3 * ray + 1]; f.oz = a.rays_o[3 * ray + 2];
+    f.dx = a.rays_d[3 * ray]; f.dy = a.rays_d[3 * ray + 1]; f.dz = a.rays_d[3 * ray + 2];
     const float sd = *a.sample_dist;
-    // cos_anneal_ratio / flip_saturation of this step: from the schedule kernel's device words where the caller fed them (uniform loads)
-    const float car = a.sched ? a.sched[2] : a.car, flip_sat = a.sched ? a.sched[3] : a.flip_sat;
-    float inv_s_ = a.inv_s, beta_ = a.beta, gamma_ = a.gamma;
-    if (a.var_p) {  // udf_model.py:226-227,259-263 + udf_renderer_blending.py:466-472
-        inv_s_ = clipf(expf(FMUL(a.var_p[0], 10.0f)), 1e-6f, 1e6f);
-        beta_ = clipf(clipf(expf(FMUL(a.beta_p[0], 10.0f)), 0.0f, FDIV(1.0f, a.beta_min)), 1e-6f, 1e6f);
-        gamma_ = clipf(expf(FMUL(a.gamma_p[0], 10.0f)), 1e-6f, 1e6f);
-    }
+    f.s = render_scalars(a);
     if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
 #pragma unroll
-        for (int i = 0; i < C; ++i) {       // :463-464,480: dirs . (g / (|g| + 1e-5)), the expression of cosn below
-            const float gi = FADD(sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
-            tc[i] = FADD(FADD(FMUL(dx, FDIV(gx[i], gi)), FMUL(dy, FDIV(gy[i], gi))), FMUL(dz, FDIV(gz[i], gi)));
+        for (int i = 0; i < C; ++i) {       // :463-464,480
+            const NormCos n = norm_cos(f.dx, f.dy, f.dz, f.gx[i], f.gy[i], f.gz[i]);
+            f.tc[i] = n.cos;
+            if constexpr (KEEP) f.gi[i] = n.gi;
         }
     } else if constexpr (MODE == EMAP_RENDER_UNBIASED) {
 #pragma unroll
-        for (int i = 0; i < C; ++i) tc[i] = FADD(FADD(FMUL(dx, gx[i]), FMUL(dy, gy[i])), FMUL(dz, gz[i]));      // :482
+        for (int i = 0; i < C; ++i) f.tc[i] = FADD(FADD(FMUL(f.dx, f.gx[i]), FMUL(f.dy, f.gy[i])), FMUL(f.dz, f.gz[i]));      // :482
     }
-    z[C] = dpp_next_f(0.f, z[0]);       // sample e+1 of a lane's last sample is the next lane's first
-    if constexpr (MODE != EMAP_RENDER_PLAIN) tc[C] = dpp_next_f(0.f, tc[0]);
-    float dists[C], av[C], sb[C];
-    float alpha[C];
-    if constexpr (MODE == EMAP_RENDER_PLAIN) {
+    f.z[C] = dpp_next_f(0.f, f.z[0]);       // sample e+1 of a lane's last sample is the next lane's first
+    if constexpr (MODE != EMAP_RENDER_PLAIN) f.tc[C] = dpp_next_f(0.f, f.tc[0]);
 #pragma unroll
-        for (int i = 0; i < C; ++i) {
-            dists[i] = last[i] ? sd : FSUB(z[i + 1], z[i]);                             // :435-444
-            const float raw_occ = udf2logistic1(u[i], beta_);                           // :553-558
-            alpha[i] = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma_), dists[i])));    // :559
-            av[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            dists[i] = last[i] ? sd : FSUB(z[i + 1], z[i]);                                 // :435-444
-            const float raw_occ = udf2logistic1(u[i], beta_);                               // :492
-            const float occ = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma_), dists[i])));   // :497
-            const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);    // :500-509
-            av[i] = FADD(clipf(FADD(FSUB(1.0f, occ), FMUL(flip_sat, vis_mask)), 0.0f, 1.0f), 1e-7f);  // :515
-        }
-        ray_prefix_prod<C>(av, ok, sb);     // vis_prob (:511-523)
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            const float vp = clipf(sb[i], 0.0f, 1.0f);                                      // :528
-            const float tcn = -fabsf(tc[i]);
-            const float ap = sdf2alpha(u[i], tcn, dists[i], inv_s_, a.anneal != 0, car);  // :530-543
-            const float am = sdf2alpha(-u[i], tcn, dists[i], inv_s_, a.anneal != 0, car);
-            alpha[i] = FADD(FMUL(ap, vp), FMUL(am, FSUB(1.0f, vp)));                        // :545
-            av[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
+    for (int i = 0; i < C; ++i) {
+        f.dists[i] = f.last[i] ? sd : FSUB(f.z[i + 1], f.z[i]);                         // :435-444
+        const OccOpacity o = occ_opacity(f.u[i], f.s.beta, f.s.gamma, f.dists[i]);      // :492-497; plain :553-558
+        if constexpr (KEEP) f.oc[i] = o;
+        if constexpr (MODE == EMAP_RENDER_PLAIN) {
+            f.alpha[i] = FSUB(1.0f, o.eq);                                              // :559
+        } else {
+            const float occ = FSUB(1.0f, o.eq);
+            const float vis_mask = f.last[i] ? 1.0f : ((f.tc[i + 1] < 0.01f) ? 1.0f : 0.0f);    // :500-509
+            const float ain = FADD(FSUB(1.0f, occ), FMUL(f.s.flip_sat, vis_mask));
+            if constexpr (ADJ) f.ain[i] = ain;
+            f.av[i] = FADD(clipf(ain, 0.0f, 1.0f), 1e-7f);                              // :515
         }
     }
-    ray_prefix_prod<C>(av, ok, sb);     // transmittance (:593-602)
+    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_prefix_prod<C>(f.av, f.ok, f.vpr);     // vis_prob (:511-523)
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+        if constexpr (MODE != EMAP_RENDER_PLAIN) {
+            const float vp = clipf(f.vpr[i], 0.0f, 1.0f);                               // :528
+            const float tcn = -fabsf(f.tc[i]);
+            Sdf2AlphaKeep kp, km;
+            const float ap = sdf2alpha_keep(f.u[i], tcn, f.dists[i], f.s.inv_s, a.anneal != 0, f.s.car, kp);   // :530-543
+            const float am = sdf2alpha_keep(-f.u[i], tcn, f.dists[i], f.s.inv_s, a.anneal != 0, f.s.car, km);
+            f.alpha[i] = FADD(FMUL(ap, vp), FMUL(am, FSUB(1.0f, vp)));                  // :545
+            if constexpr (ADJ) { f.vp[i] = vp; f.ap[i] = ap; f.am[i] = am; }
+            if constexpr (KEEP) { f.kp[i] = kp; f.km[i] = km; }
+        }
+        f.om[i] = FADD(FSUB(1.0f, f.alpha[i]), 1e-7f);
+    }
+    ray_prefix_prod<C>(f.om, f.ok, f.T);    // transmittance (:593-602)
+    return f;
+}
+
+// composite_forward + render_core's outputs and per-ray reductions: the body of composite_kernel (sampler.hip: one workgroup per ray) and of
+// the fused tail of udf_mlp_rev32.inc
+template <int C, bool COH, int MODE = EMAP_RENDER_UNBIASED>
+__device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int ray, const int lane) {
+    const RayForward<C, false> f = composite_forward<C, COH, MODE, false>(a, ray, lane);
+    const size_t rb = (size_t)ray * a.S;
     double wsum = 0, dsum = 0, nx = 0, ny = 0, nz = 0, e_rel = 0, c_rel = 0, e_ns = 0, c_ns = 0, sp = 0;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        const float w = FMUL(alpha[i], sb[i]);
-        const float mid = FADD(z[i], FMUL(dists[i], 0.5f));                             // :446
-        const float px = FADD(ox, FMUL(dx, mid)), py = FADD(oy, FMUL(dy, mid)), pz = FADD(oz, FMUL(dz, mid));
+        const float w = FMUL(f.alpha[i], f.T[i]);
+        const float mid = FADD(f.z[i], FMUL(f.dists[i], 0.5f));                         // :446
+        const float px = FADD(f.ox, FMUL(f.dx, mid)), py = FADD(f.oy, FMUL(f.dy, mid)), pz = FADD(f.oz, FMUL(f.dz, mid));
         const float pn = sqrtf(FADD(FADD(FMUL(px, px), FMUL(py, py)), FMUL(pz, pz)));   // :563
-        const float gm = sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i])));   // :463
-        const float gi = FADD(gm, 1e-5f);
-        const float cosn = FADD(FADD(FMUL(dx, FDIV(gx[i], gi)), FMUL(dy, FDIV(gy[i], gi))), FMUL(dz, FDIV(gz[i], gi)));  // :485
-        const float flip = (MODE == EMAP_RENDER_PLAIN) ? 1.0f : ((cosn > 0.f) ? -1.0f : 1.0f);   // :486-489; plain: :639
+        const NormCos n = norm_cos(f.dx, f.dy, f.dz, f.gx[i], f.gy[i], f.gz[i]);        // :463, :485
+        const float gm = n.gm;
+        const float flip = (MODE == EMAP_RENDER_PLAIN) ? 1.0f : ((n.cos > 0.f) ? -1.0f : 1.0f);   // :486-489; plain: :639
         const float inside = (pn < 2.0f) ? 1.0f : 0.0f, relax = (pn < 2.4f) ? 1.0f : 0.0f;  // :568-569
-        const float ns = (u[i] < a.near_surface) ? 1.0f : 0.0f;                         // :570
+        const float ns = (f.u[i] < a.near_surface) ? 1.0f : 0.0f;                       // :570
         const float ge = FMUL(FSUB(gm, 1.0f), FSUB(gm, 1.0f));                          // :612-617
-        if (ok[i]) {
+        if (f.ok[i]) {
             const size_t q = rb + lane * C + i;
             if (a.out.weights) a.out.weights[q] = w;
-            if (a.out.alpha) a.out.alpha[q] = alpha[i];
+            if (a.out.alpha) a.out.alpha[q] = f.alpha[i];
             if (a.out.mid_z) a.out.mid_z[q] = mid;
-            if (a.out.dists) a.out.dists[q] = dists[i];
+            if (a.out.dists) a.out.dists[q] = f.dists[i];
             if (a.out.inside_sphere) a.out.inside_sphere[q] = inside;
             if (a.out.gradient_mag) a.out.gradient_mag[q] = gm;
             if (a.out.gradients_flip) {
-                a.out.gradients_flip[3 * q] = FMUL(flip, gx[i]);
-                a.out.gradients_flip[3 * q + 1] = FMUL(flip, gy[i]);
-                a.out.gradients_flip[3 * q + 2] = FMUL(flip, gz[i]);
+                a.out.gradients_flip[3 * q] = FMUL(flip, f.gx[i]);
+                a.out.gradients_flip[3 * q + 1] = FMUL(flip, f.gy[i]);
+                a.out.gradients_flip[3 * q + 2] = FMUL(flip, f.gz[i]);
             }
             wsum += w;
             dsum += (double)FMUL(mid, w);
-            nx += (double)FMUL(FMUL(flip, gx[i]), w); ny += (double)FMUL(FMUL(flip, gy[i]), w); nz += (double)FMUL(FMUL(flip, gz[i]), w);
+            nx += (double)FMUL(FMUL(flip, f.gx[i]), w); ny += (double)FMUL(FMUL(flip, f.gy[i]), w); nz += (double)FMUL(FMUL(flip, f.gz[i]), w);
             e_rel += (double)FMUL(relax, ge); c_rel += relax;
             e_ns += (double)FMUL(ns, ge); c_ns += ns;
-            sp += (double)expf(FMUL(-a.sparse_scale, u[i]));                            // :642-644
+            sp += (double)expf(FMUL(-a.sparse_scale, f.u[i]));                          // :642-644
         }
     }
     wsum = wave_sum_d(wsum); dsum = wave_sum_d(dsum);
@@ -184,13 +222,8 @@ __device__ __forceinline__ void composite_reduce_body(const float* partials, int
         scalars[2] = (float)(t[4] / (double)N);
         scalars[3] = e_rel; scalars[4] = c_rel; scalars[5] = e_ns; scalars[6] = c_ns; scalars[7] = (float)t[4];
         // s_val = 1/inv_s, 1/beta, gamma: the "variance"/"beta"/"gamma" entries of the render dict (:656-658)
-        float inv_s_ = a.inv_s, beta_ = a.beta, gamma_ = a.gamma;
-        if (a.var_p) {
-            inv_s_ = clipf(expf(FMUL(a.var_p[0], 10.0f)), 1e-6f, 1e6f);
-            beta_ = clipf(clipf(expf(FMUL(a.beta_p[0], 10.0f)), 0.0f, FDIV(1.0f, a.beta_min)), 1e-6f, 1e6f);
-            gamma_ = clipf(expf(FMUL(a.gamma_p[0], 10.0f)), 1e-6f, 1e6f);
-        }
-        scalars[8] = FDIV(1.0f, inv_s_); scalars[9] = FDIV(1.0f, beta_); scalars[10] = gamma_; scalars[11] = inv_s_;
+        const RenderScalars s = render_scalars(a);
+        scalars[8] = FDIV(1.0f, s.inv_s); scalars[9] = FDIV(1.0f, s.beta); scalars[10] = s.gamma; scalars[11] = s.inv_s;
         if (err && ge != ge) atomicOr(err, EMAP_F_NAN_GRADERR);
     }
 }

@@ -149,20 +149,25 @@ struct PointSource {
     int32_t* zero_cnt;         // render's fused compositing tail, CompositeFuse::ray_cnt); may be null
 };
 
-// ---- render_core's tail (udf_renderer_blending.py:435-455,463-677): arguments of composite_kernel / composite_ray (composite_dev.inc) ----
-struct CompositeArgs {
+// ---- render_core's tail (udf_renderer_blending.py:435-455,463-677) ----
+// What the ray forward (composite_dev.inc:composite_forward) reads: the part of the arguments that compositing and its adjoint share
+struct CompositeCore {
     const float *rays_o, *rays_d, *z, *udf, *grad, *depth_scale, *sample_dist;
     int N, S;
     float inv_s, beta, gamma, car;
     int anneal;
-    float flip_sat, near_surface, sparse_scale, background;
+    float flip_sat, near_surface, background;
     int has_bg;
     const float *var_p, *beta_p, *gamma_p;  // optional raw device parameters (see EmapRenderParams)
     float beta_min;
-    EmapCompositeOut out;
-    float* partials;
     // device-fed schedule (the *_sched entry points), or null: [2] replaces car and [3] flip_sat, read once per wave as uniform values
     const float* sched;
+};
+// arguments of composite_kernel / composite_ray
+struct CompositeArgs : CompositeCore {
+    float sparse_scale;
+    EmapCompositeOut out;
+    float* partials;
 };
 
 // What the fused tail of udf_mlp_rev32_kernel needs beside the compositing arguments: one arrival counter per ray (points of the ray

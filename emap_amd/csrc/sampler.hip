@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void coarse_z_kernel(const float* near, const 
 // ---------------------------------------------------------------------------------------------
 // render_core tail (udf_renderer_blending.py:435-455,463-677)
 // ---------------------------------------------------------------------------------------------
-#include "composite_dev.inc"     // composite_ray<C, COH, MODE>: the per-ray body, shared with udf_mlp_rev32.inc's fused tail
+#include "composite_dev.inc"     // composite_forward / composite_ray<C, COH, MODE>: the per-ray bodies, shared with udf_mlp_rev32.inc's fused tail
 
 template <int C, int MODE = EMAP_RENDER_UNBIASED>
 __global__ __launch_bounds__(64) void composite_kernel(const CompositeArgs a) {
@@ -230,23 +230,13 @@ __global__ __launch_bounds__(256) void composite_reduce_kernel(const float* part
 // Given dL/d{edge, depth} per ray and dL/d{gradient_error, gradient_error_near_surface}, produces dL/dudf (N,S),
 // dL/d(grad_x udf) (N,S,3) and per-ray partial sums of dL/d{inv_s, beta, gamma}.  The derivation (and its check against
 // torch.autograd through the oracle) is oracle/vjp_mirror.py:composite_bwd / tests/test_vjp_math.py.  One wave per ray;
-// the forward quantities are recomputed with the forward kernel's own expressions so that every clip / mask decision is
-// the one the forward took; the two cumprod adjoints are exclusive suffix sums (fp64 wave scans).
+// the two cumprod adjoints are exclusive suffix sums (fp64 wave scans).
 //
-// Round 5: the ray lives in REGISTERS - lane l holds the C = 1, 2, 4 (8, 16: S > 256) consecutive samples [l C, (l+1) C) (the chunking wave_scan uses,
-// so the two prefix products are bit-identical to the forward kernel's), every input is fetched by one burst of loads at the top (one
-// memory round trip instead of one per pass and loop iteration), neighbours (z, true_cos of sample e+1) come over the DPP network, and
-// the sigmoids / exponentials of the forward recomputation are kept for the adjoint instead of being evaluated a second time.  No LDS,
-// no barriers.  The round-4 kernel (13 LDS arrays per ray, strided passes) took 24 us at 512 rays and 108 us at 4096.
-struct CompositeBwdArgs {
-    const float *rays_o, *rays_d, *z, *udf, *grad, *depth_scale, *sample_dist;
-    int N, S;
-    float inv_s, beta, gamma, car;
-    int anneal;
-    float flip_sat, near_surface, background;
-    int has_bg;
-    const float *var_p, *beta_p, *gamma_p;
-    float beta_min;
+// The forward quantities come from composite_forward (composite_dev.inc), the body composite_kernel runs: every clip / mask decision is the
+// one the forward took and the two prefix products are the forward's, bit for bit, because they are the same code.  For C <= 4 the sigmoids
+// and exponentials of the forward are kept for the adjoint instead of being evaluated a second time (RayForward::KEEP).  The round-4 kernel
+// (13 LDS arrays per ray, strided passes) took 24 us at 512 rays and 108 us at 4096.
+struct CompositeBwdArgs : CompositeCore {
     const float *d_edge, *d_depth;      // (N) or null
     const float *d_ge, *d_ge_ns;        // device scalars or null
     const float* scalars;               // the forward's scalars: [4] = sum(relax), [6] = sum(near)
@@ -256,7 +246,6 @@ struct CompositeBwdArgs {
     float* raymax;                      // (N,2): the per-ray maxima behind them (null iff absmax is)
     float* zero_tail;                   // EmapCompositeGrads.zero_tail / n_zero_tail (cleared by the reduce kernel), or null
     long long n_zero_tail;
-    const float* sched;                 // CompositeArgs::sched
 };
 
 // lane l <- lane 63 - l
@@ -282,24 +271,6 @@ __device__ __forceinline__ void ray_suffix_sum(const float (&in)[C], const bool 
 // alive from) its first evaluation on v.  No instruction is emitted.
 __device__ __forceinline__ float opaque_f(float v) { asm volatile("" : "+v"(v)); return v; }
 
-// sdf2alpha (the forward's expressions, bit for bit) that also hands back what its adjoint needs
-struct Sdf2AlphaKeep { float val, pc, nc, den, en, ep; };
-__device__ __forceinline__ float sdf2alpha_keep(float sdf, float true_cos, float dists, float inv_s, bool anneal, float car, Sdf2AlphaKeep& k) {
-    float iter_cos = true_cos;
-    if (anneal) {
-        const float a = FMUL(relu_(FADD(FMUL(-true_cos, 0.5f), 0.5f)), FSUB(1.0f, car));
-        const float b = FMUL(relu_(-true_cos), car);
-        iter_cos = -FADD(a, b);
-    }
-    const float h = FMUL(FMUL(iter_cos, dists), 0.5f);
-    k.en = FADD(sdf, h);
-    k.ep = FSUB(sdf, h);
-    k.pc = sigmoidf_(FMUL(k.ep, inv_s));
-    k.nc = sigmoidf_(FMUL(k.en, inv_s));
-    k.den = FADD(k.pc, 1e-5f);
-    k.val = FDIV(FADD(FSUB(k.pc, k.nc), 1e-5f), k.den);
-    return clipf(k.val, 0.0f, 1.0f);
-}
 // backward of sdf2alpha(sdf, -tabs, dists, inv_s) for an upstream gradient dval on its clipped output
 __device__ __forceinline__ void sdf2alpha_bwd(const Sdf2AlphaKeep& k, float tabs, float dists, float inv_s, bool anneal, float car, float dval,
                                               float& d_sdf, float& d_tabs, float& d_inv_s) {
@@ -319,169 +290,99 @@ __device__ __forceinline__ void sdf2alpha_bwd(const Sdf2AlphaKeep& k, float tabs
 // autograd gradients, tests/golden/g17_normcos_*: tests/test_gpu_render_modes.py).
 template <int C, int MODE = EMAP_RENDER_UNBIASED>
 __global__ __launch_bounds__(64) void composite_bwd_kernel(const CompositeBwdArgs a) {
-    const int ray = blockIdx.x, lane = threadIdx.x, S = a.S;
-    const size_t rb = (size_t)ray * S;
-    // one burst: the ray's samples (clamped to the last one past the end), then the per-ray and per-launch scalars
-    float z[C + 1], u[C], gx[C], gy[C], gz[C], tc[C + 1];
-    bool ok[C], last[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        const int e = lane * C + i;
-        ok[i] = e < S; last[i] = !(e < S - 1);
-        const size_t q = rb + (ok[i] ? e : S - 1);
-        z[i] = a.z[q]; u[i] = a.udf[q];
-        gx[i] = a.grad[3 * q]; gy[i] = a.grad[3 * q + 1]; gz[i] = a.grad[3 * q + 2];
-    }
-    const float ox = a.rays_o[3 * ray], oy = a.rays_o[3 * ray + 1], oz = a.rays_o[3 * ray + 2];
-    const float dx = a.rays_d[3 * ray], dy = a.rays_d[3 * ray + 1], dz = a.rays_d[3 * ray + 2];
-    const float sd = *a.sample_dist;
-    float inv_s_ = a.inv_s, beta_ = a.beta, gamma_ = a.gamma;
-    if (a.var_p) {
-        inv_s_ = clipf(expf(FMUL(a.var_p[0], 10.0f)), 1e-6f, 1e6f);
-        beta_ = clipf(clipf(expf(FMUL(a.beta_p[0], 10.0f)), 0.0f, FDIV(1.0f, a.beta_min)), 1e-6f, 1e6f);
-        gamma_ = clipf(expf(FMUL(a.gamma_p[0], 10.0f)), 1e-6f, 1e6f);
-    }
+    const int ray = blockIdx.x, lane = threadIdx.x;
+    const size_t rb = (size_t)ray * a.S;
+    // the upstream gradients are requested with the forward's load burst: one memory round trip, not one more after the forward
     const float g_edge = a.d_edge ? a.d_edge[ray] * (a.has_bg ? (1.0f - a.background) : 1.0f) : 0.f;
     const float g_depth = a.d_depth ? a.d_depth[ray] * (a.depth_scale ? a.depth_scale[ray] : 1.0f) : 0.f;
     const float c_ge = a.d_ge ? a.d_ge[0] / (a.scalars[4] + 1e-5f) : 0.f;
     const float c_ns = a.d_ge_ns ? a.d_ge_ns[0] / (a.scalars[6] + 1e-5f) : 0.f;
+    const RayForward<C, true> f = composite_forward<C, false, MODE, true>(a, ray, lane);
+    constexpr bool KEEP = RayForward<C, true>::KEEP;
+    const float beta_ = f.s.beta, gamma_ = f.s.gamma, inv_s_ = f.s.inv_s, car = f.s.car;
     const bool anneal = a.anneal != 0;
-    const float car = a.sched ? a.sched[2] : a.car, flip_sat = a.sched ? a.sched[3] : a.flip_sat;      // composite_ray's
-
-    // C >= 8 (S > 256): the per-sample pieces of the forward recomputation that the adjoint reuses (udf2logistic's, sdf2alpha_keep's, |g| + 1e-5)
-    // do not all stay in registers next to the rest (C = 16 spilled to scratch): they are evaluated a second time where the adjoint needs them -
-    // same expressions on the same inputs, same bits.  C <= 4 keeps them in arrays, as it always did.
-    constexpr bool KEEP = C <= 4;
-    float gi[KEEP ? C : 1];                    // normalised cosine: |g| + 1e-5 (composite_ray's expression)
-    if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) {
-            const int k = KEEP ? i : 0;
-            gi[k] = FADD(sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
-            tc[i] = FADD(FADD(FMUL(dx, FDIV(gx[i], gi[k])), FMUL(dy, FDIV(gy[i], gi[k]))), FMUL(dz, FDIV(gz[i], gi[k])));
-        }
-    } else if constexpr (MODE == EMAP_RENDER_UNBIASED) {
-#pragma unroll
-        for (int i = 0; i < C; ++i) tc[i] = FADD(FADD(FMUL(dx, gx[i]), FMUL(dy, gy[i])), FMUL(dz, gz[i]));
-    }
-    z[C] = dpp_next_f(0.f, z[0]);       // sample e+1 of a lane's last sample is the next lane's first
-    if constexpr (MODE != EMAP_RENDER_PLAIN) tc[C] = dpp_next_f(0.f, tc[0]);
-    float dists[C], E[KEEP ? C : 1], opE[KEEP ? C : 1], raw[KEEP ? C : 1], eq[KEEP ? C : 1], ain[C], av[C], vpr[C];
-    constexpr bool PLAIN_NOKEEP = MODE == EMAP_RENDER_PLAIN && !KEEP;
-    float aocc[PLAIN_NOKEEP ? C : 1];          // PLAIN, C >= 8: alpha = 1 - eq, taken while eq of the sample is at hand
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        const int k = KEEP ? i : 0;
-        dists[i] = last[i] ? sd : FSUB(z[i + 1], z[i]);
-        E[k] = expf(FMUL(-beta_, u[i]));                        // udf2logistic1(u, beta) with its pieces kept
-        opE[k] = FADD(1.0f, E[k]);
-        raw[k] = FDIV(FMUL(beta_, E[k]), FMUL(opE[k], opE[k]));
-        eq[k] = expf(FMUL(FMUL(-relu_(raw[k]), gamma_), dists[i]));            // 1 - alpha_occ up to rounding
-        if constexpr (PLAIN_NOKEEP) aocc[i] = FSUB(1.0f, eq[0]);
-        if constexpr (MODE != EMAP_RENDER_PLAIN) {
-            const float vis_mask = last[i] ? 1.0f : ((tc[i + 1] < 0.01f) ? 1.0f : 0.0f);
-            const float occ = FSUB(1.0f, eq[k]);
-            ain[i] = FADD(FSUB(1.0f, occ), FMUL(flip_sat, vis_mask));
-            av[i] = FADD(clipf(ain[i], 0.0f, 1.0f), 1e-7f);
-        }
-    }
-    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_prefix_prod<C>(av, ok, vpr);           // raw (unclipped) visibility product
-    Sdf2AlphaKeep kp[KEEP ? C : 1], km[KEEP ? C : 1];
-    float ap[C], am[C], vp[C], alpha[C], om[C], T[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        if constexpr (MODE == EMAP_RENDER_PLAIN) {
-            if constexpr (PLAIN_NOKEEP) alpha[i] = aocc[i];
-            else alpha[i] = FSUB(1.0f, eq[i]);                  // composite_ray's alpha, bit for bit
-        } else {
-            vp[i] = clipf(vpr[i], 0.0f, 1.0f);
-            const float tcn = -fabsf(tc[i]);
-            ap[i] = sdf2alpha_keep(u[i], tcn, dists[i], inv_s_, anneal, car, kp[KEEP ? i : 0]);
-            am[i] = sdf2alpha_keep(-u[i], tcn, dists[i], inv_s_, anneal, car, km[KEEP ? i : 0]);
-            alpha[i] = FADD(FMUL(ap[i], vp[i]), FMUL(am[i], FSUB(1.0f, vp[i])));
-        }
-        om[i] = FADD(FSUB(1.0f, alpha[i]), 1e-7f);
-    }
-    ray_prefix_prod<C>(om, ok, T);             // transmittance
     float mid[C], dal[C], x[C], suf[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        mid[i] = FADD(z[i], FMUL(dists[i], 0.5f));
+        mid[i] = FADD(f.z[i], FMUL(f.dists[i], 0.5f));
         dal[i] = g_edge + g_depth * mid[i];                     // dL/dw_e for now
-        x[i] = dal[i] * alpha[i] * T[i];                        // dw_e * w_e
+        x[i] = dal[i] * f.alpha[i] * f.T[i];                    // dw_e * w_e
     }
-    ray_suffix_sum<C>(x, ok, suf, lane);
+    ray_suffix_sum<C>(x, f.ok, suf, lane);
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        dal[i] = dal[i] * T[i] - suf[i] * __builtin_amdgcn_rcpf(om[i]);
+        dal[i] = dal[i] * f.T[i] - suf[i] * __builtin_amdgcn_rcpf(f.om[i]);
         if constexpr (MODE != EMAP_RENDER_PLAIN) {
-            const float dvp = (vpr[i] >= 0.f && vpr[i] <= 1.f) ? dal[i] * (ap[i] - am[i]) : 0.f;
-            x[i] = dvp * vpr[i];
+            const float dvp = (f.vpr[i] >= 0.f && f.vpr[i] <= 1.f) ? dal[i] * (f.ap[i] - f.am[i]) : 0.f;
+            x[i] = dvp * f.vpr[i];
         }
     }
-    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_suffix_sum<C>(x, ok, suf, lane);
+    if constexpr (MODE != EMAP_RENDER_PLAIN) ray_suffix_sum<C>(x, f.ok, suf, lane);
     double p_is = 0.0, p_beta = 0.0, p_gamma = 0.0;
     float mx_u = 0.f, mx_g = 0.f;
 #pragma unroll
     for (int i = 0; i < C; ++i) {
-        const int k = KEEP ? i : 0;
-        float uk = u[i];
-        if constexpr (!KEEP) {
-            uk = opaque_f(u[i]);
-            E[0] = expf(FMUL(-beta_, uk));
-            opE[0] = FADD(1.0f, E[0]);
-            raw[0] = FDIV(FMUL(beta_, E[0]), FMUL(opE[0], opE[0]));
-            eq[0] = expf(FMUL(FMUL(-relu_(raw[0]), gamma_), dists[i]));
-            if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
-                const float gxk = opaque_f(gx[i]);
-                gi[0] = FADD(sqrtf(FADD(FADD(FMUL(gxk, gxk), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i]))), 1e-5f);
-            }
+        const float u = f.u[i], dists = f.dists[i], gx = f.gx[i], gy = f.gy[i], gz = f.gz[i], tc = f.tc[i];
+        // the forward's per-sample pieces: kept (C <= 4), or evaluated a second time through the forward's own helpers (C >= 8: they do not all
+        // stay in registers next to the rest, C = 16 spilled to scratch) - same code on the same inputs, same bits
+        const float uk = KEEP ? u : opaque_f(u);
+        OccOpacity o;
+        float gi = 0.f;
+        if constexpr (KEEP) {
+            o = f.oc[i];
+            if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) gi = f.gi[i];
+        } else {
+            o = occ_opacity(uk, beta_, gamma_, dists);
+            if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) gi = norm_cos(f.dx, f.dy, f.dz, opaque_f(gx), gy, gz).gi;
         }
         // occlusion branch: a_i = clip(1 - occ + fs*vm) + 1e-7; plain: alpha = occ itself
         float docc;
         if constexpr (MODE == EMAP_RENDER_PLAIN) {
             docc = dal[i];
         } else {
-            const float da = suf[i] * __builtin_amdgcn_rcpf(av[i]);
-            docc = (ain[i] >= 0.f && ain[i] <= 1.f) ? -da : 0.f;
+            const float da = suf[i] * __builtin_amdgcn_rcpf(f.av[i]);
+            docc = (f.ain[i] >= 0.f && f.ain[i] <= 1.f) ? -da : 0.f;
         }
-        const float dq = docc * eq[k];
-        const float r1 = __builtin_amdgcn_rcpf(opE[k]), r2 = r1 * r1;
-        const float draw = (raw[k] > 0.f) ? dq * gamma_ * dists[i] : 0.f;
-        const float fE = (1.0f - E[k]) * r2 * r1;
-        float du = draw * (-beta_ * beta_ * E[k] * fE);
-        const float pb = draw * (E[k] * r2 - beta_ * u[i] * E[k] * fE), pg = dq * relu_(raw[k]) * dists[i];
+        const float dq = docc * o.eq;
+        const float r1 = __builtin_amdgcn_rcpf(o.opE), r2 = r1 * r1;
+        const float draw = (o.raw > 0.f) ? dq * gamma_ * dists : 0.f;
+        const float fE = (1.0f - o.E) * r2 * r1;
+        float du = draw * (-beta_ * beta_ * o.E * fE);
+        const float pb = draw * (o.E * r2 - beta_ * u * o.E * fE), pg = dq * relu_(o.raw) * dists;
         // alpha branch
         float dtc = 0.f, d_is = 0.f;
         if constexpr (MODE != EMAP_RENDER_PLAIN) {
-            const float tabs = fabsf(tc[i]);
-            float s1, t1, i1, s2, t2, i2;
-            if constexpr (!KEEP) {
-                (void)sdf2alpha_keep(uk, -tabs, dists[i], inv_s_, anneal, car, kp[0]);
-                (void)sdf2alpha_keep(-uk, -tabs, dists[i], inv_s_, anneal, car, km[0]);
+            const float tabs = fabsf(tc);
+            Sdf2AlphaKeep kp, km;
+            if constexpr (KEEP) {
+                kp = f.kp[i]; km = f.km[i];
+            } else {
+                (void)sdf2alpha_keep(uk, -tabs, dists, inv_s_, anneal, car, kp);
+                (void)sdf2alpha_keep(-uk, -tabs, dists, inv_s_, anneal, car, km);
             }
-            sdf2alpha_bwd(kp[k], tabs, dists[i], inv_s_, anneal, car, dal[i] * vp[i], s1, t1, i1);
-            sdf2alpha_bwd(km[k], tabs, dists[i], inv_s_, anneal, car, dal[i] * (1.0f - vp[i]), s2, t2, i2);
+            float s1, t1, i1, s2, t2, i2;
+            sdf2alpha_bwd(kp, tabs, dists, inv_s_, anneal, car, dal[i] * f.vp[i], s1, t1, i1);
+            sdf2alpha_bwd(km, tabs, dists, inv_s_, anneal, car, dal[i] * (1.0f - f.vp[i]), s2, t2, i2);
             du += s1 - s2;
             d_is = i1 + i2;
-            dtc = (t1 + t2) * ((tc[i] > 0.f) ? 1.f : ((tc[i] < 0.f) ? -1.f : 0.f));
+            dtc = (t1 + t2) * ((tc > 0.f) ? 1.f : ((tc < 0.f) ? -1.f : 0.f));
         }
         // eikonal terms (:612-625), masks detached
-        const float px = FADD(ox, FMUL(dx, mid[i])), py = FADD(oy, FMUL(dy, mid[i])), pz = FADD(oz, FMUL(dz, mid[i]));
+        const float px = FADD(f.ox, FMUL(f.dx, mid[i])), py = FADD(f.oy, FMUL(f.dy, mid[i])), pz = FADD(f.oz, FMUL(f.dz, mid[i]));
         const float pn = sqrtf(FADD(FADD(FMUL(px, px), FMUL(py, py)), FMUL(pz, pz)));
-        const float gm = sqrtf(FADD(FADD(FMUL(gx[i], gx[i]), FMUL(gy[i], gy[i])), FMUL(gz[i], gz[i])));
-        const float relax = (pn < 2.4f) ? 1.0f : 0.0f, ns = (u[i] < a.near_surface) ? 1.0f : 0.0f;
+        const float gm = norm_cos(f.dx, f.dy, f.dz, gx, gy, gz).gm;
+        const float relax = (pn < 2.4f) ? 1.0f : 0.0f, ns = (u < a.near_surface) ? 1.0f : 0.0f;
         const float coef = (gm > 0.f) ? (c_ge * relax + c_ns * ns) * 2.0f * (gm - 1.0f) * __builtin_amdgcn_rcpf(gm) : 0.f;
-        float ogx = dtc * dx + coef * gx[i], ogy = dtc * dy + coef * gy[i], ogz = dtc * dz + coef * gz[i];
+        float ogx = dtc * f.dx + coef * gx, ogy = dtc * f.dy + coef * gy, ogz = dtc * f.dz + coef * gz;
         if constexpr (MODE == EMAP_RENDER_UNBIASED_NORMCOS) {
             // true_cos = d . g / (|g| + eps): its gradient in g is d / (|g| + eps) - (d . g) g / (|g| (|g| + eps)^2)
-            const float rgi = __builtin_amdgcn_rcpf(gi[k]);
-            const float k2 = (gm > 0.f) ? (dx * gx[i] + dy * gy[i] + dz * gz[i]) * rgi * rgi * __builtin_amdgcn_rcpf(gm) : 0.f;
-            ogx = dtc * (dx * rgi - k2 * gx[i]) + coef * gx[i];
-            ogy = dtc * (dy * rgi - k2 * gy[i]) + coef * gy[i];
-            ogz = dtc * (dz * rgi - k2 * gz[i]) + coef * gz[i];
+            const float rgi = __builtin_amdgcn_rcpf(gi);
+            const float k2 = (gm > 0.f) ? (f.dx * gx + f.dy * gy + f.dz * gz) * rgi * rgi * __builtin_amdgcn_rcpf(gm) : 0.f;
+            ogx = dtc * (f.dx * rgi - k2 * gx) + coef * gx;
+            ogy = dtc * (f.dy * rgi - k2 * gy) + coef * gy;
+            ogz = dtc * (f.dz * rgi - k2 * gz) + coef * gz;
         }
-        if (ok[i]) {
+        if (f.ok[i]) {
             const size_t q = rb + lane * C + i;
             a.d_udf[q] = du;
             a.d_grad[3 * q] = ogx; a.d_grad[3 * q + 1] = ogy; a.d_grad[3 * q + 2] = ogz;
@@ -538,13 +439,11 @@ __global__ __launch_bounds__(256) void composite_bwd_reduce_kernel(const float* 
         double t[3];
         for (int k = 0; k < 3; ++k) t[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
         float r_var = 0.f, r_beta = 0.f, r_gamma = 0.f;
-        if (a.var_p) {
-            const float xs = expf(FMUL(a.var_p[0], 10.0f));
-            if (xs >= 1e-6f && xs <= 1e6f) r_var = (float)t[0] * 10.0f * xs;
-            const float xb = expf(FMUL(a.beta_p[0], 10.0f)), hi = FDIV(1.0f, a.beta_min);
-            if (xb >= 0.f && xb <= hi && xb >= 1e-6f && xb <= 1e6f) r_beta = (float)t[1] * 10.0f * xb;
-            const float xg = expf(FMUL(a.gamma_p[0], 10.0f));
-            if (xg >= 1e-6f && xg <= 1e6f) r_gamma = (float)t[2] * 10.0f * xg;
+        if (a.var_p) {      // a clip passes the gradient on where it left x as it was
+            const RenderScalars s = render_scalars(a);
+            if (s.inv_s == s.x_var) r_var = (float)t[0] * 10.0f * s.x_var;
+            if (s.beta == s.x_beta) r_beta = (float)t[1] * 10.0f * s.x_beta;
+            if (s.gamma == s.x_gamma) r_gamma = (float)t[2] * 10.0f * s.x_gamma;
         } else {   // by-value scalars: report the gradients w.r.t. inv_s, beta, gamma themselves
             r_var = (float)t[0]; r_beta = (float)t[1]; r_gamma = (float)t[2];
         }
@@ -670,25 +569,29 @@ int launch_coarse(const float* near, const float* far, const float* t_rand, int 
     return check_launch("coarse_z");
 }
 
-// the render scalars CompositeArgs and CompositeBwdArgs share, from the entry point's EmapRenderParams
-template <class A>
-static void copy_render_scalars(const EmapRenderParams& p, A& a) {
+// The arguments compositing and its adjoint share (CompositeCore), checked and filled from the entry point's.  who: the prefix of the error
+// texts; outputs: the caller's own output pointers are there
+static int fill_composite_core(const char* who, bool outputs, const float* rays_o, const float* rays_d, const float* z, const float* udf,
+                               const float* grad3, const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
+                               const float* sched, CompositeCore& a) {
+    if (S < 1 || S > MAXS_WIDE) { set_error("%s: S=%d out of range (max %d)", who, S, MAXS_WIDE); return EMAP_E_INVALID; }
+    if (!outputs) { set_error("%s: out/partials must not be null", who); return EMAP_E_INVALID; }
+    if (p.variance_dev && (!p.beta_dev || !p.gamma_dev)) { set_error("%s: variance_dev given without beta_dev/gamma_dev", who); return EMAP_E_INVALID; }
+    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
+    a.sample_dist = sample_dist; a.N = N; a.S = S;
     a.inv_s = p.inv_s; a.beta = p.beta; a.gamma = p.gamma; a.car = p.cos_anneal_ratio; a.anneal = p.has_cos_anneal;
     a.flip_sat = p.flip_saturation; a.near_surface = p.near_surface; a.background = p.background; a.has_bg = p.has_background;
     a.var_p = p.variance_dev; a.beta_p = p.beta_dev; a.gamma_p = p.gamma_dev; a.beta_min = p.beta_min;
+    a.sched = sched;
+    return EMAP_OK;
 }
 
 int fill_composite_args(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
                         const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams& p,
                         const EmapCompositeOut* out, float* partials, CompositeArgs* pa, const float* sched) {
-    if (S < 1 || S > MAXS_WIDE) { set_error("composite: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
-    if (!out || !partials) { set_error("composite: out/partials must not be null"); return EMAP_E_INVALID; }
-    if (p.variance_dev && (!p.beta_dev || !p.gamma_dev)) { set_error("composite: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
-    CompositeArgs& a = *pa;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
-    a.sample_dist = sample_dist; a.N = N; a.S = S;
-    copy_render_scalars(p, a);
-    a.sparse_scale = p.sparse_scale; a.out = *out; a.partials = partials; a.sched = sched;
+    const int rc = fill_composite_core("composite", out && partials, rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, p, sched, *pa);
+    if (rc) return rc;
+    pa->sparse_scale = p.sparse_scale; pa->out = *out; pa->partials = partials;
     return EMAP_OK;
 }
 
@@ -708,24 +611,21 @@ int launch_composite(const float* rays_o, const float* rays_d, const float* z, c
     with_render_mode(p.render_mode, [&](auto mode) {
         with_chunk(S, [&](auto c) { hipLaunchKernelGGL((composite_kernel<c, mode>), dim3(N), dim3(64), 0, st, a); });
     });
-    if (out->scalars) hipLaunchKernelGGL(composite_reduce_kernel, dim3(1), dim3(256), 0, st, partials, N, out->scalars, err, a);
-    return check_launch("composite");
+    const int rl = check_launch("composite");
+    return rl ? rl : launch_composite_reduce(a, err, st);
 }
 
 int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* z, const float* udf, const float* grad3,
                          const float* depth_scale, int N, int S, const float* sample_dist, const EmapRenderParams* p,
                          const EmapCompositeGrads* gr, float* d_udf, float* d_grad3, float* partials, uint32_t* absmax,
                          hipStream_t st, const float* sched) {
-    if (S < 1 || S > MAXS_WIDE) { set_error("composite_bwd: S=%d out of range (max %d)", S, MAXS_WIDE); return EMAP_E_INVALID; }
-    if (N <= 0) return EMAP_OK;
-    if (p->variance_dev && (!p->beta_dev || !p->gamma_dev)) { set_error("composite_bwd: variance_dev given without beta_dev/gamma_dev"); return EMAP_E_INVALID; }
     CompositeBwdArgs a;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.z = z; a.udf = udf; a.grad = grad3; a.depth_scale = depth_scale;
-    a.sample_dist = sample_dist; a.N = N; a.S = S;
-    copy_render_scalars(*p, a);
+    const int rc = fill_composite_core("composite_bwd", true, rays_o, rays_d, z, udf, grad3, depth_scale, N, S, sample_dist, *p, sched, a);
+    if (rc) return rc;
+    if (N <= 0) return EMAP_OK;
     a.d_edge = gr->d_edge; a.d_depth = gr->d_depth; a.d_ge = gr->d_gradient_error; a.d_ge_ns = gr->d_gradient_error_near_surface;
     a.scalars = gr->scalars; a.d_udf = d_udf; a.d_grad = d_grad3; a.partials = partials; a.absmax = absmax;
-    a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail; a.sched = sched;
+    a.zero_tail = gr->n_zero_tail > 0 ? gr->zero_tail : nullptr; a.n_zero_tail = gr->n_zero_tail;
     a.raymax = absmax ? partials + (size_t)N * 4 : nullptr;     // internal callers (emap_render_bwd) size `partials` as (N,4) + (N,2)
     if ((a.d_ge || a.d_ge_ns) && !a.scalars) { set_error("composite_bwd: the eikonal gradients need the forward's scalars"); return EMAP_E_INVALID; }
     with_render_mode(p->render_mode, [&](auto mode) {

@@ -132,8 +132,10 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
     const float step = FDIV(FSUB(end, start), (float)(steps - 1));
     return (i < steps / 2) ? FADD(start, FMUL(step, (float)i)) : FSUB(end, FMUL(step, (float)(steps - i - 1)));
 }
-// sdf2alpha, 'numerical' branch (udf_renderer_blending.py:379-411)
-__device__ __forceinline__ float sdf2alpha(float sdf, float true_cos, float dists, float inv_s, bool anneal, float car) {
+// sdf2alpha, 'numerical' branch (udf_renderer_blending.py:379-411).  k: what the compositing adjoint (sampler.hip:sdf2alpha_bwd) needs of it -
+// est_next / est_prev, the two sigmoids, prev_cdf + 1e-5 and the unclipped value
+struct Sdf2AlphaKeep { float val, pc, nc, den, en, ep; };
+__device__ __forceinline__ float sdf2alpha_keep(float sdf, float true_cos, float dists, float inv_s, bool anneal, float car, Sdf2AlphaKeep& k) {
     float iter_cos = true_cos;
     if (anneal) {
         const float a = FMUL(relu_(FADD(FMUL(-true_cos, 0.5f), 0.5f)), FSUB(1.0f, car));
@@ -141,19 +143,40 @@ __device__ __forceinline__ float sdf2alpha(float sdf, float true_cos, float dist
         iter_cos = -FADD(a, b);
     }
     const float h = FMUL(FMUL(iter_cos, dists), 0.5f);
-    const float est_next = FADD(sdf, h);
-    const float est_prev = FSUB(sdf, h);
-    const float prev_cdf = sigmoidf_(FMUL(est_prev, inv_s));
-    const float next_cdf = sigmoidf_(FMUL(est_next, inv_s));
-    const float p = FSUB(prev_cdf, next_cdf);
-    return clipf(FDIV(FADD(p, 1e-5f), FADD(prev_cdf, 1e-5f)), 0.0f, 1.0f);
+    k.en = FADD(sdf, h);
+    k.ep = FSUB(sdf, h);
+    k.pc = sigmoidf_(FMUL(k.ep, inv_s));
+    k.nc = sigmoidf_(FMUL(k.en, inv_s));
+    k.den = FADD(k.pc, 1e-5f);
+    k.val = FDIV(FADD(FSUB(k.pc, k.nc), 1e-5f), k.den);
+    return clipf(k.val, 0.0f, 1.0f);
+}
+__device__ __forceinline__ float sdf2alpha(float sdf, float true_cos, float dists, float inv_s, bool anneal, float car) {
+    Sdf2AlphaKeep k;
+    return sdf2alpha_keep(sdf, true_cos, dists, inv_s, anneal, car, k);
 }
 
-// udf2logistic(udf, inv_s, gamma=1, abs_cos=1) (udf_renderer_blending.py:155-170)
-__device__ __forceinline__ float udf2logistic1(float udf, float inv_s) {
-    const float e = expf(FMUL(-inv_s, udf));
-    const float den = FADD(1.0f, e);
-    return FDIV(FMUL(inv_s, e), FMUL(den, den));
+// The occlusion opacity (udf_renderer_blending.py:303-305, :492-497, :553-559, :960-964): raw = udf2logistic(udf, beta, gamma=1, abs_cos=1)
+// (:155-170) and eq = exp(-relu(raw) gamma dists), which is 1 - alpha_occ up to rounding; E = exp(-beta udf) and opE = 1 + E are what the
+// compositing adjoint reuses of raw.
+struct OccOpacity { float E, opE, raw, eq; };
+__device__ __forceinline__ OccOpacity occ_opacity(float udf, float beta, float gamma, float dists) {
+    OccOpacity k;
+    k.E = expf(FMUL(-beta, udf));
+    k.opE = FADD(1.0f, k.E);
+    k.raw = FDIV(FMUL(beta, k.E), FMUL(k.opE, k.opE));
+    k.eq = expf(FMUL(FMUL(-relu_(k.raw), gamma), dists));
+    return k;
+}
+
+// |g|, |g| + 1e-5 and the normalised cosine dirs . (g / (|g| + 1e-5)) (:463-464, :480, :485)
+struct NormCos { float gm, gi, cos; };
+__device__ __forceinline__ NormCos norm_cos(float dx, float dy, float dz, float gx, float gy, float gz) {
+    NormCos n;
+    n.gm = sqrtf(FADD(FADD(FMUL(gx, gx), FMUL(gy, gy)), FMUL(gz, gz)));
+    n.gi = FADD(n.gm, 1e-5f);
+    n.cos = FADD(FADD(FMUL(dx, FDIV(gx, n.gi)), FMUL(dy, FDIV(gy, n.gi))), FMUL(dz, FDIV(gz, n.gi)));
+    return n;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -247,8 +270,7 @@ __device__ __forceinline__ void upsample_body_c(float ox, float oy, float oz, fl
         const float tcp = i ? tc[i ? i - 1 : 0] : tc_left;
         const float dists_raw = oki[i] ? FSUB(z[i + 1], z[i]) : sd;                       // :254-263
         const float vis_mask = (e == 0) ? 1.0f : ((tcp < 0.05f) ? 1.0f : 0.0f);           // :293-300
-        const float raw_occ = udf2logistic1(u[i], beta);                                  // :303
-        const float alpha_occ = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma), dists_raw)));  // :305
+        const float alpha_occ = FSUB(1.0f, occ_opacity(u[i], beta, gamma, dists_raw).eq); // :303-305
         av[i] = FADD(clipf(FADD(FSUB(1.0f, alpha_occ), vis_mask), 0.0f, 1.0f), 1e-7f);    // :312
     }
     ray_prefix_prod<C>(av, ok, sb);        // vis_prob (:308-319)
@@ -329,8 +351,7 @@ __device__ __forceinline__ void upsample_plain_body_c(float sd, const float* s_z
 #pragma unroll
     for (int i = 0; i < C; ++i) {
         const float dists = oki[i] ? FSUB(z[i + 1], z[i]) : sd;                             // :946-955
-        const float raw_occ = udf2logistic1(u[i], beta);                                    // :960
-        const float alpha_occ = FSUB(1.0f, expf(FMUL(FMUL(-relu_(raw_occ), gamma), dists)));  // :962-964
+        const float alpha_occ = FSUB(1.0f, occ_opacity(u[i], beta, gamma, dists).eq);       // :960-964
         av[i] = FADD(alpha_occ, 1e-5f);                                                     // sample_pdf :73 on alpha_occ[:, :-1]
         if (oki[i]) part += (double)av[i];
     }
