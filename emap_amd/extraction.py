@@ -1,22 +1,42 @@
 """Dense-grid extraction queries (SURVEY par. 8 f2): the second consumer of the UDF field kernels.
 
-Mirror of ``get_udf_normals_grid`` (src/edge_extraction/extract_pointcloud.py:5-95): same arguments, same return tuple,
-same jitter draws (one ``torch.randn((n, sampling_N, 3), device=device)`` per ``max_batch`` chunk, in the same order), but
+Mirrors of ``get_udf_normals_grid``, ``get_udf_normals_slow`` and ``get_pointcloud_from_udf`` (src/edge_extraction/extract_pointcloud.py:5-95,
+:98-193, :212-293): same arguments, same return values, same jitter draws (one ``torch.randn((n, sampling_N, 3), device=device)`` per
+``max_batch`` points of a stage, in the same order), but
   * the grid, the thresholded subset and all jittered neighbourhoods are evaluated in a few launches of up to 2^20 points
-    instead of the reference's N^3/4096 + 51 x n/4096 calls of 4096 points - for ANY ``func`` / ``func_grad``, in particular the
-    closure ``Runner_UDF.extract_edge`` passes (runner_udf.py:520-527: ``udf_network.gradient`` followed by a normalisation).
-    Both callables act point by point, so the chunk size cannot change a result; it only decides whether the field kernels
-    see 4096 points (a latency-bound launch) or a million (large gradient launches run the reverse-sweep kernel).  When the
-    callables are this package's bound ``UDFNetwork.udf`` / ``.gradient`` the wrappers are skipped as well,
+    instead of the reference's N^3/4096 + 51 x n/4096 latency-bound calls of 4096 points - for ANY ``func`` / ``func_grad`` that acts point by point,
+    in particular the closure ``Runner_UDF.extract_edge`` passes (runner_udf.py:520-527: ``udf_network.gradient`` followed by a normalisation),
   * the line direction ``F.normalize(torch.linalg.svd(grad_ld)[2][:, -1, :])`` (:86-88) is one HIP kernel over the
     3x3 matrices G^T G (``emap_null_direction``): no 50x3 SVD batch.
 There is no CPU fallback: tensors must live on the GPU and libemap_hip.so must be loadable.
+
+ONE evaluator (``_evaluator``) stands between the three routines and the callables.  It decides what ``(func, func_grad)`` are, and with
+that how a point set is cut into calls.  The cut is part of the RESULT, to the last bit: the kernel that computes the gradient is chosen
+by launch size (forward-mode tangents below 8 193 points, the reverse sweep above).  With B = ``_BIG``, M = ``_MAX_BATCH``:
+
+  kind        what the callables are                                           the two query routines       get_pointcloud_from_udf
+  fused       the network's own bound ``udf`` and ``gradient``                 hip_udf per B                streamed, hip_udf per B
+  closure     bound ``udf`` + a callable that holds THAT network (rule 2)      point-wise if rule 1 sees    streamed: values hip_udf,
+                                                                               the network, else opaque     gradients the closure, per B
+  point-wise  both callables evaluate a package network (rule 1)               func / func_grad per B       composed (the query routines)
+  opaque      anything else (may not act point by point, max_batch may bound   per max_batch, x sampling_N  composed
+              its memory)                                                      for a neighbourhood
+  grid: lattice values, gradients of the df < thr subset, the flattened n x sampling_N neighbourhood.  slow: fused: ONE hip_udf(with_grad=
+  True) per B gives value and gradient; otherwise func, then func_grad; neighbourhood.  streamed: lattice per B; subset gradients per B;
+  neighbourhoods in groups of max(B // (sampling_N x M), 1) x M points (whole draws, no tensor above B points), one call per group; per
+  shift value + gradient per B; the last shift's neighbourhoods with the reference's 50 / 5e-3.
 """
 import torch
 
 from . import _lib
 
 _BIG = 1 << 20          # points per launch of the fast path (bounds the temporaries: 12 MB in, 16 MB out)
+
+
+def _gpu(device):
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("emap_amd.extraction runs on the GPU only (no CPU fallback)")
+    return torch.device(device)
 
 
 def null_direction(grads: torch.Tensor) -> torch.Tensor:
@@ -31,43 +51,122 @@ def null_direction(grads: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _fast_net(func, func_grad):
-    from .udf_model import UDFNetwork
-    net = getattr(func, "__self__", None)
-    if isinstance(net, UDFNetwork) and getattr(func_grad, "__self__", None) is net \
-            and func.__name__ == "udf" and func_grad.__name__ == "gradient":
-        return net
-    return None
+# what the callables are: one walk over what a callable holds, two owner rules, one evaluator
+def _captured(f):
+    """The objects a callable holds: its ``__self__``, the contents of its non-empty closure cells, its ``__defaults__``."""
+    cells = []
+    for c in (getattr(f, "__closure__", None) or ()):
+        try:
+            cells.append(c.cell_contents)
+        except ValueError:                                   # an empty cell
+            pass
+    return [o for o in (getattr(f, "__self__", None), *cells, *(getattr(f, "__defaults__", None) or ())) if o is not None]
 
 
+# The two owner rules below DISAGREE, and are kept apart on purpose: rule 1 sees an owner only through an attribute called
+# ``udf_network``, rule 2 through any attribute or registered module.  So the runner's closure (its network is ``udf_network_fine``)
+# streams through get_pointcloud_from_udf but gets max_batch chunks when handed straight to the two query routines.  Known and
+# deferred: unifying them changes launch sizes, hence bits.
 def _uses_package_net(f) -> bool:
-    """True for a callable that evaluates this package's UDFNetwork point by point: the network's own bound methods, or a closure
-    over the network / over an object that owns one (the runner's normalising closure, runner_udf.py:520-527).  Such callables are
-    driven with 2^20-point launches; any OTHER callable keeps the caller's ``max_batch`` chunks (it may not act point by point, and
-    ``max_batch`` may be its memory bound)."""
+    """Rule 1 (chunk size): ``f`` evaluates this package's UDFNetwork point by point - the network's own bound methods, or a closure
+    over a network / over an object whose ``udf_network`` is one.  Such callables are driven with 2^20-point launches."""
     from .udf_model import UDFNetwork
-    owns = lambda o: isinstance(o, UDFNetwork) or isinstance(getattr(o, "udf_network", None), UDFNetwork)
-    if owns(getattr(f, "__self__", None)):
-        return True
-    cells = [c.cell_contents for c in (getattr(f, "__closure__", None) or []) if c is not None]
-    return any(owns(o) for o in cells) or any(owns(o) for o in (getattr(f, "__defaults__", None) or ()))
+    return any(isinstance(o, UDFNetwork) or isinstance(getattr(o, "udf_network", None), UDFNetwork) for o in _captured(f))
 
 
-def _chunk(func, func_grad, max_batch, mult=1):
-    return _BIG if (_uses_package_net(func) and _uses_package_net(func_grad)) else max(int(max_batch) * mult, 1)
+def _closes_over(f, net) -> bool:
+    """Rule 2 (streaming): ``f`` holds ``net`` itself or an object one of whose attributes IS ``net`` - whatever the attribute is
+    called.  The runner's closure holds the runner (``self``), whose network is ``self.udf_network_fine`` (runner_udf.py:520-527)."""
+    def holds(o):
+        if o is net:
+            return True
+        try:
+            values = list(vars(o).values())
+        except TypeError:
+            return False
+        values += list(getattr(o, "_modules", {}).values()) if isinstance(getattr(o, "_modules", None), dict) else []
+        return any(v is net for v in values)
+    return any(holds(o) for o in _captured(f))
 
 
-def _eval(fn, pts, chunk):
-    return torch.cat([fn(pts[h:h + chunk]) for h in range(0, pts.shape[0], chunk)]) if pts.shape[0] else fn(pts)
+def _cat(parts, pts, width):
+    return (parts[0] if len(parts) == 1 else torch.cat(parts)).reshape(-1, width) if parts else pts.new_empty((0, width))
+
+
+class _Evaluator:
+    """The field behind ``(func, func_grad)``: ``kind`` as in the module docstring's table, ``net`` the network of the fused and closure
+    kinds.  Owns the chunk rule, the ``detach`` and the shapes; an empty point set is answered without a call."""
+
+    def __init__(self, kind, net, func, func_grad, pointwise, max_batch, streamed):
+        self.kind, self.net, self.func, self.func_grad, self.max_batch = kind, net, func, func_grad, max_batch
+        self.fused, self.streams = kind == "fused", kind in ("fused", "closure")
+        self.direct = self.fused or (streamed and self.streams)      # values from the network's kernel, not through ``func``
+        self.big = self.direct or pointwise
+
+    def chunk(self, mult=1):
+        """Points per call; ``mult`` = sampling_N for a flattened neighbourhood.  Reads the module constants at call time."""
+        return _BIG if self.big else max(int(_MAX_BATCH if self.max_batch is None else self.max_batch) * mult, 1)
+
+    def _each(self, fn, pts, mult=1):
+        c = self.chunk(mult)
+        return [fn(pts[h:h + c]) for h in range(0, int(pts.shape[0]), c)]
+
+    def values(self, pts):                                    # (P, 3) -> (P, 1)
+        fn = (lambda p: self.net.hip_udf(p, with_grad=False)[0]) if self.direct else (lambda p: self.func(p)[0].detach())
+        return _cat(self._each(fn, pts), pts, 1)
+
+    def gradients(self, pts, mult=1):                         # (P, 3) -> (P, 3), whether the callable returns (P, 3) or, as ``UDFNetwork.gradient``, (P, 1, 3)
+        fn = (lambda p: self.net.hip_udf(p, with_grad=True)[1]) if self.fused else (lambda p: self.func_grad(p).detach().reshape(-1, 3))
+        return _cat(self._each(fn, pts, mult), pts, 3)
+
+    def values_and_gradients(self, pts):
+        if not self.fused:
+            return self.values(pts), self.gradients(pts)
+        res = self._each(lambda p: self.net.hip_udf(p, with_grad=True), pts)          # the fused kernel gives both
+        return _cat([r[0] for r in res], pts, 1), _cat([r[1] for r in res], pts, 3)
+
+
+def _evaluator(func, func_grad, max_batch=None, streamed=False):
+    """The one classification of ``(func, func_grad)``.  ``streamed``: closure values from the network's kernel, everything per ``_BIG``."""
+    from .udf_model import UDFNetwork
+    net, kind = getattr(func, "__self__", None), None
+    if isinstance(net, UDFNetwork) and getattr(func, "__name__", "") == "udf":
+        if getattr(func_grad, "__self__", None) is net and getattr(func_grad, "__name__", "") == "gradient":
+            kind = "fused"
+        elif callable(func_grad) and _closes_over(func_grad, net):
+            kind = "closure"         # a closure over any other network, or over nothing recognisable, does not stream
+    pointwise = _uses_package_net(func) and _uses_package_net(func_grad)
+    if kind is None:
+        kind, net = ("point-wise" if pointwise else "opaque"), None
+    return _Evaluator(kind, net, func, func_grad, pointwise, max_batch, streamed)
+
+
+def _draw(n, sampling_N, max_batch, device):
+    """The reference's draw sequence: one randn per ``max_batch`` points of a stage, in order (:75-79, :163-167)."""
+    return torch.cat([torch.randn((min(max_batch, n - h), sampling_N, 3), device=device) for h in range(0, n, max_batch)])
+
+
+def _line_directions(ev, pts, sampling_N, sampling_delta, noise, max_batch, group=None):
+    """(n, 3) null direction of the gradients in a jittered neighbourhood of every point (:75-88).  ``noise`` (n, sampling_N, 3)
+    replaces the draws.  ``group``: points per neighbourhood tensor - the whole set, or a multiple of ``max_batch`` (whole draws)."""
+    n = int(pts.shape[0])
+    if noise is not None and tuple(noise.shape) != (n, sampling_N, 3):
+        raise ValueError(f"noise {tuple(noise.shape)} given for a stage of {n} points x {sampling_N} samples")
+    out = torch.empty(n, 3, device=pts.device)
+    group = group or max(n, 1)
+    for h in range(0, n, group):
+        t = min(h + group, n)
+        z = _draw(t - h, sampling_N, max_batch, pts.device) if noise is None else noise[h:t]
+        g = ev.gradients(jitter_points(pts[h:t], z, sampling_delta), mult=sampling_N)
+        out[h:t] = null_direction(g.reshape(t - h, sampling_N, 3))
+    return out
 
 
 def get_udf_normals_grid(func, func_grad, N, udf_threshold, is_linedirection=False, sampling_N=50, sampling_delta=0.005,
                          max_batch=int(2 ** 12), device="cuda", noise=None):
     """See the module docstring.  ``noise`` (n_below_threshold, sampling_N, 3) replaces the jitter draws (parity tests)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("emap_amd.extraction runs on the GPU only (no CPU fallback)")
-    net = _fast_net(func, func_grad)
+    device = _gpu(device)
+    ev = _evaluator(func, func_grad, max_batch)
     # the N^3 lattice on [-1, 1]^3, first coordinate slowest (the reference's point order and fp32 arithmetic, :36-54: index * 2/(N-1) - 1)
     voxel_size = 2.0 / (N - 1)
     axis = torch.arange(N, device=device, dtype=torch.float32) * voxel_size + (-1)
@@ -75,33 +174,13 @@ def get_udf_normals_grid(func, func_grad, N, udf_threshold, is_linedirection=Fal
     samples[:, :3] = torch.stack(torch.meshgrid(axis, axis, axis, indexing="ij"), dim=-1).reshape(-1, 3)
 
     with torch.no_grad():
-        pts = samples[:, :3].contiguous()
-        if net is not None:
-            df = _eval(lambda p: net.hip_udf(p, with_grad=False)[0], pts, _BIG)
-        else:
-            df = _eval(lambda p: func(p)[0].detach(), pts, _chunk(func, func_grad, max_batch))
-        samples[:, 3:4] = df
-
+        samples[:, 3:4] = ev.values(samples[:, :3].contiguous())
         norm_idx = torch.where(samples[:, 3] < udf_threshold)[0]            # :64-65
         sub = samples[norm_idx, :3].contiguous()
-        if net is not None:
-            grad = _eval(lambda p: net.hip_udf(p, with_grad=True)[1], sub, _BIG).reshape(-1, 1, 3) if len(norm_idx) else sub.reshape(-1, 1, 3)
-        else:
-            grad = _eval(lambda p: func_grad(p).detach(), sub, _chunk(func, func_grad, max_batch)) if len(norm_idx) else sub.reshape(-1, 1, 3)
         # the reference normalises the (P,1,3) gradient along dim=1 - the singleton - i.e. per component (:71)
-        samples[norm_idx, 4:7] = -torch.nn.functional.normalize(grad, dim=1)[:, 0]
-
-        if is_linedirection and len(norm_idx):
-            if noise is None:
-                # same draw sequence as the reference: one randn per max_batch chunk of the thresholded points (:75-79)
-                noise = torch.cat([torch.randn((min(max_batch, len(norm_idx) - h), sampling_N, 3), device=device)
-                                   for h in range(0, len(norm_idx), max_batch)])
-            ld_pts = (sub.unsqueeze(1) + sampling_delta * noise.to(device)).reshape(-1, 3)
-            if net is not None:
-                grad_ld = _eval(lambda p: net.hip_udf(p, with_grad=True)[1], ld_pts, _BIG)
-            else:
-                grad_ld = _eval(lambda p: func_grad(p).detach().reshape(-1, 3), ld_pts, _chunk(func, func_grad, max_batch, sampling_N))
-            samples[norm_idx, 8:11] = null_direction(grad_ld.reshape(len(norm_idx), sampling_N, 3))
+        samples[norm_idx, 4:7] = -torch.nn.functional.normalize(ev.gradients(sub).reshape(-1, 1, 3), dim=1)[:, 0]
+        if is_linedirection:
+            samples[norm_idx, 8:11] = _line_directions(ev, sub, sampling_N, sampling_delta, noise, max_batch)
 
     df_values = samples[:, 3].reshape(N, N, N)
     vecs = samples[:, 4:7].reshape(N, N, N, 3)
@@ -114,34 +193,17 @@ def get_udf_normals_slow(func, func_grad, voxel_size, xyz, is_linedirection, sam
     """Mirror of ``get_udf_normals_slow`` (extract_pointcloud.py:98-193): values, normals (-grad/|grad|) and optional line
     directions at arbitrary points ``xyz`` (n,3).  Same return tuple ``(df_values, normals, ld, samples)`` with the
     reference's 13-column ``samples``; ``voxel_size`` is unused there as well."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("emap_amd.extraction runs on the GPU only (no CPU fallback)")
-    net = _fast_net(func, func_grad)
+    device = _gpu(device)
+    ev = _evaluator(func, func_grad, max_batch)
     xyz = xyz.to(device).float()
-    n = xyz.shape[0]
-    samples = torch.cat([xyz, torch.zeros(n, 10, device=device)], dim=-1)
+    samples = torch.cat([xyz, torch.zeros(xyz.shape[0], 10, device=device)], dim=-1)
     with torch.no_grad():
         pts = samples[:, 0:3].contiguous()
-        if net is not None:
-            res = [net.hip_udf(pts[h:h + _BIG], with_grad=True) for h in range(0, n, _BIG)] if n else []
-            df = torch.cat([r[0] for r in res]) if n else pts[:, :1]
-            grad = torch.cat([r[1] for r in res]) if n else pts
-        else:
-            df = _eval(lambda p: func(p)[0].detach(), pts, _chunk(func, func_grad, max_batch))
-            grad = _eval(lambda p: func_grad(p).detach()[:, 0], pts, _chunk(func, func_grad, max_batch))
+        df, grad = ev.values_and_gradients(pts)
         samples[:, 3] = df.squeeze(-1)
         samples[:, 4:7] = -torch.nn.functional.normalize(grad, dim=1)                     # :158-160
-        if is_linedirection and n:
-            if noise is None:
-                noise = torch.cat([torch.randn((min(max_batch, n - h), sampling_N, 3), device=device)
-                                   for h in range(0, n, max_batch)])                           # :163-167, per chunk
-            ld_pts = (pts.unsqueeze(1) + sampling_delta * noise.to(device)).reshape(-1, 3)
-            if net is not None:
-                grad_ld = _eval(lambda p: net.hip_udf(p, with_grad=True)[1], ld_pts, _BIG)
-            else:
-                grad_ld = _eval(lambda p: func_grad(p.float()).detach()[:, 0], ld_pts, _chunk(func, func_grad, max_batch, sampling_N))
-            samples[:, 7:10] = null_direction(grad_ld.reshape(n, sampling_N, 3))
+        if is_linedirection:
+            samples[:, 7:10] = _line_directions(ev, pts, sampling_N, sampling_delta, noise, max_batch)    # :163-167
     return samples[:, 3], samples[:, 4:7], samples[:, 7:10], samples
 
 
@@ -156,9 +218,7 @@ _SLOW_SAMPLING_N, _SLOW_SAMPLING_DELTA, _MAX_BATCH = 50, 0.005, 1 << 12    # wha
 def lattice_points(N, first, count, device="cuda", out=None):
     """Points [first, first + count) of the N^3 lattice on [-1, 1]^3, first coordinate slowest: (count, 3), bit-identical to
     ``arange(N) * (2 / (N - 1)) + (-1)`` (the order and fp32 arithmetic of ``get_udf_normals_grid``)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("emap_amd.extraction runs on the GPU only (no CPU fallback)")
+    device = _gpu(device)
     count = int(count)
     if out is None:
         xyz = torch.empty(count, 3, device=device, dtype=torch.float32)
@@ -250,6 +310,16 @@ class Compactor:
         n = self.count
         return self.xyz[:n], self.df[:n], self.idx[:n]
 
+    def run(self, heads, append_from):
+        """``append_from(h)`` for every h of ``heads``; after an overflow the calls are repeated from the one that did not fit.  -> ``result()``"""
+        done = 0
+        while True:
+            for h in heads[done:]:
+                append_from(h)
+            _, done, overflowed = self.finish()
+            if not overflowed:
+                return self.result()
+
 
 def compact(df, xyz, threshold, inclusive, capacity=_SURVIVORS0, chunk=_BIG):
     """Order-preserving ``(xyz[mask], df[mask], torch.where(mask)[0])`` with ``mask = df <= threshold`` (inclusive) or
@@ -259,111 +329,49 @@ def compact(df, xyz, threshold, inclusive, capacity=_SURVIVORS0, chunk=_BIG):
     df = _lib.f32c(df).reshape(-1)
     xyz = _lib.f32c(xyz)
     c = Compactor(df.device, capacity)
-    heads = list(range(0, int(df.shape[0]), chunk))
-    done = 0
-    while True:
-        for h in heads[done:]:
-            c.append(df[h:h + chunk], xyz[h:h + chunk], threshold, inclusive, first_index=h)
-        _, done, overflowed = c.finish()
-        if not overflowed:
-            return c.result()
-
-
-def _closes_over(f, net) -> bool:
-    """True if the closure ``f`` holds ``net`` itself or an object one of whose attributes IS ``net`` - whatever the attribute is
-    called.  The runner's closure holds the runner (``self``), whose network is ``self.udf_network_fine`` (runner_udf.py:520-527)."""
-    def holds(o):
-        if o is net:
-            return True
-        try:
-            values = list(vars(o).values())
-        except TypeError:
-            return False
-        values += list(getattr(o, "_modules", {}).values()) if isinstance(getattr(o, "_modules", None), dict) else []
-        return any(v is net for v in values)
-    cells = []
-    for c in (getattr(f, "__closure__", None) or ()):
-        try:
-            cells.append(c.cell_contents)
-        except ValueError:                                   # an empty cell
-            pass
-    return any(holds(o) for o in [getattr(f, "__self__", None), *cells, *(getattr(f, "__defaults__", None) or ())] if o is not None)
+    return c.run(range(0, int(df.shape[0]), chunk), lambda h: c.append(df[h:h + chunk], xyz[h:h + chunk], threshold, inclusive, first_index=h))
 
 
 def _stream_fns(func, func_grad):
-    """(net, grad) for the streamed path, or None: ``func`` is this package's bound ``UDFNetwork.udf`` and ``func_grad`` its bound
-    ``.gradient`` (grad = None: the fused value + gradient kernel) or a closure over THAT network or over an object that owns it -
-    the runner's normalising closure over ``self`` (runner_udf.py:520-527) - which is then called on up to 2^20 points at a time.
-    A closure over any other network, or over nothing recognisable, takes the composed path."""
-    from .udf_model import UDFNetwork
-    net = _fast_net(func, func_grad)
-    if net is not None:
-        return net, None
-    net = getattr(func, "__self__", None)
-    if isinstance(net, UDFNetwork) and getattr(func, "__name__", "") == "udf" and callable(func_grad) and _closes_over(func_grad, net):
-        return net, func_grad
-    return None
-
-
-def _gradients(net, grad_fn, pts):
-    """(P, 3) gradients at pts (P <= 2^20 per launch)."""
-    if grad_fn is None:
-        return _eval(lambda p: net.hip_udf(p, with_grad=True)[1], pts, _BIG)
-    return _eval(lambda p: grad_fn(p).detach().reshape(-1, 3), pts, _BIG)
-
-
-def _line_directions(net, grad_fn, pts, sampling_N, sampling_delta, noise, device):
-    """Null direction of the gradients in a jittered neighbourhood of every point, in groups of whole ``max_batch`` draws so that
-    no neighbourhood tensor exceeds 2^20 points.  The draws are the reference's: one randn per 4096 points, in order."""
-    n = int(pts.shape[0])
-    out = torch.empty(n, 3, device=device)
-    if noise is not None and tuple(noise.shape) != (n, sampling_N, 3):
-        raise ValueError(f"noise {tuple(noise.shape)} given for a stage of {n} points x {sampling_N} samples")
-    group = max(_BIG // (sampling_N * _MAX_BATCH), 1) * _MAX_BATCH
-    for h in range(0, n, group):
-        t = min(h + group, n)
-        if noise is None:
-            z = torch.cat([torch.randn((min(_MAX_BATCH, t - b), sampling_N, 3), device=device) for b in range(h, t, _MAX_BATCH)])
-        else:
-            z = noise[h:t].to(device)
-        g = _gradients(net, grad_fn, jitter_points(pts[h:t], z, sampling_delta))
-        out[h:t] = null_direction(g.reshape(t - h, sampling_N, 3))
-    return out
+    """(net, grad) for the streamed path - grad None: the fused kind - or None: the composed path.  A view of the one classification."""
+    ev = _evaluator(func, func_grad)
+    return (ev.net, None if ev.fused else func_grad) if ev.streams else None
 
 
 def _pointcloud_stream(net, grad_fn, N, thr, sampling_N, sampling_delta, is_pointshift, iters, is_linedirection, device, noise, trace=None):
-    """The streamed routine; returns device tensors (points, line directions).  Host reads per stage: the compaction state, once
-    (again after a grown buffer), plus at the grid stage the index build of the df < thr subset.
+    """The streamed routine on what ``_stream_fns`` returned; returns device tensors (points, line directions).  Host reads per stage: the
+    compaction state, once (again after a grown buffer), plus at the grid stage the index build of the df < thr subset.
     ``trace`` is TEST-ONLY scaffolding and not reachable through the public function: a dict that receives references (no copies)
     to each stage's lattice indices, which the parity test needs to align the reference's recorded jitter rows with this run's
     point sets.  Production callers leave it None."""
     F = torch.nn.functional
-    noise = iter(noise) if noise is not None else None
-    take = (lambda: next(noise, None)) if noise is not None else (lambda: None)
+    ev = _evaluator(net.udf, grad_fn or net.gradient, streamed=True)
+    noise = iter(noise) if noise is not None else iter(())
+
+    def directions(pts, sampling_N, sampling_delta):
+        # groups of whole _MAX_BATCH draws (the reference's: one randn per 4096 points, in order), no neighbourhood tensor above _BIG points
+        return _line_directions(ev, pts, sampling_N, sampling_delta, next(noise, None), _MAX_BATCH,
+                                group=max(_BIG // (sampling_N * _MAX_BATCH), 1) * _MAX_BATCH)
+
     total = N ** 3
     with torch.no_grad():
         # grid stage: value pass + compaction of clamp(df, 0) <= thr.  For thr >= 0 that set is df <= thr, which also holds every
         # point of the normals' set df < thr; for thr < 0 it is empty while df < thr may not be - then the raw set is kept.
         c = Compactor(device)
         buf = torch.empty(min(_BIG, total), 3, device=device)
-        heads, done = list(range(0, total, _BIG)), 0
-        while True:
-            for h in heads[done:]:
-                xyz = lattice_points(N, h, min(_BIG, total - h), device, out=buf)
-                c.append(net.hip_udf(xyz, with_grad=False)[0], xyz, thr, thr >= 0, first_index=h)
-            _, done, overflowed = c.finish()
-            if not overflowed:
-                break
+
+        def walk(h):
+            xyz = lattice_points(N, h, min(_BIG, total - h), device, out=buf)
+            c.append(ev.values(xyz), xyz, thr, thr >= 0, first_index=h)
+        xyz, df, idx = c.run(range(0, total, _BIG), walk)
         del buf
-        xyz, df, idx = c.result()
         below = torch.where(df < thr)[0]                                    # :65 - normals and directions live here (the stage's one index build)
         sub = xyz[below]
         n = int(xyz.shape[0])
         normals, lds = torch.zeros(n, 3, device=device), torch.zeros(n, 3, device=device)
-        grad = _gradients(net, grad_fn, sub).reshape(-1, 1, 3)
-        normals[below] = -F.normalize(grad, dim=1)[:, 0]                    # per component: the reference's dim=1 on (P, 1, 3), :72
+        normals[below] = -F.normalize(ev.gradients(sub).reshape(-1, 1, 3), dim=1)[:, 0]    # per component: the reference's dim=1 on (P, 1, 3), :72
         if is_linedirection:
-            lds[below] = _line_directions(net, grad_fn, sub, sampling_N, sampling_delta, take(), device)
+            lds[below] = directions(sub, sampling_N, sampling_delta)
         if trace is not None:
             trace["grid"] = dict(idx=idx, below=below, df=df)
         # :259-262, clamp(df, 0) <= thr: every compacted point for thr >= 0 (df <= thr, and a negative df clamps to 0), none for thr < 0
@@ -375,19 +383,12 @@ def _pointcloud_stream(net, grad_fn, N, thr, sampling_N, sampling_delta, is_poin
         if is_pointshift and iters > 0:
             for it in range(iters):
                 shifted = shift_points(xyz, df, normals)                    # :273
-                last = it == iters - 1
                 n = int(shifted.shape[0])
-                if grad_fn is None:
-                    res = [net.hip_udf(shifted[h:h + _BIG], with_grad=True) for h in range(0, n, _BIG)]
-                    sdf = torch.cat([r[0] for r in res]).reshape(-1) if n else shifted[:, 0]
-                    grad = torch.cat([r[1] for r in res]) if n else shifted
-                else:
-                    sdf = _eval(lambda p: net.hip_udf(p, with_grad=False)[0], shifted, _BIG).reshape(-1) if n else shifted[:, 0]
-                    grad = _gradients(net, grad_fn, shifted) if n else shifted
+                sdf, grad = ev.values_and_gradients(shifted)
+                sdf = sdf.reshape(-1)
                 snormals = -F.normalize(grad, dim=1)                        # :160-161
-                slds = torch.zeros(n, 3, device=device)
-                if last:                                                    # the reference's own sampling_N / delta here, not the caller's
-                    slds = _line_directions(net, grad_fn, shifted, _SLOW_SAMPLING_N, _SLOW_SAMPLING_DELTA, take(), device)
+                # the last shift: the reference's own sampling_N / delta here, not the caller's
+                slds = directions(shifted, _SLOW_SAMPLING_N, _SLOW_SAMPLING_DELTA) if it == iters - 1 else torch.zeros(n, 3, device=device)
                 sxyz, sdf_kept, src = compact(sdf, shifted, thr, True, capacity=n)      # :282
                 if trace is not None:
                     trace[f"shift{it}"] = dict(idx=idx, df=sdf, xyz=shifted, kept=src)
@@ -399,12 +400,12 @@ def _pointcloud_stream(net, grad_fn, N, thr, sampling_N, sampling_delta, is_poin
 
 def _pointcloud_composed(func, func_grad, N_MC, udf_threshold, sampling_N, sampling_delta, is_pointshift, iters, is_linedirection,
                          device, noise):
-    """Any other callable: the reference's own composition of the two query routines (extract_pointcloud.py:240-293)."""
-    noise = iter(noise) if noise is not None else None
-    take = (lambda: next(noise, None)) if noise is not None else (lambda: None)
+    """Any other callable: the reference's own composition of the two query routines (extract_pointcloud.py:240-293).  Not bit-identical
+    to the streamed routine (other launch shapes), and the only path for callables that cannot stream."""
+    noise = iter(noise) if noise is not None else iter(())
     df, lds, normals, samples, voxel_size = get_udf_normals_grid(
         func, func_grad, N_MC, udf_threshold, is_linedirection, sampling_N, sampling_delta, device=device,
-        noise=take() if is_linedirection else None)
+        noise=next(noise, None) if is_linedirection else None)
     df, lds, normals, xyz = df.reshape(-1), lds.reshape(-1, 3), normals.reshape(-1, 3), samples.reshape(-1, 12)[:, 0:3]
     df = df.clamp(min=0)
     keep = df <= udf_threshold
@@ -414,7 +415,7 @@ def _pointcloud_composed(func, func_grad, N_MC, udf_threshold, sampling_N, sampl
             last = it == iters - 1
             shifted = xyz + df.unsqueeze(-1) * normals
             sdf, snormals, lds, _ = get_udf_normals_slow(func, func_grad, voxel_size, shifted, last, device=device,
-                                                         noise=take() if last else None)
+                                                         noise=next(noise, None) if last else None)
             keep = sdf <= udf_threshold
             xyz, df, normals, lds = shifted[keep], sdf[keep], snormals[keep], lds[keep]
     return xyz, lds
@@ -428,13 +429,11 @@ def get_pointcloud_from_udf(func, func_grad, N_MC=128, udf_threshold=1.0, sampli
     through ``get_udf_normals_grid`` / ``get_udf_normals_slow`` as in the reference.  ``noise``: a list with one (n_stage,
     sampling_N, 3) tensor per stage that draws jitter, in order - the grid stage (if ``is_linedirection``; rows follow the lattice
     points with df < threshold) and the last shift iteration (always 50 samples there, as in the reference) - replacing the randn draws."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("emap_amd.extraction runs on the GPU only (no CPU fallback)")
+    device = _gpu(device)
     N_MC, thr = int(N_MC), float(udf_threshold)
     fns = _stream_fns(func, func_grad)
     if fns is not None:
-        xyz, lds = _pointcloud_stream(fns[0], fns[1], N_MC, thr, int(sampling_N), float(sampling_delta), is_pointshift, int(iters),
+        xyz, lds = _pointcloud_stream(*fns, N_MC, thr, int(sampling_N), float(sampling_delta), is_pointshift, int(iters),
                                       is_linedirection, device, noise)
     else:
         xyz, lds = _pointcloud_composed(func, func_grad, N_MC, thr, sampling_N, sampling_delta, is_pointshift, int(iters),

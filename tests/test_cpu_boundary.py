@@ -289,8 +289,8 @@ def test_extraction_chunking_policy():
     foreign = lambda x: x * 2
     assert E._uses_package_net(net.udf) and E._uses_package_net(closure) and E._uses_package_net(via_owner)
     assert not E._uses_package_net(foreign) and not E._uses_package_net(len)
-    assert E._chunk(net.udf, closure, 4096) == E._BIG == 1 << 20
-    assert E._chunk(net.udf, foreign, 4096) == 4096 and E._chunk(foreign, foreign, 128, 50) == 6400
+    assert E._evaluator(net.udf, closure, 4096).chunk() == E._BIG == 1 << 20
+    assert E._evaluator(net.udf, foreign, 4096).chunk() == 4096 and E._evaluator(foreign, foreign, 128).chunk(50) == 6400
 
 
 def test_graft_entry_verifies_the_prebuilt_library():

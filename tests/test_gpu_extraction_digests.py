@@ -1,0 +1,179 @@
+"""The three extraction routines bit for bit: sha256 of every tensor get_udf_normals_grid, get_udf_normals_slow and
+get_pointcloud_from_udf return, for every kind of callable they tell apart.
+
+The parity tests (test_gpu_parity.py, test_gpu_pointcloud.py) bound the results by tolerances.  The kernel that computes the gradient
+is chosen by launch size, so HOW a point set is cut into calls is part of the result to the last bit, and a slip in a
+chunk rule, a group size or the order of the jitter rows hides under any tolerance.  Every case here compares one digest over all
+returned tensors with the digest recorded on an MI355X from extraction.py as it stood before its evaluation paths were consolidated
+into one evaluator.  Points and noise come from numpy's PCG64 and the weights from synthetic.make_udf_state; the stage sizes of the
+noise list come from public calls only.  The ``noise=None`` cases involve no digest: a call that draws its own jitter after
+torch.manual_seed must equal the same call given the noise the documented draw rule produces after the same seed."""
+import functools
+import hashlib
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from emap_amd import extraction, synthetic
+from test_gpu_parity import mk, DEV
+
+pytestmark = pytest.mark.gpu
+
+NETS = ("d4w128L10", "d8w256L10")
+NET_KINDS = ("bound", "runner_fine", "owner", "lambdas")
+ROUTINES = ("grid", "slow", "pointcloud")
+CASES = [f"{r}/{n}/{k}" for r in ROUTINES for n in NETS for k in NET_KINDS] + [f"{r}/analytic" for r in ROUTINES]
+
+
+@functools.lru_cache(maxsize=None)
+def _net(name):
+    return mk(name, "f16x3")[0]
+
+
+def callables(kind, net=None):
+    """(func, func_grad) of one kind.  Only what the routines can see tells the kinds apart: bound methods, closures and what they hold."""
+    if kind == "bound":                                       # the network's own methods
+        return net.udf, net.gradient
+    if kind == "runner_fine":                                 # what Runner_UDF.extract_edge passes: a closure over the runner
+        return synthetic.extract_edge_callables(types.SimpleNamespace(udf_network_fine=net))
+    if kind == "owner":                                       # a closure over an object whose network is called `udf_network`
+        owner = types.SimpleNamespace(udf_network=net)
+        return owner.udf_network.udf, (lambda p: owner.udf_network.gradient(p))
+    if kind == "lambdas":                                     # plain lambdas over the network
+        return (lambda p: net.udf(p)), (lambda p: net.gradient(p))
+    assert kind == "analytic"                                 # a torch field the package knows nothing about: |(|p - c|) - r|
+
+    def signed(p):
+        q = p - torch.tensor([0.1, -0.2, 0.05], device=p.device)
+        r = torch.sqrt(q[:, 0:1] * q[:, 0:1] + q[:, 1:2] * q[:, 1:2] + q[:, 2:3] * q[:, 2:3])
+        return q, r, r - 0.6
+
+    def func(p):
+        return (signed(p)[2].abs(),)
+
+    def func_grad(p):
+        q, r, s = signed(p)
+        return (torch.sign(s) * q / (r + 1e-12)).unsqueeze(1)                       # (P, 1, 3), as UDFNetwork.gradient
+    return func, func_grad
+
+
+def _rng(case):
+    return np.random.Generator(np.random.PCG64(int.from_bytes(hashlib.sha256(case.encode()).digest()[:4], "little")))
+
+
+def _normal(rng, *shape):
+    return torch.from_numpy(rng.standard_normal(shape, dtype=np.float32))
+
+
+def _quantile(func, func_grad, N, q):
+    """The q quantile of the field on the N^3 lattice (numpy; rounded to fp32, so that a comparison with it is the same in any precision),
+    and the field, through the public grid routine."""
+    df = extraction.get_udf_normals_grid(func, func_grad, N, -1.0, False, device=DEV)[0].reshape(-1).cpu().numpy()
+    return float(np.float32(np.quantile(df.astype(np.float64), q))), df
+
+
+GRID = dict(N=20, is_linedirection=True, sampling_N=50, sampling_delta=0.005, max_batch=256, device=DEV)
+SLOW = dict(is_linedirection=True, sampling_N=50, sampling_delta=0.005, max_batch=128, device=DEV)
+CLOUD = dict(N_MC=32, sampling_N=50, sampling_delta=5e-3, is_pointshift=True, iters=2, is_linedirection=True, device=DEV)
+
+
+def _cloud_stage_sizes(func, func_grad, thr, df):
+    """Rows of the two noise tensors: the lattice points with df < thr, and the points that enter the last shift (= what a run with one
+    iteration less and no directions returns)."""
+    before_last = extraction.get_pointcloud_from_udf(func, func_grad, **dict(CLOUD, udf_threshold=thr, iters=CLOUD["iters"] - 1,
+                                                                              is_linedirection=False))[0]
+    return int((df < np.float32(thr)).sum()), len(before_last)
+
+
+def run(case, noise="pcg"):
+    """Returned tensors of one case, as a list of numpy arrays.  noise: "pcg" (numpy draws) | None (the routine draws) | "rule" (the
+    documented draw rule restated here: one randn per max_batch points of a stage, in order)."""
+    routine, *rest = case.split("/")
+    func, func_grad = callables("analytic") if rest == ["analytic"] else callables(rest[1], _net(rest[0]))
+    rng = _rng(case)
+
+    def draws(n, k, max_batch):
+        if noise == "pcg":
+            return _normal(rng, n, k, 3)
+        if noise is None:
+            return None
+        return torch.cat([torch.randn((min(max_batch, n - h), k, 3), device=DEV) for h in range(0, n, max_batch)])
+
+    if routine == "grid":
+        thr, df = _quantile(func, func_grad, GRID["N"], 0.10)
+        n = int((df < np.float32(thr)).sum())
+        assert 0 < n < len(df)
+        out = extraction.get_udf_normals_grid(func, func_grad, udf_threshold=thr, noise=draws(n, 50, GRID["max_batch"]), **GRID)
+    elif routine == "slow":
+        xyz = torch.from_numpy(rng.random((300, 3), dtype=np.float32) * 2 - 1)
+        out = extraction.get_udf_normals_slow(func, func_grad, None, xyz, noise=draws(300, 50, SLOW["max_batch"]), **SLOW)
+    else:
+        thr, df = _quantile(func, func_grad, CLOUD["N_MC"], 0.02)
+        n_grid, n_last = _cloud_stage_sizes(func, func_grad, thr, df)
+        assert n_grid > 0 and n_last > 0
+        if noise is None:
+            z = None
+        else:                                                 # the grid stage draws first, then the last shift with its own 50 samples
+            z = [draws(n_grid, CLOUD["sampling_N"], extraction._MAX_BATCH), draws(n_last, 50, extraction._MAX_BATCH)]
+        out = extraction.get_pointcloud_from_udf(func, func_grad, udf_threshold=thr, noise=z, **CLOUD)
+    torch.cuda.synchronize()
+    return [o if isinstance(o, np.ndarray) else o.detach().cpu().numpy() for o in out]
+
+
+def compute(case):
+    h = hashlib.sha256()
+    for a in run(case):
+        h.update(repr((a.shape, str(a.dtype))).encode())
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+# recorded on an MI355X from extraction.py as it stood before the one-evaluator consolidation
+DIGESTS = {
+    "grid/d4w128L10/bound": "03a3bbf82bdbd405503e3986cac589ea93773340b8086291076aed31b54adc4b",
+    "grid/d4w128L10/runner_fine": "7ef1fc7b578a239a7cfa38ff9e2b1eb326aaa71e9dd2e7a0eba23bd8f7c8dfac",
+    "grid/d4w128L10/owner": "6198e3c62aefec8ddddfe86fb8a92240bb6f28565ff3b8a895cdcc46d9f1ea08",
+    "grid/d4w128L10/lambdas": "4ab64dfb4d36500bf013b032ae0933df16a0c83b4e7373040be7c1e2395af178",
+    "grid/d8w256L10/bound": "6357b83f6ba27d8dbae4cea5067d0a498672c379b95015c6c7f0109f627406ab",
+    "grid/d8w256L10/runner_fine": "efa35836ac38da6a4155a5b4da5f0e44d27437609d0fb2761c3c9b137058ad02",
+    "grid/d8w256L10/owner": "2fc3b96779bc3fdc5fdc6e36a81cdcb67583619ec5eea755ba2e7d512df00b55",
+    "grid/d8w256L10/lambdas": "d23595c9fe4d571b09f9e54128e0c5733eb0b2e96ac4149ad17f87f861e21b6c",
+    "slow/d4w128L10/bound": "6dd44ba804ce4a8d07d0e6d8aa4759387fa4e22f32f81d365097bace161ff15c",
+    "slow/d4w128L10/runner_fine": "f4d523fbfc3b788bfefbc24ef73d576106bf6ad8dde91828c87dc14b01732e9d",
+    "slow/d4w128L10/owner": "523917e9b42686b02d22f9e9efc0db369415884608dc4b5c8ff4f3417d8c46a3",
+    "slow/d4w128L10/lambdas": "2769656900e2a9ae0a78a925a5d391dd3f19cad401a6b94b1925b29ca47f49e0",
+    "slow/d8w256L10/bound": "0482789be98636e3863e2c91f032367627360dac22386f653778c68bc34adae6",
+    "slow/d8w256L10/runner_fine": "12c8cf2a48b28bbd57130af36850fa4ae1b686f17d20e71c1bb36da82be93b49",
+    "slow/d8w256L10/owner": "26632b6f128105adf412f3396358a5efeb45784fc8aa646e97eaec960a1a4a2c",
+    "slow/d8w256L10/lambdas": "2b17abc7694e9fe002e830fd659b1cba3c72e672311bf126fa7a8fb249be8266",
+    "pointcloud/d4w128L10/bound": "ead95b5439e2ca0058d385357f50d1efa36c7f3f63a7990b46bb161c15178b42",
+    "pointcloud/d4w128L10/runner_fine": "dd3f6925acd70d5822c0fbcddafd600b8aef78907814b2967f7de9fe3de606af",
+    "pointcloud/d4w128L10/owner": "5e1bd5764fe6427d844a73410863adca0a2e74ffa399d07c1d4c637383b8e4dc",
+    "pointcloud/d4w128L10/lambdas": "bc9ce01cd074e6e1e9f0949bdd2af46ee167cd96695235a6adb806f69eae7c5c",
+    "pointcloud/d8w256L10/bound": "87ca2e2531d3af718156ad6589635bc5701ae79deecce3c2292a6a9aaaf8cfee",
+    "pointcloud/d8w256L10/runner_fine": "47e24a76495d0d3336b77f7da985014991736c87c35995059fe2e0a7abecbd80",
+    "pointcloud/d8w256L10/owner": "b245bbff53bb7cc8d63099eb756a92c842ea64e65b2ecb4e8cff03f781c3e013",
+    "pointcloud/d8w256L10/lambdas": "119b60d59c2c4ac524779d7403930ca5fc555f3775e498af9459608a8bc7fa1a",
+    "grid/analytic": "733d4b5967eaf9dc4e2c579f58db79f127b56c7a720acf621ecaac08465cd713",
+    "slow/analytic": "501f76ab8c63dfbfc8817e0742e9a950f8a909c6a064385847941fa425ffa3f2",
+    "pointcloud/analytic": "485a181ab2973b320fb38a56efe823a4cd3a0f4d364909c20b63aafd1265dae4",
+}
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_extraction_digest(case):
+    assert compute(case) == DIGESTS[case]
+
+
+@pytest.mark.parametrize("routine", ROUTINES)
+def test_own_draws_follow_the_documented_rule(routine):
+    case = f"{routine}/d4w128L10/bound"
+    torch.manual_seed(1234)
+    own = run(case, noise=None)
+    torch.manual_seed(1234)
+    given = run(case, noise="rule")
+    assert len(own) == len(given) and all(np.array_equal(a, b) for a, b in zip(own, given))
+    ld = own[{"grid": 1, "slow": 2, "pointcloud": 1}[routine]]
+    assert ld.any()                                           # the line directions were drawn for and computed

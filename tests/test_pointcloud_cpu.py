@@ -159,6 +159,114 @@ def test_streamed_path_is_chosen_for_the_closure_extract_edge_really_builds():
     assert extraction._stream_fns(r.udf_network_fine.udf, other.extract_edge()[1]) is None
 
 
+def test_kind_table_of_the_one_classification():
+    """extraction._evaluator on every pair of callables the tests of this package hand to the routines: the kind (the table in the
+    module docstring), the network of the fused and closure kinds, and ``big`` - whether the two query routines drive the pair in
+    launches of _BIG points or in the caller's max_batch chunks.  The two owner rules disagree, both ways round: a closure over an
+    owner whose network is an instance attribute not called ``udf_network`` streams but gets max_batch chunks from the query routines; an
+    owner whose ``udf_network`` is a class attribute gets _BIG launches there but does not stream."""
+    from emap_amd import synthetic
+    kw = dict(d_in=3, d_out=1, d_hidden=128, n_layers=4, skip_in=(4,), multires=10, bias=0.5)
+    net, other = emap_amd.UDFNetwork(**kw), emap_amd.UDFNetwork(**kw)
+
+    def over_net(xyz):
+        return net.gradient(xyz) * 2.0
+
+    class ClassOwner:
+        udf_network = net
+
+    fine, named, by_class = types.SimpleNamespace(udf_network_fine=net), types.SimpleNamespace(udf_network=net), ClassOwner()
+    foreign = lambda x: x * 2
+    table = [  # func, func_grad, kind, big
+        (net.udf, net.gradient, "fused", True),
+        (net.udf, over_net, "closure", True),
+        (net.udf, net.udf, "closure", True),
+        (net.udf, synthetic.extract_edge_callables(fine)[1], "closure", False),
+        (net.udf, lambda x: fine.udf_network_fine.gradient(x), "closure", False),
+        (net.udf, lambda x: named.udf_network.gradient(x), "closure", True),
+        (net.udf, lambda x: by_class.udf_network.gradient(x), "point-wise", True),
+        (lambda p: net.udf(p), lambda p: net.gradient(p), "point-wise", True),
+        (lambda p, n=net: n.udf(p), lambda p, n=net: n.gradient(p), "point-wise", True),          # held as a default
+        (net.gradient, net.gradient, "point-wise", True),
+        (other.udf, over_net, "point-wise", True),                                                # a closure over ANOTHER network
+        (net.udf, lambda p: p, "opaque", False),
+        (net.udf, foreign, "opaque", False),
+        (foreign, foreign, "opaque", False),
+        (len, len, "opaque", False),
+    ]
+    for i, (func, func_grad, kind, big) in enumerate(table):
+        for streamed in (False, True):
+            ev = extraction._evaluator(func, func_grad, 4096, streamed=streamed)
+            assert ev.kind == kind and ev.streams == (kind in ("fused", "closure")), (i, ev.kind)
+            assert ev.net is (net if ev.streams else None), i
+            assert ev.big == (big or (streamed and ev.streams)), i         # the streamed routine drives what streams per _BIG
+            assert ev.chunk() == (extraction._BIG if ev.big else 4096) and ev.chunk(50) == (extraction._BIG if ev.big else 4096 * 50), i
+            assert ev.direct == (kind == "fused" or (streamed and kind == "closure")), i
+
+
+def test_evaluator_chunks_detaches_and_answers_an_empty_set_without_a_call(monkeypatch):
+    """The evaluator's chunk rule on CPU tensors, ``net.hip_udf`` replaced by a recording fake: _BIG and _MAX_BATCH are read when a
+    method is called; fused: one hip_udf per _BIG points (with_grad=True gives both); streamed closure: values from hip_udf, gradients
+    from the closure, per _BIG; point-wise: the callables per _BIG; opaque: per max_batch, x mult for a neighbourhood."""
+    kw = dict(d_in=3, d_out=1, d_hidden=128, n_layers=4, skip_in=(4,), multires=10, bias=0.5)
+    net, rec = emap_amd.UDFNetwork(**kw), []
+
+    def hip_udf(x, with_grad=False, precision=None):
+        rec.append(("hip_udf", len(x), with_grad))
+        return x[:, :1] * 2, (x * 3 if with_grad else None)
+    net.hip_udf = hip_udf
+    w = torch.ones(1, requires_grad=True)
+
+    def f(p):
+        rec.append(("func", len(p), None))
+        return (p[:, :1] * 2 * w,)
+
+    def g(p):
+        rec.append(("func_grad", len(p), None))
+        return (p * 3 * w).unsqueeze(1)                                            # (P, 1, 3), attached to a graph
+
+    owner = types.SimpleNamespace(udf_network_fine=net)
+    closure = lambda p: (g(p), owner)[0]
+    pointwise_f, pointwise_g = (lambda p, n=net: f(p)), (lambda p, n=net: g(p))
+    fused = extraction._evaluator(net.udf, net.gradient, 3)
+    streamed = extraction._evaluator(net.udf, closure, streamed=True)
+    query = extraction._evaluator(net.udf, closure, 3)
+    pointwise = extraction._evaluator(pointwise_f, pointwise_g, 3)
+    opaque, opaque_default = extraction._evaluator(f, g, 3), extraction._evaluator(f, g)
+    assert [e.kind for e in (fused, streamed, query, pointwise, opaque)] == ["fused", "closure", "closure", "point-wise", "opaque"]
+    monkeypatch.setattr(extraction, "_BIG", 8)                                     # after the evaluators were made
+    monkeypatch.setattr(extraction, "_MAX_BATCH", 4)
+    pts = torch.arange(19 * 3, dtype=torch.float32).reshape(19, 3)
+    per = lambda which, flag, c, n=19: [(which, min(c, n - h), flag) for h in range(0, n, c)]
+
+    def check(call, want_calls, *want):
+        rec.clear()
+        out = call()
+        out = out if isinstance(out, tuple) else (out,)
+        assert rec == want_calls, (rec, want_calls)
+        assert len(out) == len(want) and all(torch.equal(a, b) and not a.requires_grad for a, b in zip(out, want))
+
+    v, d = pts[:, :1] * 2, pts * 3
+    check(lambda: fused.values(pts), per("hip_udf", False, 8), v)
+    check(lambda: fused.gradients(pts, mult=5), per("hip_udf", True, 8), d)
+    check(lambda: fused.values_and_gradients(pts), per("hip_udf", True, 8), v, d)
+    check(lambda: streamed.values(pts), per("hip_udf", False, 8), v)
+    check(lambda: streamed.gradients(pts, mult=5), per("func_grad", None, 8), d)
+    check(lambda: streamed.values_and_gradients(pts), per("hip_udf", False, 8) + per("func_grad", None, 8), v, d)
+    check(lambda: query.gradients(pts), per("func_grad", None, 3), d)              # rule 1 does not see this owner: max_batch chunks
+    check(lambda: query.gradients(pts, mult=5), per("func_grad", None, 15), d)
+    check(lambda: pointwise.values(pts), per("func", None, 8), v)
+    check(lambda: pointwise.values_and_gradients(pts), per("func", None, 8) + per("func_grad", None, 8), v, d)
+    check(lambda: opaque.values(pts), per("func", None, 3), v)
+    check(lambda: opaque.gradients(pts), per("func_grad", None, 3), d)
+    check(lambda: opaque.gradients(pts, mult=5), per("func_grad", None, 15), d)
+    check(lambda: opaque.values_and_gradients(pts), per("func", None, 3) + per("func_grad", None, 3), v, d)
+    check(lambda: opaque_default.gradients(pts, mult=2), per("func_grad", None, 8), d)        # no max_batch given: _MAX_BATCH, as it is now
+    for ev in (fused, streamed, pointwise, opaque):
+        check(lambda: ev.values_and_gradients(pts[:0]), [], pts[:0, :1], pts[:0])
+        check(lambda: ev.gradients(pts[:0], mult=5), [], pts[:0])
+
+
 def test_dropin_aliases_the_point_cloud_routine_in_both_modules():
     """install() re-binds get_pointcloud_from_udf in src.edge_extraction.extract_pointcloud and, where the runner module holds
     the name by ``from ... import`` (runner_udf.py:16), there too; a runner module without the name is left alone."""
