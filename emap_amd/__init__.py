@@ -10,6 +10,11 @@ from .udf_renderer_blending import UDFRendererBlending, sample_pdf  # noqa: F401
 from .ray_sampler import DeviceRaySampler  # noqa: F401
 from .schedule import TrainSchedule  # noqa: F401
 from .monitor import TrainMonitor  # noqa: F401
+from . import edge_metrics  # noqa: F401
+from .edge_metrics import (nearest_neighbors, chamfer_distance, compute_chamfer_distance, compute_precision_recall_IOU,  # noqa: F401
+                           downsample_point_cloud_average, sample_segments, evaluate_edges, metrics_from_stats, f_score)
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
-           "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor"]
+           "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
+           "edge_metrics", "nearest_neighbors", "chamfer_distance", "compute_chamfer_distance", "compute_precision_recall_IOU",
+           "downsample_point_cloud_average", "sample_segments", "evaluate_edges", "metrics_from_stats", "f_score"]

@@ -543,6 +543,32 @@ int emap_compact_append(const float* df, const float* xyz, int64_t n, int64_t fi
 int emap_jitter_points(const float* x, const float* noise, int64_t n, int k, float delta, float* out, void* stream);
 int emap_shift_points(const float* x, const float* df, const float* normal, int64_t n, float* out, void* stream);
 
+/* ---- edge metrics: nearest neighbours and distance statistics (src/eval/eval_util.py:20-58 chamfer_distance, :138-191
+ *      compute_precision_recall_IOU; csrc/metrics.hip) -----------------------------------------------------------------------------
+ * Added functions only (no struct or signature of ABI 12 changes).  What the reference takes from point_cloud_utils' k-d tree on the CPU.
+ * emap_nearest_neighbors : for every row of q (n_q, 3) the row of r (n_r, 3) of least squared distance
+ *                            d2 = (dx*dx + dy*dy) + dz*dz,  dx = q.x - r.x, ...   every operation rounded to fp32, no FMA contraction;
+ *                          among equal d2 the lowest r index wins.  A pure function of the inputs - independent of tiling, of the split
+ *                          of r over workgroups and of launch order; a numpy fp32 expression reproduces it bit for bit.
+ *                          dist (n_q) = sqrt(d2) and idx (n_q, int64); either may be NULL.  A query whose every d2 is NaN gets idx = -1
+ *                          and dist = NaN; r rows with NaN never win; d2 = +inf is a legal minimum (dist = +inf, lowest index).
+ *                          q and r need 4-byte alignment only.  split = 0: the library chooses the number of r splits; split >= 1 forces
+ *                          it (clamped to the number of r tiles) - the result does not depend on it.
+ *                          workspace: emap_nn_workspace_bytes(n_q) bytes (the 64-bit keys), 8-byte aligned, used by this call only.
+ *                          Brute force: n_q * n_r distance evaluations, bound by the fp32 VALU rate.
+ * emap_dist_stats        : out[0] = the sum of dist[0 .. n) accumulated in fp64, out[1 + k] = the count of dist < thresholds_host[k]
+ *                          compared in fp32 (a NaN is never counted, and makes the sum NaN), k < n_thr <= 8: 1 + n_thr doubles on the
+ *                          device.  A fixed reduction order, no floating-point atomics: the same bits on every run.  thresholds_host is
+ *                          HOST memory, read during the call.
+ * Host checks, before any HIP call: n_q = 0 returns 0 and enqueues nothing; n = 0 enqueues the one launch that writes zeros (nothing when
+ * out is NULL).  EMAP_E_INVALID: a negative count, a NULL q / r / dist-of-stats / out with a positive count, n_r = 0 with n_q > 0,
+ * n_r > 2^31 - 1 (the key's index half), split < 0, n_thr outside 0..8, NULL thresholds_host with n_thr > 0.  EMAP_E_WORKSPACE: workspace
+ * NULL or smaller than the query's value. */
+int emap_nn_workspace_bytes(int64_t n_q, size_t* bytes);
+int emap_nearest_neighbors(const float* q, int64_t n_q, const float* r, int64_t n_r, int split, float* dist, int64_t* idx, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int emap_dist_stats(const float* dist, int64_t n, const float* thresholds_host, int n_thr, double* out, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * While enabled, emap_render_fwd / emap_render_bwd bracket their dominant kernels with hipEvents on the launch
  * stream; emap_profile_read[_kernel] (after the caller synchronised) returns the summed duration and the number of

@@ -16,7 +16,14 @@ the run goes on at the checkpoint's iteration, up to `--steps`.
 eager steps on the sampler's batches): the host reads the device once per report, every trajectory entry of the JSON line carries the
 monitor's rows of ALL the iterations since the previous report ("rows", one list per iteration in the order of "monitor"."columns": loss,
 psnr, udf_min, weight_sum, variance / beta / gamma, the learning rates, ...) and `--best PATH` is written by the runner's
-ckpt_best rule (runner_udf.py:243-244, :277-285) on the monitor's 500-iteration loss average (`--window`)."""
+ckpt_best rule (runner_udf.py:243-244, :277-285) on the monitor's 500-iteration loss average (`--window`).
+
+`--eval` measures the PRODUCT after training: the edge point cloud of `extraction.get_pointcloud_from_udf` on a 128^3 lattice with
+udf_threshold 0.04 (a converged 4000-step run leaves a mean UDF of ~0.024 ON the wire frame and ~0.21 away from it) and NO point shift
+(the reference's grid-stage normal is normalised per component, i.e. (+-1, +-1, +-1): with that floor on the wire a shift by df along it throws every
+point off the wire and the shift stage's filter keeps none - measured: 0 points), evaluated by `edge_metrics.evaluate_edges` against the
+wire frame sampled every 5 mm (`sample_segments(wireframe_segments())`): chamfer / acc / comp and precision / recall / F-score / IoU at
+5, 10 and 20 mm, added to the JSON line as "edge_metrics" (with the number of extracted points).  Without `--eval` the output is unchanged."""
 import argparse
 import json
 import math
@@ -29,7 +36,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import emap_amd  # noqa: E402
-from emap_amd import synthetic  # noqa: E402
+from emap_amd import edge_metrics, extraction, synthetic  # noqa: E402
 from emap_amd.parallel import Trainer  # noqa: E402
 from emap_amd.validation import render_image  # noqa: E402
 
@@ -48,6 +55,7 @@ def main():
     ap.add_argument("--monitor", action="store_true", help="train through parallel.fit with a TrainMonitor: one host read per report")
     ap.add_argument("--best", metavar="PATH", help="with --monitor: the checkpoint of the best window average of the edge loss")
     ap.add_argument("--window", type=int, default=500, help="with --monitor: iterations per loss average (the reference's 500)")
+    ap.add_argument("--eval", action="store_true", help="extract the edge point cloud after training and add edge_metrics.evaluate_edges to the JSON line")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -151,6 +159,11 @@ def main():
     psnr1 = view_psnr(held_out)
     psnr_train = view_psnr(1)
     u1 = udf_on_off()
+    edge_eval = {}
+    if a.eval:                     # the product's own measure: extracted edge points against the sampled wire frame
+        points, _ = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=128, udf_threshold=0.04, is_pointshift=False, device=dev)
+        gt = edge_metrics.sample_segments(synthetic.wireframe_segments())
+        edge_eval = {"edge_metrics": {"n_extracted": int(points.shape[0]), **(edge_metrics.evaluate_edges(points, gt, device=dev) if len(points) else {})}}
     print(json.dumps({
         "what": "training loop of runner_udf.py on a synthetic wire frame (13 segments, %d views %dx%d, view %d held out), HIP path only"
                 % (a.views, a.res, a.res, held_out),
@@ -158,6 +171,7 @@ def main():
         "held_out_view_psnr_db": {"before": psnr0[0], "after": psnr1[0]}, "train_view_psnr_db_after": psnr_train[0],
         "mean_udf_on_wireframe": {"before": u0[0], "after": u1[0]}, "mean_udf_away_from_it": {"before": u0[1], "after": u1[1]},
         "variance": float(devn.variance), "beta": float(bet.beta), "gamma": float(bet.gamma),
+        **edge_eval,
         **({"monitor": {"columns": list(emap_amd.TrainMonitor.COLUMNS), "record": mon.read(), "best_loss": fit_out.best_loss, "best_saved_at": fit_out.saved}} if mon is not None else {}),
         "trajectory": log}))
 
