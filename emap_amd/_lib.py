@@ -115,6 +115,9 @@ SYMBOLS = {
     "emap_nn_workspace_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
     "emap_nearest_neighbors": (_RC, [_P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "emap_dist_stats": (_RC, [_P, C.c_int64, C.POINTER(C.c_float), C.c_int, _P, _P]),
+    "emap_edge_sample_counts": (_RC, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
+    "emap_edge_sample_fill": (_RC, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int64, _P]),
+    "emap_edge_sample_fill_tangents": (_RC, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "emap_sample_pdf": (_RC, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_sample_pdf_u": (_RC, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "emap_upsample_step": (_RC, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_float, C.c_float, C.c_float,

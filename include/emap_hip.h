@@ -569,6 +569,41 @@ int emap_nearest_neighbors(const float* q, int64_t n_q, const float* r, int64_t 
                            size_t workspace_bytes, void* stream);
 int emap_dist_stats(const float* dist, int64_t n, const float* thresholds_host, int n_thr, double* out, void* stream);
 
+/* ---- points on fitted parametric edges (src/eval/eval_util.py:90-135 bezier_curve_length, :300-415 get_pred_points_and_directions;
+ *      src/edge_extraction/extract_parametric_edge.py:65-134 process_geometry_data; csrc/parametric.hip) -------------------------------
+ * Added functions only (no struct or signature of ABI 12 changes).  All arrays are fp64 on the device, contiguous; an edge set is C cubic
+ * Beziers, curves (C, 4, 3), followed by L segments, lines (L, 2, 3): edge e < C is curve e, edge C + j is line j.
+ * emap_edge_sample_counts : lengths[e] and counts[e] = (int64) floor(lengths[e] / resolution) of the C + L edges.  A curve's length is the
+ *                           reference's nested composite Simpson rule with num_samples sub-intervals of num_samples steps each
+ *                           (a = s / ns, b = (s + 1) / ns, h = (b - a) / ns; odd points weighted 4, the even points 2 <= i < ns - 1
+ *                           weighted 2, both ends added, times h / 3), the sub-intervals added in index order, over the derivative
+ *                           3 (1-t)^2 (P1-P0) + 6 (1-t) t (P2-P1) + 3 t^2 (P3-P2); a line's length is sqrt(dx^2 + dy^2 + dz^2).  No FMA
+ *                           contraction, IEEE sqrt and division, no atomics: a pure function of the inputs, the same bits on every run.
+ *                           A length that is not finite, or a quotient of 9e18 or more, gives counts[e] = -1.
+ * emap_edge_sample_fill   : offsets (C + L + 1, int64, device) partition [0, n): edge e owns rows offsets[e] .. offsets[e + 1) of points
+ *                           (n, 3), directions (n, 3; may be NULL) and edge_id (n, int32; may be NULL; receives e).  With num rows the
+ *                           parameters are numpy.linspace(0, 1, num): t_i = i * (1 / (num - 1)), the last exactly 1, num = 1 gives t = 0,
+ *                           num = 0 writes nothing.  Curve point [t^3, t^2, t, 1] . M . P (the Bernstein matrix); line point
+ *                           p0 + t (p1 - p0).  directions reproduce what get_pred_points_and_directions returns: for a line
+ *                           (p1 - p0) / (|p1 - p0| + 1e-6); for a curve v / |v| with no epsilon (v = 0 gives NaN) and, in the
+ *                           reference's operation order, v = A (3 t^2) + B (2 t) + C with A = -3 P0 + 9 P1 - 9 P2 + 3 P3, B = 6 P0 -
+ *                           12 P1 + 6 P2, C = -3 P0 + 3 P1.  A and B already hold the factors 3 and 2, so v = 9 t^2 a3 + 4 t a2 + a1 in
+ *                           the curve's power coefficients: this is the reference's formula and NOT the derivative 3 t^2 a3 + 2 t a2 + a1 -
+ *                           for t > 0 directions are not the curve's tangents.  An edge whose offsets are not
+ *                           0 <= offsets[e] <= offsets[e + 1] <= n writes nothing.
+ * emap_edge_sample_fill_tangents : the same launch with one more output, tangents (n, 3; may be NULL): the unit tangent, for a curve the
+ *                           derivative of emap_edge_sample_counts over its norm with no epsilon (NaN where it vanishes: t = 0 with P0 = P1,
+ *                           t = 1 with P2 = P3), for a line (p1 - p0) / |p1 - p0|.
+ * Host checks, before any HIP call.  EMAP_E_INVALID: C < 0 or L < 0, C + L > 2^31 - 1, NULL curves with C > 0 or NULL lines with L > 0;
+ * counts: resolution not finite or <= 0, num_samples outside 1..1024, NULL lengths / counts; fill (both forms): n < 0 or n > 2^31 - 1, NULL offsets /
+ * points.  C + L = 0 (and, for fill, n = 0) returns 0 and enqueues nothing. */
+int emap_edge_sample_counts(const double* curves, int C, const double* lines, int L, double resolution, int num_samples, double* lengths,
+                            int64_t* counts, void* stream);
+int emap_edge_sample_fill(const double* curves, int C, const double* lines, int L, const int64_t* offsets, double* points, double* directions,
+                          int32_t* edge_id, int64_t n, void* stream);
+int emap_edge_sample_fill_tangents(const double* curves, int C, const double* lines, int L, const int64_t* offsets, double* points,
+                                   double* directions, double* tangents, int32_t* edge_id, int64_t n, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------------
  * While enabled, emap_render_fwd / emap_render_bwd bracket their dominant kernels with hipEvents on the launch
  * stream; emap_profile_read[_kernel] (after the caller synchronised) returns the summed duration and the number of
