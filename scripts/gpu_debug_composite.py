@@ -2,15 +2,15 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import torch, torch.nn.functional as F
 from conftest import load_golden, t, net_state
-import test_gpu_parity as T
+from gpu_helpers import mk, mk_renderer, _render_core_on_z
 from oracle import emap_oracle as O
 case = "c64_64_4"
 g = load_golden("g5_render_" + case)
 ns, ni, steps = [int(v) for v in g["cfg"]]
-net, _, _ = T.mk(T.G5[case], "f16x3")
-r = T.mk_renderer(net, ns, ni, steps)
+net, _, _ = mk("d8w256L10", "f16x3")      # the network of that golden
+r = mk_renderer(net, ns, ni, steps)
 z = t(g[f"z_after_step{steps - 1}"])
-out = T._render_core_on_z(net, r, g, z, 1.0, 0.9)
+out = _render_core_on_z(net, r, g, z, 1.0, 0.9)
 ref_w = t(g["out.weights"]); w = out["weights"].cpu()
 d = (w - ref_w).abs(); i = int(d.argmax()); ray, s = divmod(i, w.shape[1])
 print("worst weights diff", float(d.max()), "at ray", ray, "sample", s, "ours", float(w[ray, s]), "ref", float(ref_w[ray, s]), "max ref", float(ref_w.max()))

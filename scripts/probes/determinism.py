@@ -7,7 +7,7 @@ import torch
 prec, what = sys.argv[1], sys.argv[2]
 P = int(sys.argv[3]) if len(sys.argv) > 3 else 524288
 reps = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-from test_gpu_parity import mk
+from gpu_helpers import mk
 net, state, cfg = mk("d8w256L10", prec)
 gen = torch.Generator().manual_seed(5)
 x = (torch.rand(P, 3, generator=gen) * 2 - 1).cuda()

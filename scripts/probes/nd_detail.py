@@ -3,7 +3,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
 import torch
-from test_gpu_parity import mk
+from gpu_helpers import mk
 prec = sys.argv[1] if len(sys.argv) > 1 else "bf16x3"
 P = int(sys.argv[2]) if len(sys.argv) > 2 else 131072
 from emap_amd import _lib

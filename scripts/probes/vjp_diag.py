@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests"))
 import torch
 from test_gpu_backward import _hip_vjp, _mirror_param_grads
-from test_gpu_parity import mk
+from gpu_helpers import mk
 
 for name in ("d4w128L10", "d8w256L10"):
     net, state, cfg = mk(name, "f16x3")

@@ -20,7 +20,7 @@ from emap_amd import _lib
 from emap_amd.backward import ParamLayout
 from oracle import emap_oracle as O
 from oracle import vjp_mirror as M
-from test_gpu_parity import mk, mk_renderer, rel, DEV, _render_core_on_z
+from gpu_helpers import mk, mk_renderer, rel, DEV, _render_core_on_z
 
 pytestmark = pytest.mark.gpu
 

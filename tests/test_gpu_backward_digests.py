@@ -16,7 +16,7 @@ import torch
 from conftest import load_golden, t
 from emap_amd import _lib
 from emap_amd.backward import ParamLayout
-from test_gpu_parity import mk, mk_renderer, DEV, _render_core_on_z
+from gpu_helpers import mk, mk_renderer, DEV, _render_core_on_z
 from test_gpu_render_modes import _setup, _train_golden
 
 pytestmark = pytest.mark.gpu

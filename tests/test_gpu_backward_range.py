@@ -40,7 +40,7 @@ import torch
 import emap_amd
 from emap_amd import _lib, synthetic
 from test_gpu_backward import _hip_vjp, _mirror_param_grads, _cmp, TOL
-from test_gpu_parity import mk, mk_renderer, DEV
+from gpu_helpers import mk, mk_renderer, DEV
 
 pytestmark = pytest.mark.gpu
 

@@ -7,7 +7,7 @@ import torch
 
 from emap_amd import synthetic
 from emap_amd.parallel import Trainer
-from test_gpu_parity import mk, mk_renderer, DEV
+from gpu_helpers import mk, mk_renderer, DEV
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 from emap_amd import extraction, synthetic
-from test_gpu_parity import mk, DEV
+from gpu_helpers import mk, DEV
 
 pytestmark = pytest.mark.gpu
 

@@ -23,7 +23,7 @@ import pytest
 import torch
 
 from emap_amd import extraction
-from test_gpu_parity import mk, DEV
+from gpu_helpers import mk, DEV
 from test_gpu_extraction_digests import callables
 
 pytestmark = pytest.mark.gpu

@@ -68,7 +68,7 @@ from oracle import emap_oracle as O
 from oracle import vjp_mirror as M
 import offinit_states as S
 from test_gpu_backward import _hip_vjp, _mirror_param_grads, _cmp, TOL
-from test_gpu_parity import mk_renderer, rel, DEV
+from gpu_helpers import mk_renderer, rel, DEV
 
 pytestmark = pytest.mark.gpu
 

@@ -20,29 +20,9 @@ from conftest import load_golden, t, net_state, NETS
 import emap_amd
 from emap_amd import _lib, synthetic
 from oracle import emap_oracle as O
+from gpu_helpers import DEV, rel, mk, mk_renderer, _render_core_on_z, _well_conditioned, _fused_vs_chain, CHAIN_BOUND, MOVED_BOUND
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def rel(a, b):
-    a = a.detach().cpu().double().reshape(-1)
-    b = b.detach().cpu().double().reshape(-1)
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
-
-
-def mk(name, precision="f16x3", scale=1.0):
-    kw, state = net_state(name)
-    net = emap_amd.UDFNetwork(scale=scale, precision=precision, **kw)
-    net.load_state_dict(state)
-    cfg = O.UDFConfig(d_hidden=kw["d_hidden"], n_layers=kw["n_layers"], multires=kw["multires"], scale=scale)
-    return net.to(DEV), state, cfg
-
-
-def mk_renderer(net, ns, ni, steps):
-    dev = emap_amd.SingleVarianceNetwork(0.3).to(DEV)
-    bet = emap_amd.BetaNetwork(0.5, 0.3, 0.3, 5e-5, True, True, False).to(DEV)
-    return emap_amd.UDFRendererBlending(None, net, dev, bet, ns, ni, 0, steps, 1.0, device=DEV)
 
 
 def test_native_library_is_what_runs():
@@ -371,17 +351,6 @@ def test_upsample_and_merge_bit_exact_vs_reference():
         z, udf = t(g[f"step{i}.z_out"]).to(DEV), t(g[f"step{i}.udf_out"]).to(DEV)
 
 
-def _well_conditioned(z, weights, inds, m):
-    """samples whose inverse-CDF lerp is well conditioned: the pdf mass of their interval is >= 1e-3 (sample_pdf :92-96 divides
-    by it; in empty intervals the reference's own result depends on the last ulp of its cumsum)"""
-    w = weights + 1e-5
-    pdf = w / w.sum(-1, keepdim=True)
-    below = (inds - 1).clamp(min=0)
-    above = inds.clamp(max=z.shape[1] - 1)
-    mass = torch.where(above > below, torch.gather(pdf, 1, below.clamp(max=pdf.shape[1] - 1)), torch.zeros_like(z[:, :m]))
-    return mass >= 1e-3
-
-
 @pytest.mark.parametrize("case", ["c64_64_4", "c64_50_5", "c32_32_4_small"])
 def test_upsampling_steps_and_chain_vs_reference(case):
     """Every one of the K up-sampling steps through the HIP kernels, for the full-size golden renders (G4 pins two steps of a
@@ -482,52 +451,11 @@ def test_merge_ties_are_stable():
 
 
 # ---------------------------------------------------------------------------------------- render_core on fixed z
-# measured on MI355X (round 2) + margin: fraction of rays with any sample moved by > 1e-3 w.r.t. the reference's z_vals (the
-# sampler is discontinuous in its inputs; the per-step kernels are bit-exact on reference inputs, see the chain test), and the
-# resulting relative difference of the batch-wide gradient_error
-# (measured 0.062 / 0.031 / 0.25 / 0.0 and 1.9e-3 / 2.0e-4 / 5.9e-3 / 0)
-MOVED_BOUND = {"c64_50_5": 0.13, "c64_64_4": 0.10, "c32_32_4_small": 0.35, "c64_64_4_L6": 0.07}
+# the relative difference of the batch-wide gradient_error that the rays with moved samples (gpu_helpers.MOVED_BOUND) bring about:
+# measured on MI355X (round 2) + margin (measured 1.9e-3 / 2.0e-4 / 5.9e-3 / 0)
 GE_BOUND = {"c64_50_5": 4e-3, "c64_64_4": 1e-3, "c32_32_4_small": 1.2e-2, "c64_64_4_L6": 1e-3}
-# up-sampling steps on reference inputs (max over steps): (index mismatch fraction, fraction of samples off by > 2e-6, the same among
-# the well-conditioned samples, fraction of rays whose chained final z_vals equal the golden's) - measured on MI355X (round 2) + margin
-# measured: indices 0 / 0 / 0 mismatches; samples 0 / 0 / 3.5 % (one |p| < 1 decision of the d4 case flips); chained rays equal to the
-# golden 97 / 94 / 81 % - the CPU oracle on the same host reaches 97 / 94 / 62 % against the golden recorded on another CPU
-CHAIN_BOUND = {"c64_64_4": (0.002, 0.01, 0.01, 0.90), "c64_50_5": (0.002, 0.01, 0.01, 0.85), "c32_32_4_small": (0.002, 0.07, 0.07, 0.70)}
 G5 = {"c64_50_5": "d8w256L10", "c64_64_4": "d8w256L10", "c32_32_4_small": "d4w128L10", "c64_64_4_L6": "d8w256L6"}
 PER_SAMPLE = ["udf", "weights", "gradients", "gradients_flip", "inside_sphere", "gradient_mag", "mid_z_vals", "dists"]
-
-
-def _render_core_on_z(net, r, g, z, car, fs, bg=None):
-    """MLP value+grad at the reference's z_vals + emap_composite_fwd_p: render_core (:418-677) through the C ABI."""
-    L = _lib.lib()
-    ro, rd, near, far, ds = [t(g[k]).to(DEV) for k in ("rays_o", "rays_d", "near", "far", "depth_scale")]
-    N, S = z.shape
-    sd = ((far - near) / r.n_samples).mean().reshape(1)
-    z = z.to(DEV).contiguous()
-    dists = torch.cat([z[:, 1:] - z[:, :-1], sd.expand(N, 1)], -1)
-    mid = z + dists * 0.5
-    pts = (ro[:, None, :] + rd[:, None, :] * mid[..., None]).reshape(-1, 3)
-    with torch.no_grad():
-        udf, grad = net.hip_udf(pts, with_grad=True)
-    p = r._params(N, car, fs, bg)
-    names = ["weights", "alpha", "mid_z", "dists", "inside_sphere", "gradient_mag"]
-    bufs = {k: torch.empty(N, S, device=DEV) for k in names}
-    bufs.update(gradients_flip=torch.empty(N, S, 3, device=DEV), edge=torch.empty(N, 1, device=DEV), depth=torch.empty(N, 1, device=DEV),
-                weight_sum=torch.empty(N, 1, device=DEV), normals=torch.empty(N, 3, device=DEV), scalars=torch.zeros(16, device=DEV))
-    co = _lib.CompositeOut()
-    for k, v in bufs.items():
-        setattr(co, k, v.data_ptr())
-    partials = torch.empty(N, 8, device=DEV)
-    err = torch.zeros(1, dtype=torch.int32, device=DEV)
-    ds_flat = ds.reshape(-1).contiguous()
-    _lib.check(L.emap_composite_fwd_p(_lib.ptr(ro), _lib.ptr(rd), _lib.ptr(z), _lib.ptr(udf), _lib.ptr(grad), _lib.ptr(ds_flat),
-                                      N, S, _lib.ptr(sd), C.byref(p), C.byref(co), _lib.ptr(partials), _lib.ptr(err), _lib.stream_ptr()))
-    torch.cuda.synchronize()
-    assert int(err.item()) == 0
-    out = dict(bufs)
-    out.update(udf=udf.view(N, S), gradients=grad.view(N, S, 3), mid_z_vals=bufs["mid_z"], gradient_error=bufs["scalars"][0],
-               gradient_error_near_surface=bufs["scalars"][1])
-    return out
 
 
 @pytest.mark.parametrize("case", list(G5))
@@ -641,34 +569,6 @@ def test_fused_importance_sampling_equals_the_launch_chain_bit_for_bit(netname, 
 @pytest.mark.parametrize("prec", ["f16x3m", "f16x3e", "bf16x3", "f16", "bf16"])
 def test_fused_importance_sampling_in_every_precision_mode(prec):
     _fused_vs_chain("d8w256L10", 512, prec)
-
-
-def _fused_vs_chain(netname, N, prec):
-    """ABI v8: importance_sample (udf_renderer_blending.py:802-841) as ONE launch - the sampler steps run inside the workgroups of the narrow MLP
-    passes, the ray's lists stay in LDS (udf_mlp_kernel.inc, IS) - against the chain of 2 K - 1 launches it replaces
-    (emap_set_fused_sampling(0)): z_vals and every rendered quantity identical bit for bit, for every workgroup geometry the launcher picks
-    (2 rays x 8 waves, 2 x 4, 1 x 8 / 1 x 4, odd ray counts), with and without the per-ray jitter."""
-    from emap_amd import synthetic
-    net, _, _ = mk(netname, prec)
-    r = mk_renderer(net, 64, 64, 4)
-    ro, rd, near, far, ds = [v.to(DEV) for v in synthetic.make_rays(N, seed=5)]
-    tr = synthetic.make_t_rand(N).to(DEV)
-    L = _lib.lib()
-    outs = {}
-    try:
-        for fused in (2, 1, 0):       # 2: the fused kernel whatever the size rule says (round 6: the rule hands 768 ... 1024 rays at m = 16 to the chain), 1: the rule's pick
-            L.emap_set_fused_sampling(fused)
-            with torch.no_grad():
-                o1 = r.render(ro, rd, near, far, ds, cos_anneal_ratio=1.0, flip_saturation=0.9, t_rand=tr)
-                o2 = r.render(ro, rd, near, far, ds, cos_anneal_ratio=1.0, perturb_overwrite=0, flip_saturation=0.9)
-            torch.cuda.synchronize()
-            r.check_errors()
-            outs[fused] = {tag + k: v.clone() for tag, o in (("jitter.", o1), ("plain.", o2)) for k, v in o.items() if isinstance(v, torch.Tensor)}
-    finally:
-        L.emap_set_fused_sampling(1)
-    assert set(outs[0]) == set(outs[1]) == set(outs[2]) and "jitter.z_vals" in outs[1] and "plain.z_vals" in outs[1]
-    for k in outs[1]:
-        assert torch.equal(outs[1][k], outs[0][k]) and torch.equal(outs[2][k], outs[0][k]), k
 
 
 def test_perturb_path_and_float_near_far():

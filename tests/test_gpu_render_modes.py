@@ -10,28 +10,14 @@ import torch
 from conftest import load_golden, t
 import emap_amd
 from emap_amd import _lib, synthetic
-from test_gpu_parity import mk, DEV, _render_core_on_z, _well_conditioned, CHAIN_BOUND, MOVED_BOUND
+from gpu_helpers import mk, mk_renderer, DEV, _render_core_on_z, _well_conditioned, CHAIN_BOUND, MOVED_BOUND
+from gpu_helpers import rel_floored as rel          # every rel() of this file has the 1e-4 floor
 from test_gpu_backward import _cmp
 
 pytestmark = pytest.mark.gpu
 
 CASES = {"c64_64_4": "d8w256L10", "c32_32_4_small": "d4w128L10"}
 MODES = {"plain": ("g16_plain_", dict(use_unbias_render=False)), "normcos": ("g17_normcos_", dict(use_norm_grad_for_cosine=True))}
-
-
-def rel(a, b):
-    """max-normalised difference.  The floor of 1e-4 stands for the fp32 noise of quantities that are all near zero: the d8 network's
-    plain-mode edge is 0 and its normalised-cosine weights sit at ~1e-5 (the + 1e-5 of sample_pdf's scale), where |g| from sqrt vs
-    torch.linalg.norm alone moves them by an ulp."""
-    a = a.detach().cpu().double().reshape(-1)
-    b = b.detach().cpu().double().reshape(-1)
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-4))
-
-
-def mk_renderer(net, ns, ni, steps, **mode):
-    dev = emap_amd.SingleVarianceNetwork(0.3).to(DEV)
-    bet = emap_amd.BetaNetwork(0.5, 0.3, 0.3, 5e-5, True, True, False).to(DEV)
-    return emap_amd.UDFRendererBlending(None, net, dev, bet, ns, ni, 0, steps, 1.0, device=DEV, **mode)
 
 
 def _setup(mname, case, prec="f16x3"):

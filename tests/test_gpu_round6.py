@@ -1,60 +1,25 @@
-"""GPU tests added in round 6 (-m gpu), all through the C ABI / the drop-in classes."""
-import copy
-
-import numpy as np
+"""GPU tests (-m gpu) first written in round 6 that still await a place by subject (the optimizer, f16x3e and training-run tests of that
+round are in test_gpu_adam.py, test_gpu_precision_modes.py and test_gpu_training_runs.py), through the C ABI / the drop-in classes:
+the value launches' tile-geometry table, fused importance sampling at m != 16 and from 2048 rays, compositing inside the value + grad_x
+kernel, a whole image in one call, f16x3e's weight gradients on the g6 cases, and the reverse sweep's fused output layer."""
 import pytest
 import torch
 
+from conftest import load_golden, t
 import emap_amd
 from emap_amd import _lib, synthetic
-from emap_amd.parallel import Trainer, FusedAdam
+from gpu_helpers import DEV, rel, mk, mk_renderer, _fused_vs_chain
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
-# ------------------------------------------------------------------------------------------------ FusedAdam after a resume
-def test_fused_adam_follows_lr_changes_after_load_state_dict():
-    """ADVICE r5 (high).  The resume path of the drop-in (runner_udf.py:260-273: load_checkpoint -> optimizer.load_state_dict, then
-    update_learning_rate writes param_groups[i]['lr'] every step): load a checkpoint, CHANGE the learning rates, step - equal to
-    torch.optim.Adam doing the same."""
-    from test_gpu_round5 import _groups, _clone, _mk, _steps
-    gen = torch.Generator().manual_seed(31)
-    geo_a, tail_a = _groups(gen)
-    geo_b, tail_b = _clone(geo_a), _clone(tail_a)
-    oa, ob = _mk(FusedAdam, geo_a, tail_a), _mk(torch.optim.Adam, geo_b, tail_b)
-    _steps([(oa, geo_a + tail_a), (ob, geo_b + tail_b)], torch.Generator().manual_seed(32), 3)
-    sd = copy.deepcopy(oa.state_dict())
-    geo_c, tail_c = _clone(geo_a), _clone(tail_a)
-    oc = _mk(FusedAdam, geo_c, tail_c)
-    oc.load_state_dict(sd)
-    for s in range(3):
-        for opt in (oc, ob):                       # the runner's scheduler: geo group its own lr, every other group the common one
-            for i, g in enumerate(opt.param_groups):
-                g["lr"] = (2e-3 if i == 0 else 7e-3) * (0.5 ** s)
-        _steps([(oc, geo_c + tail_c), (ob, geo_b + tail_b)], torch.Generator().manual_seed(40 + s), 1, s0=3 + s)
-    for pc, pb in zip(geo_c + tail_c, geo_b + tail_b):
-        assert torch.allclose(pc, pb, rtol=3e-6, atol=1e-7), (pc, pb)
-    # and from_adam on an Adam that has already stepped (it goes through load_state_dict)
-    geo_d, tail_d = _clone(geo_b), _clone(tail_b)
-    od_ref = _mk(torch.optim.Adam, geo_d, tail_d)
-    od_ref.load_state_dict(copy.deepcopy(ob.state_dict()))
-    od = FusedAdam.from_adam(od_ref)
-    for opt in (od, ob):
-        for i, g in enumerate(opt.param_groups):
-            g["lr"] = 3e-3 if i == 0 else 4e-3
-    _steps([(od, geo_d + tail_d), (ob, geo_b + tail_b)], torch.Generator().manual_seed(50), 2, s0=6)
-    for pd_, pb in zip(geo_d + tail_d, geo_b + tail_b):
-        assert torch.allclose(pd_, pb, rtol=3e-6, atol=1e-7)
-
-
+# ------------------------------------------------------------------------------------------------ the value launches' tile geometry
 @pytest.mark.parametrize("prec", ["f16x3", "bf16x3"])
 def test_value_launch_geometry_table_is_bit_identical_across_its_ranges(prec):
     """Round 6: the value launches pick their tile geometry from a measured table (udf_mlp_kernel.inc:launch_mlp_fs2_mode: 16- / 32- / 48- / 64-point tiles
     as one 8-wave workgroup per CU, 48- / 64-point tiles as two 4-wave workgroups per CU, the 8-wave forms again in three rounds).  Every geometry sums
     in the same K order: a point's udf is the same bit for bit whichever launch size carries it - both sides of every boundary of the table, ragged
     last tiles included."""
-    from test_gpu_parity import mk
     from oracle import emap_oracle as O
     net, state, cfg = mk("d8w256L10", prec)
     gen = torch.Generator().manual_seed(123)
@@ -73,34 +38,6 @@ def test_value_launch_geometry_table_is_bit_identical_across_its_ranges(prec):
 
 
 # ------------------------------------------------------------------------------------------------ fused importance sampling, widened
-def _fused_vs_chain(netname, N, prec, n_samples, n_importance, steps, fused_mode=1):
-    """importance_sample (udf_renderer_blending.py:802-841) as ONE launch against the chain of 2 K - 1 launches: every rendered tensor
-    identical bit for bit (same device code, same arithmetic; tests/test_gpu_parity.py has the m = 16 shapes of rounds 5)."""
-    from test_gpu_parity import mk, mk_renderer
-    net, _, _ = mk(netname, prec)
-    r = mk_renderer(net, n_samples, n_importance, steps)
-    ro, rd, near, far, ds = [v.to(DEV) for v in synthetic.make_rays(N, seed=5)]
-    tr = synthetic.make_t_rand(N).to(DEV)
-    L = _lib.lib()
-    outs = {}
-    try:
-        for fused in (fused_mode, 0):
-            L.emap_set_fused_sampling(fused)
-            with torch.no_grad():
-                o1 = r.render(ro, rd, near, far, ds, cos_anneal_ratio=1.0, flip_saturation=0.9, t_rand=tr)
-                o2 = r.render(ro, rd, near, far, ds, cos_anneal_ratio=1.0, perturb_overwrite=0, flip_saturation=0.9)
-            torch.cuda.synchronize()
-            r.check_errors()
-            outs[fused] = {tag + k: v.clone() for tag, o in (("jitter.", o1), ("plain.", o2)) for k, v in o.items() if isinstance(v, torch.Tensor)}
-    finally:
-        L.emap_set_fused_sampling(1)
-    a, b = outs[fused_mode], outs[0]
-    assert set(a) == set(b) and "jitter.z_vals" in a
-    assert a["jitter.z_vals"].shape == (N, n_samples + n_importance)
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
-
-
 @pytest.mark.parametrize("netname,N,ns,ni,K", [
     ("d8w256L10", 1024, 64, 50, 5),      # confs/ABC.conf:31,108-111 - the reference's own default launch shape: m = 10 new samples per step
     ("d8w256L10", 512, 64, 50, 5), ("d8w256L10", 77, 64, 50, 5), ("d8w256L10", 1, 64, 50, 5),
@@ -162,7 +99,6 @@ def test_fused_compositing_equals_the_separate_launch_bit_for_bit(netname, N, ns
     udf_mlp_rev32_kernel<..., COMP> - the workgroup that completes a ray composites it - against the separate composite_kernel launch
     (emap_set_fused_composite(0)): every entry of the render dict identical bit for bit, also when tiles straddle rays, when a tile holds
     several rays, and over several rounds of workgroups."""
-    from test_gpu_parity import mk, mk_renderer
     net, _, _ = mk(netname, "f16x3")
     r = mk_renderer(net, ns, ni, K)
     ro, rd, near, far, ds = [v.to(DEV) for v in synthetic.make_rays(N, seed=9)]
@@ -181,7 +117,6 @@ def test_fused_compositing_equals_the_separate_launch_bit_for_bit(netname, N, ns
 
 @pytest.mark.parametrize("prec", ["f16x3e", "f16x3m", "bf16x3", "f16", "bf16"])
 def test_fused_compositing_in_every_precision_mode(prec):
-    from test_gpu_parity import mk, mk_renderer
     net, _, _ = mk("d8w256L10", prec)
     r = mk_renderer(net, 64, 64, 4)
     N = 512
@@ -194,7 +129,6 @@ def test_fused_compositing_in_every_precision_mode(prec):
 def test_fused_compositing_from_a_replayed_graph_and_back_to_back():
     """The arrival counters are cleared by the render's FIRST launch: 40 replays of a captured render and 40 eager renders back to back
     (no synchronisation between them) give the same dict every time."""
-    from test_gpu_parity import mk, mk_renderer
     net, _, _ = mk("d8w256L10", "f16x3")
     r = mk_renderer(net, 64, 64, 4)
     N = 512
@@ -219,7 +153,6 @@ def test_fused_compositing_from_a_replayed_graph_and_back_to_back():
 
 
 def test_training_forward_uses_the_fused_tail_and_the_gradients_do_not_change():
-    from test_gpu_parity import mk, mk_renderer
     L = _lib.lib()
     res = {}
     try:
@@ -246,7 +179,6 @@ def test_whole_image_in_one_call_equals_the_chunked_schedules():
     """render_image's default (round 6): ONE emap_render_fwd call over all H*W rays (runner_udf.py:298-327 loops over batch_size chunks).
     Rays are independent: the same image as 1024-ray launches bit for bit (the same kernels run at both sizes: >= 10 240 points), and as
     the reference's 512-ray schedule to the render tolerances."""
-    from test_gpu_parity import mk, mk_renderer, rel, t
     from emap_amd.validation import render_image
     net, _, _ = mk("d8w256L10", "f16x3")
     r = mk_renderer(net, 64, 64, 4)
@@ -268,39 +200,6 @@ def test_whole_image_in_one_call_equals_the_chunked_schedules():
         assert rel(imgs[None][k], imgs[512][k]) <= 5e-4, k
 
 
-# ------------------------------------------------------------------------------------------------ f16x3e: 24-bit sigma' stash
-def test_mode_f16x3e_sits_on_the_fp32_floor_element_wise():
-    """the unorm16 sigma' stash was what separated the reverse sweep from fp32 autograd element-wise (p99.9 of
-    grad_x 5.7e-3 against 6.6e-4 for the reference's own fp32 arithmetic, profiles/r05_elementwise_attribution.txt).  In precision mode
-    f16x3e sigma' now travels as 24-bit fixed point (udf_mlp_rev32.inc, SG24: +50 % stash bytes in that mode only).  Against the fp64 oracle
-    on 8192 random points: max-normalised <= 3e-6 (round 5: 1.3e-5), element-wise p99.9 <= 1.2e-3 (measured 5.9e-4; round 5: 6.7e-3) - the
-    forward-mode kernel (no stash at all) gives 7.4e-7 / 4.1e-4.  And on the reference's own recorded points (g2)."""
-    from conftest import net_state, load_golden
-    from oracle import emap_oracle as O
-    from test_gpu_round5 import _rel, _p999
-    kw, state = net_state("d8w256L10")
-    cfg = O.UDFConfig(d_hidden=256, n_layers=8, multires=10)
-    x = torch.rand(65536, 3, generator=torch.Generator().manual_seed(9)) * 2 - 1
-    uo, go = O.udf_value_and_grad({k: v.double() for k, v in state.items()}, cfg, x[:8192].double())
-    n = emap_amd.UDFNetwork(precision="f16x3e", **kw)
-    n.load_state_dict(state)
-    n = n.to(DEV)
-    with torch.no_grad():
-        u, g = n.hip_udf(x.to(DEV), with_grad=True)                 # 65 536 points: the reverse sweep
-        u1, g1 = n.hip_udf(x.to(DEV), with_grad=True)
-    assert torch.equal(u, u1) and torch.equal(g, g1)
-    e_u, e_g, p999 = _rel(u[:8192], uo), _rel(g[:8192], go), _p999(g[:8192], go)
-    print(f"f16x3e vs fp64 oracle: udf {e_u:.2e}, grad_x max-normalised {e_g:.2e}, element-wise p99.9 {p999:.2e}")
-    assert e_u <= 2e-6 and e_g <= 3e-6 and p999 <= 1.2e-3
-    gold = load_golden("g2_mlp")
-    xg = torch.from_numpy(gold["x"])
-    reps = (10240 + xg.shape[0] - 1) // xg.shape[0]                 # enough points for the reverse-sweep kernel
-    with torch.no_grad():
-        ug, gg = n.hip_udf(xg.repeat(reps, 1).to(DEV), with_grad=True)
-    assert _rel(gg[:xg.shape[0]], torch.from_numpy(gold["d8w256L10.grad"]).reshape(-1, 3)) <= 6e-6
-    assert _rel(ug[:xg.shape[0]], torch.from_numpy(gold["d8w256L10.udf"])) <= 2e-6
-
-
 # ------------------------------------------------------------------------------------------------ f16x3e: precise weight gradients
 @pytest.mark.parametrize("ci", [0, 1, 2, 3])
 def test_f16x3e_parameter_gradients_meet_1e4_on_the_reference_samples(ci):
@@ -308,9 +207,7 @@ def test_f16x3e_parameter_gradients_meet_1e4_on_the_reference_samples(ci):
     operands; gate 1e-3).  Precision mode f16x3e (no MX fp6 anywhere, 24-bit sigma') now also stashes the lo parts of both operand sets and
     forms dW = Z_hi A_hi^T + (Z_hi A_lo^T + Z_lo A_hi^T) / 2^11 in three passes of the weight-gradient kernel: north_star's 1e-4 on all 27
     (15) tensors of the four g6 cases recorded from the reference's own loss.backward()."""
-    from conftest import load_golden
     from test_gpu_backward import _render_bwd_on_reference_samples, _cmp
-    from test_gpu_parity import t
     g = load_golden(f"g6_training_{ci}")
     loss, got, extra = _render_bwd_on_reference_samples(g, "f16x3e")
     assert loss == pytest.approx(float(g["loss"]), rel=1e-4)
@@ -323,75 +220,7 @@ def test_f16x3e_parameter_gradients_meet_1e4_on_the_reference_samples(ci):
         assert abs(float(extra[k]) - r_) <= 1e-3 * abs(r_) + 1e-6 * gmax, (k, float(extra[k]), r_)
 
 
-# ------------------------------------------------------------------------------------------------ C5 in miniature: against a reference-trained model
-@pytest.mark.timeout(1200)
-def test_hip_training_run_matches_the_reference_trained_model_on_a_held_out_view():
-    """BASELINE config C5 ("full training loop ... edge-accuracy parity vs reference checkpoint"), in miniature and
-    without a dataset: golden g15 is a 1000-step training run of the REFERENCE's own classes (tests/golden/make_goldens.py:g15_convergence -
-    d8 w256 from the reference's seeded geometric initialisation, the runner's Adam groups and schedules, 256 rays per step from 7 views
-    of a multi-view consistent wire frame) and its render of the held-out eighth view.  The same run on the HIP path (native Trainer: fused
-    forward, hand-written backward, fused Adam), same batches, same schedules, then the same held-out render:
-      * the loss curve tracks the reference's: means over windows of 100 steps within 25 % everywhere (measured: up to 18 % apart in the middle of
-        the run - two trajectories through a chaotic phase; the sampler's discontinuity makes single steps differ) and within 5 % over the last
-        300 steps (measured 0.01 ... 0.4 %: both runs settle on the same curve),
-      * the held-out view's PSNR against the ground-truth edge map is within 0.5 dB of the reference-trained model's,
-      * the two models' held-out edge maps agree to RMS 0.04 of a [0, 1] image (measured 0.025: a quarter of either model's own RMS error against
-        the ground truth, 0.105 at 19.6 dB - two optimisation trajectories, not two evaluations of one model)."""
-    from conftest import load_golden
-    from test_gpu_parity import mk_renderer, t
-    g = load_golden("g15_convergence")
-    ns, ni, steps_up = [int(v) for v in g["cfg"]]
-    N, n_steps = int(g["n_rays"]), int(g["n_steps"])
-    n_views, HW, held_out = [int(v) for v in g["scene"]]
-    lr, lr_geo, alpha, warm_up_end, end_iter, anneal_end = [float(v) for v in g["schedule"]]
-    ew, igr, igr_ns = [float(v) for v in g["weights3"]]
-    meta, edges = synthetic.make_wireframe_scene(n_images=n_views, H=HW, W=HW)
-    kw = dict(d_in=3, d_out=1, d_hidden=256, n_layers=8, skip_in=(4,), multires=10, bias=0.5)
-    torch.manual_seed(int(g["init_seed"]))                       # the reference's constructor under the same seed (g9 pins the RNG consumption)
-    net = emap_amd.UDFNetwork(scale=1.0, geometric_init=True, weight_norm=True, udf_type="abs", precision="f16x3", **kw)
-    for k, v in net.state_dict().items():
-        assert float(v.double().abs().sum()) == pytest.approx(float(g["init." + k + ".abs_sum"]), rel=1e-12), k
-    net = net.to(DEV)
-    r = mk_renderer(net, ns, ni, steps_up)
-    tr = Trainer(r, lr_geo=lr_geo, lr=lr, edge_weight=ew, igr_weight=igr, igr_ns_weight=igr_ns)
-    near, far = float(meta["scene_box"]["near"]), float(meta["scene_box"]["far"])
-    losses = []
-    for it in range(n_steps):
-        tr.optimizer.param_groups[0]["lr"], tr.optimizer.param_groups[1]["lr"] = float(g["lrs"][it][0]), float(g["lrs"][it][1])
-        img, px, py = synthetic.convergence_batch(meta, edges, N, seed=int(g["batch_seed0"]) + it, held_out=held_out)
-        ro, rv, ds, true_edge = synthetic.scene_rays(meta, edges, img, px, py)
-        b = {"rays_o": ro.to(DEV), "rays_d": rv.to(DEV), "near": torch.full((N, 1), near, device=DEV), "far": torch.full((N, 1), far, device=DEV),
-             "depth_scale": ds.to(DEV), "cos_anneal_ratio": float(np.min([1.0, it / anneal_end])), "flip_saturation": 0.0, "perturb_overwrite": 0}
-        losses.append(tr.step(b, true_edge.to(DEV)))
-    tr.check_errors()
-    hl = torch.stack(losses)[:, 0].cpu().double().numpy()
-    rl = np.asarray(g["loss"], dtype=np.float64)
-    win = 100
-    hm, rm = hl.reshape(-1, win).mean(1), rl.reshape(-1, win).mean(1)
-    print("loss, means over windows of 100 steps  reference:", np.round(rm, 4), " HIP:", np.round(hm, 4))
-    assert np.all(np.abs(hm - rm) <= 0.25 * rm) and np.all(np.abs(hm - rm)[-3:] <= 0.05 * rm[-3:])
-    # the held-out view, rendered like the reference rendered it (perturb_overwrite = 0, cos_anneal_ratio = 1)
-    ys, xs = np.mgrid[0:HW, 0:HW]
-    ro, rv, ds, gt = synthetic.scene_rays(meta, edges, held_out, xs.reshape(-1), ys.reshape(-1))
-    n = ro.shape[0]
-    with torch.no_grad():
-        o = r.render(ro.to(DEV), rv.to(DEV), torch.full((n, 1), near, device=DEV), torch.full((n, 1), far, device=DEV), ds.to(DEV),
-                     cos_anneal_ratio=1.0, perturb_overwrite=0, flip_saturation=0.0)
-    img_h = o["edge"].reshape(HW, HW).cpu()
-    img_r = t(g["held_out_after"])
-    gt = gt.reshape(HW, HW)
-    psnr = lambda a: 10.0 * np.log10(1.0 / max(float(((a - gt) ** 2).mean()), 1e-12))
-    p_h, p_r = psnr(img_h), psnr(img_r)
-    rms = float(((img_h - img_r) ** 2).mean().sqrt())
-    print(f"held-out view: PSNR vs ground truth  HIP-trained {p_h:.2f} dB, reference-trained {p_r:.2f} dB (recorded {float(g['psnr'][1]):.2f}; before training "
-          f"{float(g['psnr'][0]):.2f}); RMS difference of the two models' edge maps {rms:.4f}")
-    assert p_r == pytest.approx(float(g["psnr"][1]), abs=1e-6)
-    assert abs(p_h - p_r) <= 0.5 and p_h >= float(g["psnr"][0]) + 10.0
-    assert rms <= 0.04
-    assert float(r.deviation_network.variance) == pytest.approx(float(g["variance"]), rel=5e-2)
-    assert float(r.beta_network.beta) == pytest.approx(float(g["beta"]), rel=5e-2)
-
-
+# ------------------------------------------------------------------------------------------------ the reverse sweep's fused output layer
 @pytest.mark.gpu
 @pytest.mark.parametrize("prec,tol", [("f16x3", 5e-5), ("f16x3e", 2e-5), ("bf16x3", 1e-4), ("f16", 5e-3)])
 @pytest.mark.parametrize("skip_in", [(4,), (7,)])

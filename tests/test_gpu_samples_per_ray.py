@@ -6,9 +6,9 @@ import pytest
 import torch
 
 from conftest import load_golden, t
-import emap_amd
 from emap_amd import _lib, synthetic
-from test_gpu_parity import mk, DEV, _render_core_on_z
+from gpu_helpers import mk, mk_renderer, DEV, _render_core_on_z
+from gpu_helpers import rel_floored as rel          # every rel() of this file has test_gpu_render_modes.py's floor of 1e-4
 from oracle import emap_oracle as O
 from test_gpu_backward import _cmp
 
@@ -20,24 +20,11 @@ FILES = [(m, c) for m in MODES for c in CASES if m == "default" or c != "c64_448
 PER_SAMPLE = ["udf", "weights", "gradients", "gradients_flip", "inside_sphere", "gradient_mag", "mid_z_vals", "dists"]
 
 
-def rel(a, b):
-    """max-normalised difference, with test_gpu_render_modes.py's floor of 1e-4 for quantities that are all near zero"""
-    a = a.detach().cpu().double().reshape(-1)
-    b = b.detach().cpu().double().reshape(-1)
-    return float((a - b).abs().max() / max(float(b.abs().max()), 1e-4))
-
-
 def golden_out(g, k):
     """out[k] of the reference's render() dict; the fixtures store gradients_flip as the sign it applies to gradients"""
     if k == "gradients_flip":
         return t(g["out.gradients"]) * t(g["out.gradients_flip_sign"]).float()
     return t(g["out." + k])
-
-
-def mk_renderer(net, ns, ni, steps, **mode):
-    dev = emap_amd.SingleVarianceNetwork(0.3).to(DEV)
-    bet = emap_amd.BetaNetwork(0.5, 0.3, 0.3, 5e-5, True, True, False).to(DEV)
-    return emap_amd.UDFRendererBlending(None, net, dev, bet, ns, ni, 0, steps, 1.0, device=DEV, **mode)
 
 
 def _setup(mname, case, prec="f16x3"):
@@ -48,7 +35,7 @@ def _setup(mname, case, prec="f16x3"):
 
 
 def _well_conditioned(weights, inds):
-    """test_gpu_parity._well_conditioned for any m (that one assumes m <= n): samples whose interval holds >= 1e-3 of the pdf mass"""
+    """gpu_helpers._well_conditioned for any m (that one assumes m <= n): samples whose interval holds >= 1e-3 of the pdf mass"""
     w = weights + 1e-5
     pdf = w / w.sum(-1, keepdim=True)
     below = (inds - 1).clamp(min=0)

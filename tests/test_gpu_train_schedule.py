@@ -12,8 +12,7 @@ import emap_amd
 from emap_amd import _lib, synthetic, TrainSchedule
 from emap_amd.parallel import Trainer
 from conftest import load_golden
-from test_gpu_parity import mk, DEV
-from test_gpu_render_modes import mk_renderer
+from gpu_helpers import mk, mk_renderer, DEV
 from test_train_schedule_cpu import schedule_sets
 
 pytestmark = pytest.mark.gpu

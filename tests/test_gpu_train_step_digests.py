@@ -16,8 +16,7 @@ import torch
 
 from emap_amd import synthetic
 from emap_amd.parallel import Trainer, FusedAdam
-from test_gpu_parity import mk, DEV
-from test_gpu_render_modes import mk_renderer
+from gpu_helpers import mk, mk_renderer, DEV
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +66,7 @@ def trainer_digest(name, ns, ni, steps, capture=False, freeze_beta=False, **mode
 
 
 def fused_adam_digest(flat_geo_grads):
-    """FusedAdam alone on the parameter groups of test_gpu_round5.py: three steps with fixed gradients; the third tail parameter is frozen
+    """FusedAdam alone on the parameter groups of test_gpu_adam.py: three steps with fixed gradients; the third tail parameter is frozen
     at first and gets its gradient from step 2 on.  flat_geo_grads: the geometry gradients are consecutive views of one buffer (the
     optimizer then reads them in place: one launch for the geometry range, one for the tail)."""
     rng = np.random.Generator(np.random.PCG64(501))

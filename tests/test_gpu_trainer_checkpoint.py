@@ -11,8 +11,7 @@ import torch
 import emap_amd
 from emap_amd import _lib, synthetic
 from emap_amd.parallel import Trainer, FusedAdam
-from test_gpu_parity import mk, DEV
-from test_gpu_render_modes import mk_renderer
+from gpu_helpers import mk, mk_renderer, DEV
 from test_gpu_train_schedule import COMPRESSED, same_bits, _state, _assert_same_state
 
 pytestmark = pytest.mark.gpu
