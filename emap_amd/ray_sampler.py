@@ -20,7 +20,8 @@ checkpoint (``Trainer.save_checkpoint(path, sampler)``).
 
 The host RNG streams (torch CPU generator, python ``random``) cannot be reproduced on a device: the draw is a
 Philox4x32-10 stream keyed by ``seed``; the deterministic part (rays of given pixels) and the sampling distribution are what
-the parity tests pin.
+the parity tests pin.  The draw itself - which pixel and jitter each (seed, step, ray) gives - is defined in include/emap_hip.h and held
+to that definition bit for bit (tests/ray_draw_ref.py, tests/test_gpu_ray_draw.py).
 """
 from __future__ import annotations
 

@@ -323,6 +323,18 @@ int emap_render_bwd_staged(const EmapNetConfig* cfg, const void* packed, int pre
  * mean edge value).
  * Random numbers: Philox4x32-10 with key `seed`, stream = step, index = ray.  step = *counter_dev when counter_dev != NULL
  * (the kernel chain then increments it: the sampler can live inside a captured graph), else `offset`.
+ * The draw of ray i at step s, from the four 32-bit words w0 .. w3 of Philox4x32-10 with counter = [i lo, i hi, s lo, s hi], key =
+ * [seed lo, seed hi], multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds (tests/ray_draw_ref.py is
+ * this paragraph in numpy, and the suite holds the kernel to it bit for bit):
+ *   rand_below(r, n) = (uint64(r) * n) >> 32                an integer in [0, n), never n
+ *   uniform ray    px = rand_below(w0, W), py = rand_below(w1, H)
+ *   weighted ray   ne = n_edge[img], nn = H*W - ne, d = density[img] widened to fp64, we = ne (1 - d), wn = nn d, all in fp64;
+ *                  u = ((w0 + 0.5) 2^-32) (we + wn): the ray is in the edge class if (u < we and ne > 0) or nn == 0;
+ *                  w1 picks the class member: pix = pixel_order[img][rand_below(w1, ne)] in the edge class, else
+ *                  pixel_order[img][ne + rand_below(w1, nn)];  px = pix % W, py = pix / W
+ *   t_rand         float(w2 >> 8) * 2^-24 - 0.5             fp32, exact: a 2^-24 grid on [-0.5, 0.5).  w3 is not used.
+ * importance == 0: every ray is uniform.  importance != 0: rays i < batch / 2 (integer division) are uniform and the others weighted.
+ * An odd batch yields `batch` rays with batch / 2 uniform ones; the reference returns 2 * (batch // 2) rays there (:245-266).
  * img_idx < 0 selects image_perm[step % n_images] (or step % n_images when image_perm is NULL) on the device.
  * pixels_in ((N,2) int64 x,y; may be NULL) bypasses the draw: the deterministic part, used by the parity tests.
  * Any output pointer may be NULL. */

@@ -12,6 +12,7 @@ import emap_amd
 from emap_amd import _lib, synthetic
 from emap_amd.parallel import Trainer, FusedAdam
 from gpu_helpers import mk, mk_renderer, DEV
+from ray_draw_ref import philox4x32_10
 from test_gpu_train_schedule import COMPRESSED, same_bits, _state, _assert_same_state
 
 pytestmark = pytest.mark.gpu
@@ -24,14 +25,8 @@ RAYS = 64
 # ---------------------------------------------------------------------------------------------- the definition, in numpy
 def philox_keys(seed, stream, n):
     """(w0 << 32) | w1 of Philox4x32-10(key = seed, counter = [index lo, index hi, stream lo, stream hi]) for index 0 .. n - 1"""
-    u, lo = np.uint64, np.uint64(0xFFFFFFFF)
-    c = [np.arange(n, dtype=u), np.zeros(n, u), np.full(n, stream & 0xFFFFFFFF, u), np.full(n, stream >> 32, u)]
-    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
-    for _ in range(10):
-        p0, p1 = u(0xD2511F53) * c[0], u(0xCD9E8D57) * c[2]
-        c = [(p1 >> u(32)) ^ c[1] ^ u(k0), p1 & lo, (p0 >> u(32)) ^ c[3] ^ u(k1), p0 & lo]
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return (c[0] << u(32)) | c[1]
+    w = philox4x32_10(seed, stream, np.arange(n, dtype=np.uint64))       # the one Philox of the tests (ray_draw_ref.py)
+    return (w[0].astype(np.uint64) << np.uint64(32)) | w[1].astype(np.uint64)
 
 
 def epoch_order(seed, e, images):
