@@ -217,7 +217,7 @@ static Workspace plan_workspace(const RenderShape& r, const NetLayout* L = nullp
 static bool composite_fused(const NetLayout& L, int prec, const EmapRenderParams& p, const RenderShape& r) {
     const int64_t P = (int64_t)r.N * r.S;
     return p.render_mode == EMAP_RENDER_UNBIASED && r.S <= COMP_FUSED_MAX_S && g_fused_composite.load(std::memory_order_relaxed) &&
-           mlp_uses_rev(L, prec, P) && comp_list_entries(P, r.S) <= COMP_LIST_MAX;
+           mlp_uses_rev(L, prec, P) && comp_list_entries(P, r.S) <= comp_list_cap(L.H, L.nparts);
 }
 
 }  // namespace emap

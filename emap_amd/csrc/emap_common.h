@@ -31,14 +31,30 @@ inline bool attr_needed(uint64_t& mask) {
     mask |= 1ull << d;
     return true;
 }
+// dynamic LDS a workgroup may ask for (gfx950: 160 KiB per CU).  Every kernel's LDS layout struct asserts its BYTES against it.
+constexpr int LDS_LIMIT = 160 * 1024;
 // raises the dynamic-LDS limit of kernel `fn` the first time it is about to be launched on the current device (mask: one per kernel)
-inline int raise_lds_limit(uint64_t& mask, const void* fn, int bytes = 160 * 1024) {
+inline int raise_lds_limit(uint64_t& mask, const void* fn, int bytes = LDS_LIMIT) {
     if (attr_needed(mask) && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
         set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
         return EMAP_E_LAUNCH;
     }
     return EMAP_OK;
 }
+// One launch of a kernel with dynamic LDS.  raise_lds() goes first in a launcher - before its argument checks and its empty-launch return: the
+// first call may be the warm-up before a graph capture.  One instantiation per kernel pointer: it owns that kernel's per-device attribute mask.
+template <auto KERN>
+struct LdsKernel {
+    static int raise_lds() {
+        static uint64_t attr_mask = 0;   // per device: the LDS-size attribute is a property of (function, device)
+        return raise_lds_limit(attr_mask, reinterpret_cast<const void*>(KERN));
+    }
+    template <class... Args>
+    static int launch(const char* what, int grid, int block, int lds, hipStream_t st, const Args&... args) {
+        hipLaunchKernelGGL(KERN, dim3(grid), dim3(block), lds, st, args...);
+        return check_launch(what);
+    }
+};
 
 // ---- packed-weight layout -------------------------------------------------------------------
 // The MLP kernels keep activations in registers in MFMA-fragment order and never transpose them:
@@ -183,9 +199,19 @@ constexpr int REV_MAX_WG = 768;      // persistent workgroups of the reverse-mod
 // grid cap of the reverse-mode kernel's 4-wave form (two resident workgroups per CU), the only form that runs the fused tail
 // (launch_mlp_rev32_t's wg_cap, which asserts the equality)
 constexpr int REV_WG_CAP_4W = REV_MAX_WG * 2 / 3;
-// upper bound on the rays ONE workgroup of the value + grad_x kernel can come to own (its list lives in the kernel's exchange buffer): every tile
-// it runs (64 points, <= REV_WG_CAP_4W workgroups) can complete at most 64 / S + 2 rays
+// dynamic LDS of udf_mlp_rev32_kernel<H, ., ., NC, ...> in a mode of nparts parts: H / 32 + PE_KS K32-steps of 2 x NC x nparts fragments
+// (udf_mlp_rev32.inc:Rev32Lds, which takes BYTES from here; api.hip needs it for comp_list_cap)
+constexpr int rev32_lds_bytes(int H, int nparts, int NC) { return (H / 32 + PE_KS) * 2 * NC * nparts * FRAG_BYTES; }
+// The rays ONE workgroup of the value + grad_x kernel comes to own are listed in that kernel's LDS, int nd[1 + n] from its start (the fused tail,
+// 4-wave form: NC = 2): every tile it runs (64 points, <= REV_WG_CAP_4W workgroups) can complete at most 64 / S + 2 rays - comp_list_entries.  A
+// launch runs the fused tail only if that bound is within comp_list_cap: what the allocation holds, and at most COMP_LIST_MAX (the ceiling every
+// configuration but d_hidden = 128 in the single-pass modes - 24 KiB, 6143 rays - decides by); other launches composite and reduce separately.
 constexpr int COMP_LIST_MAX = 8192;
+constexpr int comp_list_cap(int H, int nparts) {
+    const int fit = rev32_lds_bytes(H, nparts, 2) / 4 - 1;
+    return fit < COMP_LIST_MAX ? fit : COMP_LIST_MAX;
+}
+static_assert(comp_list_cap(128, 1) == 6143 && comp_list_cap(128, 2) == COMP_LIST_MAX && comp_list_cap(256, 1) == COMP_LIST_MAX, "comp_list_cap");
 // samples per ray of the fused tail: it composites with lane chunks of C <= 4 (udf_mlp_rev32.inc); longer rays take the separate
 // compositing and reduction launches (sampler.hip, C = 8 / 16)
 constexpr int COMP_FUSED_MAX_S = 256;

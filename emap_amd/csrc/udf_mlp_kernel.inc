@@ -94,6 +94,20 @@ struct IsRay {
     UpsampleScratch<IS_MAXS> w;
 };
 
+// Dynamic LDS of udf_mlp_fs2_kernel, for the kernel and its two launchers.  An exchange buffer is [H / 32][NCT][NPART] 1 KiB fragments: the current
+// layer's input.  One workgroup per CU (8 waves, narrow tiles): TWO buffers - a layer reads one and writes the other, a wave stores its outputs as
+// soon as it has them and one barrier per layer remains (as in udf_mlp_vjp.inc); otherwise (two / three workgroups per CU share the LDS: <= 80 KiB)
+// one buffer overwritten by the layer's output between two barriers.  Then the PE block [PE_KS][NCT][NPART], then (IS) one IsRay per column tile.
+template <int H, int NPART, int NCT, int NW, bool IS>
+struct Fs2Lds {
+    static constexpr int XB = (H / 32) * NCT * NPART * FRAG_BYTES;
+    static constexpr int N_XB = (NW == 8) ? 2 : 1;
+    static constexpr int PE_OFF = N_XB * XB;
+    static constexpr int IS_OFF = PE_OFF + PE_KS * NCT * NPART * FRAG_BYTES;
+    static constexpr int BYTES = IS_OFF + (IS ? (NCT * (int)sizeof(IsRay) + 15) & ~15 : 0);
+    static_assert(BYTES <= LDS_LIMIT, "udf_mlp_fs2_kernel: LDS");
+};
+
 // shader clock of a launch: s_memtime counts shader cycles, s_memrealtime a constant 100 MHz (scripts/probes/clock_probe.hip)
 __device__ __forceinline__ void clock_stamp(long long* clk, int slot) {
     if (clk && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -344,14 +358,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
     static_assert(PPW >= 1 && PPW * NW == NPAIR, "H/32 must be a multiple of the waves per workgroup");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int XB = NKS * NCT * NPART * FRAG_BYTES;
-    // [NKS][NCT][NPART] 1 KiB fragments: the current layer's input.  One workgroup per CU (8 waves, narrow tiles): TWO buffers - a layer reads
-    // one and writes the other, a wave stores its outputs as soon as it has them and one barrier per layer remains (as in udf_mlp_vjp.inc);
-    // otherwise (two / three workgroups per CU share the LDS) one buffer overwritten by the layer's output between two barriers.
-    constexpr bool PP = (NW == 8);
+    using Lds = Fs2Lds<H, NPART, NCT, NW, IS>;
+    constexpr bool PP = (Lds::N_XB == 2);         // two exchange buffers
     char* const xb0 = smem;
-    char* const xb1 = smem + (PP ? XB : 0);
-    char* pebuf = smem + (PP ? 2 : 1) * XB;       // [PE_KS][NCT][NPART]
+    char* const xb1 = smem + (PP ? Lds::XB : 0);
+    char* pebuf = smem + Lds::PE_OFF;             // [PE_KS][NCT][NPART]
     int cur = 0;
 
     const int tid = threadIdx.x;
@@ -384,7 +395,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 1 : (Prec<MODE>::NPART == 1 ? 3
         for (int i = blockIdx.x * (NW * 64) + tid; i < a.src.zero_n; i += gridDim.x * (NW * 64)) a.src.zero_cnt[i] = 0;
 
     // ---- IS: the sampler step of ray blockIdx.x * NCT + wave (waves 0 .. NCT-1), on the ray's LDS state ----
-    IsRay* const is_rays = reinterpret_cast<IsRay*>(smem + (size_t)((PP ? 2 : 1) * NKS + PE_KS) * NCT * NPART * FRAG_BYTES);
+    IsRay* const is_rays = reinterpret_cast<IsRay*>(smem + Lds::IS_OFF);
     float is_sd = 0.f;
     int is_step = 0;
     auto is_sampler = [&](int step) __attribute__((always_inline)) {
@@ -730,15 +741,11 @@ static int launch_mlp_fs2_t(const NetLayout& L, const void* packed, const PointS
     MlpArgs a = fill_mlp_args(L, packed, L.frag_off_bytes, L.t_frag_off_bytes, src, P, err);
     a.udf = udf; a.grad = grad3;
     a.n_tiles = (int)((P + PT - 1) / PT);
-    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES;   // <= 80 KiB: two workgroups per CU (8 waves: one, two exchange buffers)
-    static uint64_t attr_mask = 0;   // per device: the LDS-size attribute is a property of (function, device)
-    auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, GRAD, NW>;
-    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
-    if (rc) return rc;
+    using K = LdsKernel<udf_mlp_fs2_kernel<H, MODE, NCT, GRAD, NW>>;
+    if (const int rc = K::raise_lds()) return rc;
     if (a.n_tiles <= 0) return EMAP_OK;
     const int grid = a.n_tiles < 4096 ? a.n_tiles : 4096;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return check_launch("udf_mlp_fs2");
+    return K::launch("udf_mlp_fs2", grid, NW * 64, Fs2Lds<H, NPART, NCT, NW, false>::BYTES, st, a);
 }
 
 // 32-point tiles: from this many tiles on, two 4-wave workgroups per CU (up to 512 resident) instead of one 8-wave workgroup per CU.  257: as
@@ -820,13 +827,9 @@ static int launch_is_t(const NetLayout& L, const void* packed, const IsLaunch& q
     const int grid = (q.N + NCT - 1) / NCT;
     a.n_tiles = grid;
     a.is_udf_coarse = q.udf_coarse; a.is_z_final = q.z_final; a.is_n_rays = q.N; a.is_sc = q.Sc; a.is_m = q.m; a.is_steps = q.steps;
-    const size_t lds = (size_t)((NW == 8 ? 2 : 1) * (H / 32) + PE_KS) * NCT * NPART * FRAG_BYTES + (((size_t)NCT * sizeof(IsRay) + 15) & ~(size_t)15);
-    static uint64_t attr_mask = 0;
-    auto kern = udf_mlp_fs2_kernel<H, MODE, NCT, false, NW, true>;
-    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
-    return check_launch("importance_sample");
+    using K = LdsKernel<udf_mlp_fs2_kernel<H, MODE, NCT, false, NW, true>>;
+    if (const int rc = K::raise_lds()) return rc;
+    return K::launch("importance_sample", grid, NW * 64, Fs2Lds<H, NPART, NCT, NW, true>::BYTES, st, a);
 }
 
 template <int MODE>

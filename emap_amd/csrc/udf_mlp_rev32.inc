@@ -86,7 +86,18 @@ __device__ __forceinline__ void asm_wait_vm1(V8& r0) {
 // wave and a device-scope atomic ~2 us; done tile by tile they stall the other three waves at the next barrier (measured: composited in
 // place +1 % at 512 rays, +2 % at 4096; counters per tile, compositing deferred: +0.6 % / +1.7 %).  Same arithmetic per ray whoever runs
 // it: bit-identical to the two-launch form.
+// The ray list, int nd[1 + n] from the start of the LDS, is bounded by the whole allocation (emap_common.h:comp_list_cap, which composite_fused and
+// the launcher decide by), not by xbuf: it may run on into pebuf, which is free as well once the last tile's closing barrier has passed.  The
+// reduction's double red[4][5] sits at byte 64, over the list's head: every wave has read the list by then.
 struct NoFuse {};
+// Dynamic LDS of udf_mlp_rev32_kernel, for the kernel and its launcher: xbuf, [H / 32] K32-steps of [u][c][part] fragments, then pebuf, [PE_KS] more
+template <int H, int NPART, int NC>
+struct Rev32Lds {
+    static constexpr int KSB = 2 * NC * NPART * FRAG_BYTES;   // bytes of one K32-step
+    static constexpr int PE_OFF = (H / 32) * KSB;
+    static constexpr int BYTES = rev32_lds_bytes(H, NPART, NC);
+    static_assert(BYTES == PE_OFF + PE_KS * KSB && BYTES <= LDS_LIMIT, "udf_mlp_rev32_kernel: LDS");
+};
 template <int H, int MODE, int NW = 4, int NC = 2, bool FWD6 = false, bool BWD6 = true, bool COMP = false>
 __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs a, const std::conditional_t<COMP, CompositeFuse, NoFuse> cf) {
     using T = typename Prec<MODE>::T;
@@ -107,7 +118,8 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
     constexpr int NFR = 2 * NPART;                // fragments per K32-step of one row tile: [u][part]
     constexpr int PD = (NC == 4) ? 1 : 2;         // K32-steps of weight fragments in flight (a 128-point K32-step is twice as long)
     constexpr int SG_LEAD = 2;                    // K32-steps between issuing a row tile's sigma' loads and the end of its K-loop
-    constexpr int KSB = 2 * NC * NPART * FRAG_BYTES;   // bytes of one K32-step in the exchange buffer
+    using Lds = Rev32Lds<H, NPART, NC>;
+    constexpr int KSB = Lds::KSB;                 // bytes of one K32-step in the exchange buffer
     static_assert(PPW >= 1 && KQ >= 1 && PE_KS == 2 && NW == NC * PE_KS && NC % 2 == 0, "tile geometry");
     // MX6 (split-fp16, d_hidden = 256): the cross terms W_hi x_lo + W_lo x_hi of the BACKWARD GEMMs are two MX-scaled fp6 (e2m3)
     // MFMAs of K = 64 per K64-step and column tile instead of 8 f16 MFMAs of K = 16 - a quarter of their matrix-pipe time and the
@@ -124,7 +136,7 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* xbuf = smem;                            // [NKS][u][c][part]: activations (forward) / delta_z (backward), rewritten in place
-    char* pebuf = smem + NKS * KSB;               // [PE_KS][u][c][part]: the PE block, kept for the whole tile
+    char* pebuf = smem + Lds::PE_OFF;             // [PE_KS][u][c][part]: the PE block, kept for the whole tile
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1029,8 +1041,9 @@ __global__ __launch_bounds__(NW * 64, 2) void udf_mlp_rev32_kernel(const MlpArgs
         __syncthreads();   // the tile is done with xbuf / pebuf before the next tile's PE overwrites them
     }
     if constexpr (COMP) {
-        // ---- fused render_core tail (the last tile's closing barrier has passed: xbuf is free) ----
-        int* nd = reinterpret_cast<int*>(xbuf);      // [0] = number of rays this workgroup owns, [1 ...] = the rays (<= COMP_LIST_MAX: launcher)
+        // ---- fused render_core tail (the last tile's closing barrier has passed: xbuf and pebuf are free) ----
+        int* nd = reinterpret_cast<int*>(xbuf);      // [0] = number of rays this workgroup owns, [1 ...] = the rays (<= comp_list_cap: may run on into pebuf, see COMP above)
+        static_assert(64 + sizeof(double[4][5]) <= Lds::BYTES, "composite_reduce_body's partial sums");
         const int S = cf.c.S;
         if (wave == 0) {
             // arrival counters, ALL tiles of this workgroup at once (lane = tile; one wait for the output stores instead of one per tile, the
@@ -1101,13 +1114,11 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
     MlpArgs a = fill_mlp_args(L, packed, L.r32_frag_off_bytes, L.r32_t_frag_off_bytes, src, P, err);
     a.udf = udf; a.grad = grad3;
     a.n_tiles = (int)((P + PT - 1) / PT);
-    const size_t lds = (size_t)((H / 32) + PE_KS) * 2 * NC * NPART * FRAG_BYTES;
-    static uint64_t attr_mask = 0, attr_mask_c = 0;   // per device: the LDS-size attribute is a property of (function, device)
-    auto kern = udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, false>;
-    auto kern_c = udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, true>;
-    const int rc = raise_lds_limit(fuse ? attr_mask_c : attr_mask, fuse ? reinterpret_cast<const void*>(kern_c) : reinterpret_cast<const void*>(kern));
-    if (rc) return rc;
-    if (fuse && (!fuse->ray_cnt || comp_list_entries(P, fuse->c.S) > COMP_LIST_MAX || fuse->c.S < 1 || (int64_t)fuse->c.N * fuse->c.S != P || fuse->c.udf != udf || fuse->c.grad != grad3)) {
+    constexpr int lds = Rev32Lds<H, NPART, NC>::BYTES;
+    using K = LdsKernel<udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, false>>;
+    using KC = LdsKernel<udf_mlp_rev32_kernel<H, MODE, NW, NC, FWD6, BWD6, true>>;
+    if (const int rc = fuse ? KC::raise_lds() : K::raise_lds()) return rc;
+    if (fuse && (!fuse->ray_cnt || comp_list_entries(P, fuse->c.S) > comp_list_cap(L.H, L.nparts) || fuse->c.S < 1 || (int64_t)fuse->c.N * fuse->c.S != P || fuse->c.udf != udf || fuse->c.grad != grad3)) {
         set_error("udf_mlp_rev32: the fused compositing tail needs P = N * S points written to the buffers it composites from");
         return EMAP_E_INVALID;
     }
@@ -1123,9 +1134,7 @@ static int launch_mlp_rev32_t(const NetLayout& L, const void* packed, const Poin
     if (!scratch) { set_error("udf_mlp_rev32: no scratch buffer (pass the buffer sized by emap_udf_scratch_bytes)"); return EMAP_E_WORKSPACE; }
     a.scratch = static_cast<char*>(scratch);
     a.clk = prof_clk_here();
-    if (fuse) hipLaunchKernelGGL(kern_c, dim3(grid), dim3(NW * 64), lds, st, a, *fuse);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a, NoFuse{});
-    return check_launch("udf_mlp_rev32");
+    return fuse ? KC::launch("udf_mlp_rev32", grid, NW * 64, lds, st, a, *fuse) : K::launch("udf_mlp_rev32", grid, NW * 64, lds, st, a, NoFuse{});
 }
 
 template <int MODE>

@@ -70,6 +70,26 @@ struct VjpArgs {
     int32_t swm_unit[EMAP_MAX_LIN], swm_t_unit[EMAP_MAX_LIN];
 };
 
+// Dynamic LDS of udf_mlp_vjp_kernel, for the kernel and its launcher.  Exchange buffer [H / 32][NCT][NPART]: activations (forward) / adjoints
+// (backward).  PP (one workgroup per CU: 8 waves): TWO buffers, a step reads xb[cur] and writes xb[cur ^ 1] - a wave publishes its outputs as soon
+// as it has them and ONE barrier per step remains (round 3: the "everyone has finished reading" barrier cost 1.2 k cycles of waiting plus 0.9 k of
+// exchange writes every wave did at the same time, of a 12.8 k step).  !PP (two workgroups per CU, 80 KiB each): one buffer rewritten in place
+// between two barriers.  Then the PE block [PE_KS][NCT][NPART].  red, [NW][NCT][16] partial sums of the last layer: its own 2 KiB behind the PE
+// block (PP), else the head of the exchange buffer between two extra barriers.
+template <int H, int NPART, int NW>
+struct VjpLds {
+    static constexpr int NCT = 4;
+    static constexpr bool PP = (NW == 8);
+    static constexpr int N_XB = PP ? 2 : 1;
+    static constexpr int XB = (H / 32) * NCT * NPART * FRAG_BYTES;
+    static constexpr int PB = PE_KS * NCT * NPART * FRAG_BYTES;
+    static constexpr int PE_OFF = N_XB * XB;
+    static constexpr int RED_BYTES = NW * NCT * 16 * (int)sizeof(float);
+    static constexpr int RED_OFF = PP ? PE_OFF + PB : 0;
+    static constexpr int BYTES = PE_OFF + PB + (PP ? RED_BYTES : 0);   // 146 KiB at H = 256 in the split modes
+    static_assert(RED_BYTES <= XB && BYTES <= LDS_LIMIT, "udf_mlp_vjp_kernel: LDS");
+};
+
 // SMX (round 5; split-fp16, d_hidden = 256, 8 waves): the cross terms W_hi x_lo + W_lo x_hi of every hidden-K GEMM (forward layers 1.., the
 // last layer, reverse steps) run as v_mfma_scale_f32_16x16x128_f8f6f4 on e2m3 operands - the time of ONE 16x16x32 f16 MFMA for K = 128
 // (profiles/r04_probe_mx16.txt), i.e. 16 MX MFMAs instead of 64 f16 ones per K128-step and tile pair; the hi x hi pass stays f16.
@@ -107,18 +127,13 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int XB = NKS * NCT * NPART * FRAG_BYTES;
-    constexpr int PB = PE_KS * NCT * NPART * FRAG_BYTES;
-    // Exchange buffer [NKS][NCT][NPART]: activations (forward) / adjoints (backward).  PP (one workgroup per CU: 8 waves): TWO buffers, a
-    // step reads xb[cur] and writes xb[cur ^ 1] - a wave publishes its outputs as soon as it has them and ONE barrier per step remains
-    // (round 3: the "everyone has finished reading" barrier cost 1.2 k cycles of waiting plus 0.9 k of exchange writes every wave did at
-    // the same time, of a 12.8 k step).  !PP (two workgroups per CU, 80 KiB each): one buffer rewritten in place between two barriers.
-    constexpr bool PP = (NW == 8);
+    using Lds = VjpLds<H, NPART, NW>;
+    static_assert(NCT == Lds::NCT, "VjpLds sizes the buffers for this kernel's column tiles");
+    constexpr bool PP = Lds::PP;
     char* const xb0 = smem;
-    char* const xb1 = smem + (PP ? XB : 0);
-    char* pebuf = smem + (PP ? 2 : 1) * XB;       // [PE_KS][NCT][NPART]: PE (column tiles 0,1) and its tangent (2,3)
-    // [NW][NCT][16] partial sums of the last layer: own 2 KiB behind the PE block (PP), else the head of the exchange buffer between two extra barriers
-    float* red = reinterpret_cast<float*>(PP ? smem + 2 * XB + PB : smem);
+    char* const xb1 = smem + (PP ? Lds::XB : 0);
+    char* pebuf = smem + Lds::PE_OFF;             // [PE_KS][NCT][NPART]: PE (column tiles 0,1) and its tangent (2,3)
+    float* red = reinterpret_cast<float*>(smem + Lds::RED_OFF);   // [NW][NCT][16] partial sums of the last layer
     int cur = 0;
 
     const int tid = threadIdx.x;
@@ -215,7 +230,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void udf_mlp_vjp_kernel(c
     if ((int)blockIdx.x < a.n_tiles) head_after_fwd(-1);
     // K-steps of an exchange buffer that no wave writes (the tile pairs a short layer does not have) are read against zero weights:
     // they must hold finite numbers, not whatever the LDS held before the launch
-    for (int i = tid * 16; i < (PP ? 2 : 1) * XB; i += NW * 64 * 16) *reinterpret_cast<f32x4*>(smem + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = tid * 16; i < Lds::N_XB * Lds::XB; i += NW * 64 * 16) *reinterpret_cast<f32x4*>(smem + i) = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
     for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
         const long long pbase = ((long long)va.tile0 + tile) * VJP_PT;
@@ -837,15 +852,10 @@ static int launch_vjp_sweep_t(const NetLayout& L, const void* packed, const VjpS
     va.d_udf = s.d_udf; va.d_grad = s.d_grad; va.stash_a = s.stash_a; va.stash_z = s.stash_z; va.stash_s = s.stash_s; va.absmax = s.absmax; va.ldot = s.ldot; va.V = *s.V;
     va.swm = static_cast<const char*>(packed) + L.swm_off_bytes;
     for (int l = 0; l < L.n_lin; ++l) { va.swm_unit[l] = L.swm_unit[l]; va.swm_t_unit[l] = L.swm_t_unit[l]; }
-    const size_t lds = (NW == 8) ? (size_t)(2 * (H / 32) + PE_KS) * 4 * NPART * FRAG_BYTES + (size_t)NW * 4 * 16 * 4   // two exchange buffers + PE + red: 146 KiB at H = 256 in the split modes
-                                 : (size_t)((H / 32) + PE_KS) * 4 * NPART * FRAG_BYTES;              // 80 KiB: two workgroups per CU
-    auto kern = udf_mlp_vjp_kernel<H, MODE, NW, SMX_>;
-    static uint64_t attr_mask = 0;
-    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(kern));
-    if (rc) return rc;
+    using K = LdsKernel<udf_mlp_vjp_kernel<H, MODE, NW, SMX_>>;
+    if (const int rc = K::raise_lds()) return rc;
     if (s.n_tiles <= 0) return EMAP_OK;
-    hipLaunchKernelGGL(kern, dim3(s.grid < s.n_tiles ? s.grid : s.n_tiles), dim3(NW * 64), lds, st, va);
-    return check_launch("udf_mlp_vjp");
+    return K::launch("udf_mlp_vjp", s.grid < s.n_tiles ? s.grid : s.n_tiles, NW * 64, VjpLds<H, NPART, NW>::BYTES, st, va);
 }
 
 template <int MODE>

@@ -112,7 +112,15 @@ __device__ __forceinline__ void wgrad_store(const WgradArgs& a, const WgradJob& 
 #ifndef EMAP_WGRAD_DEPTH
 #define EMAP_WGRAD_DEPTH 3
 #endif
-constexpr int WGRAD_DEPTH = EMAP_WGRAD_DEPTH;   // steps (32 KiB each) in flight per workgroup; the ring has WGRAD_DEPTH + 1 stages (<= 160 KiB of LDS)
+constexpr int WGRAD_DEPTH = EMAP_WGRAD_DEPTH;   // steps in flight per workgroup; the ring has WGRAD_DEPTH + 1 stages
+// Dynamic LDS of wgrad_kernel, for the K loop of a job with CT column tiles and (CT = 16, the widest job) the launcher
+template <int CT>
+struct WgradLds {
+    static constexpr int NST = WGRAD_DEPTH + 1;
+    static constexpr int STAGE = (CT + 16) * 1024;       // A[CT] then Z[16 row tiles]
+    static constexpr int BYTES = NST * STAGE;
+    static_assert(CT <= 16 && BYTES <= LDS_LIMIT, "wgrad_kernel: LDS");
+};
 __device__ __forceinline__ void wg_dma16(unsigned lds_dst, const char* gsrc) {
     unsigned keep;   // M0 = LDS byte address of lane 0's 16 bytes; written in the statement that uses it (the compiler owns M0)
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -124,8 +132,7 @@ __device__ __forceinline__ void wgrad_lds_run(const WgradArgs& a, const WgradJob
     constexpr int CT = 4 * NB;
     constexpr int NA = (CT + 7) / 8;              // A fragments a wave fetches per step
     constexpr int NLD = NA + 2;                   // DMA loads per wave and step
-    constexpr int D = WGRAD_DEPTH, NST = D + 1;
-    constexpr int STAGE = (CT + 16) * 1024;       // A[CT] then Z[16 row tiles]
+    constexpr int D = WGRAD_DEPTH, NST = WgradLds<CT>::NST, STAGE = WgradLds<CT>::STAGE;
     const int t0 = (int)(((long long)a.n_tiles * slice) / J.n_slices), t1 = (int)(((long long)a.n_tiles * (slice + 1)) / J.n_slices);
     const int nsteps = 2 * (t1 - t0);
     f32x4 acc[2][CT];
@@ -475,12 +482,9 @@ int launch_absmax(const float* du, const float* dg, int64_t P, uint32_t* out, hi
 
 template <class V8>
 static int launch_wgrad_t(const WgradArgs& a, int grid, hipStream_t st) {
-    constexpr size_t lds = (size_t)(WGRAD_DEPTH + 1) * 32 * 1024;   // NST stages of (16 A + 16 Z) KiB
-    static uint64_t attr_mask = 0;
-    const int rc = raise_lds_limit(attr_mask, reinterpret_cast<const void*>(wgrad_kernel<V8>), (int)lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(wgrad_kernel<V8>, dim3(grid), dim3(512), lds, st, a);
-    return check_launch("wgrad");
+    using K = LdsKernel<wgrad_kernel<V8>>;
+    if (const int rc = K::raise_lds()) return rc;
+    return K::launch("wgrad", grid, 512, WgradLds<16>::BYTES, st, a);
 }
 
 int launch_wgrad(const NetLayout& L, const VjpLayout& V, const WgradPlan& plan, const char* stash_a, const char* stash_z, float* partial,

@@ -115,6 +115,24 @@ def test_fused_compositing_equals_the_separate_launch_bit_for_bit(netname, N, ns
     assert torch.equal(red[1]["edge"], outs[1]["edge"])
 
 
+@pytest.mark.parametrize("prec", ["f16", "bf16"])
+def test_fused_compositing_at_d_hidden_128_in_the_single_pass_modes(prec):
+    """udf_mlp_rev32_kernel<128, f16 | bf16, ..., COMP>: the smallest LDS allocation of the kernel (udf_mlp_rev32.inc:Rev32Lds, 24 KiB), where the
+    fused tail's ray list (emap_common.h:comp_list_cap) has the least room.  62 samples per ray: tiles straddle rays."""
+    N, ns, ni, K = 280, 32, 30, 3
+    net, _, _ = mk("d4w128L10", prec)
+    r = mk_renderer(net, ns, ni, K)
+    ro, rd, near, far, ds = [v.to(DEV) for v in synthetic.make_rays(N, seed=9)]
+    tr = synthetic.make_t_rand(N).to(DEV)
+    assert N * (ns + ni) >= 16384                                  # udf_mlp.hip:mlp_variant, the single-pass modes: the reverse-sweep kernel runs
+    kw = dict(cos_anneal_ratio=0.7, flip_saturation=0.9, t_rand=tr)
+    for reduced in (False, True):
+        outs = _render_both_ways(r, (ro, rd, near, far, ds), kw, reduced=reduced)
+        assert set(outs[0]) == set(outs[1]) and "edge" in outs[1]
+        for k in outs[1]:
+            assert torch.equal(outs[1][k], outs[0][k]), (prec, reduced, k)
+
+
 @pytest.mark.parametrize("prec", ["f16x3e", "f16x3m", "bf16x3", "f16", "bf16"])
 def test_fused_compositing_in_every_precision_mode(prec):
     net, _, _ = mk("d8w256L10", prec)
