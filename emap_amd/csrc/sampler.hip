@@ -637,7 +637,7 @@ int launch_composite_bwd(const float* rays_o, const float* rays_d, const float* 
 }
 
 int launch_embed(const float* x, int64_t P, int L, float* pe, hipStream_t st) {
-    if (L < 1 || L > 16) { set_error("embed: multires=%d out of range", L); return EMAP_E_INVALID; }
+    if (L < 0 || L > 16) { set_error("embed: multires=%d out of range", L); return EMAP_E_INVALID; }   // 0: the raw coordinates (EmapNetConfig.multires = 0)
     if (P <= 0) return EMAP_OK;
     hipLaunchKernelGGL(embed_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, x, (long long)P, L, pe);
     return check_launch("embed");

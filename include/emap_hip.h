@@ -102,7 +102,8 @@ int emap_pack_weights(const EmapNetConfig* cfg, const float* const* g_host, cons
 /* ---- fields --------------------------------------------------------------------------------
  * emap_udf_fwd      : UDFNetwork.forward / .udf value  (udf_model.py:90-116)   x (P,3) -> udf (P)
  * emap_udf_fwd_grad : + UDFNetwork.gradient            (udf_model.py:121-135)  -> grad (P,3)
- * emap_embed        : Embedder.embed                   (embedder.py:34-35)     x (P,3) -> (P,3+6L) */
+ * emap_embed        : Embedder.embed                   (embedder.py:34-35)     x (P,3) -> (P,3+6L), L = multires in 0..16
+ *                     (0: the three coordinates, as EmapNetConfig.multires = 0) */
 int emap_udf_fwd(const EmapNetConfig* cfg, const void* packed, int prec, const float* x, int64_t P,
                  float* udf, void* stream);
 /* scratch: device buffer of emap_udf_scratch_bytes() bytes (0 for small launches; the reverse-mode kernel keeps its
