@@ -16,10 +16,13 @@ from .edge_metrics import (nearest_neighbors, chamfer_distance, compute_chamfer_
 from . import parametric_edges  # noqa: F401
 from .parametric_edges import (sample_edges, bezier_curve_length, get_pred_points_and_directions, process_geometry_data,  # noqa: F401
                                compute_visibility, finish_parametric_edges, evaluate_parametric_edges)
+from . import dtu_eval  # noqa: F401
+from .dtu_eval import point_visibility_counts, compute_point_visibility, gt_edge_points, evaluate_dtu, DTU_SCANS  # noqa: F401
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
            "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
            "edge_metrics", "nearest_neighbors", "chamfer_distance", "compute_chamfer_distance", "compute_precision_recall_IOU",
            "downsample_point_cloud_average", "sample_segments", "evaluate_edges", "metrics_from_stats", "f_score",
            "parametric_edges", "sample_edges", "bezier_curve_length", "get_pred_points_and_directions", "process_geometry_data",
-           "compute_visibility", "finish_parametric_edges", "evaluate_parametric_edges"]
+           "compute_visibility", "finish_parametric_edges", "evaluate_parametric_edges",
+           "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libemap_hip.so (include/emap_hip.h).
+"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h through its own table).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -177,7 +177,18 @@ SYMBOLS = {
     "emap_linspace_host": (None, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float)]),
 }
 
-_lib = _api = None
+# every symbol include/emap_eval_hip.h declares, in the same form: the second header of the same library, with its own version and its own
+# pair of views eval_lib() / eval_api().  SYMBOLS, lib() and api() are include/emap_hip.h's alone
+EVAL_ABI_VERSION = 1
+EVAL_POINTS_DTYPES = {torch.float64: 0, torch.float32: 1}                       # EMAP_EVAL_POINTS_*
+EVAL_MAPS_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}         # EMAP_EVAL_MAPS_*
+EVAL_SYMBOLS = {
+    "emap_eval_abi_version": (C.c_int, []),
+    "emap_point_visibility": (_RC, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                    _P, _P, _P]),
+}
+
+_lib = _api = _eval_lib = _eval_api = None
 
 
 class EmapLibraryError(RuntimeError):
@@ -214,8 +225,17 @@ def lib():
         l = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise EmapLibraryError(f"cannot load {LIB_PATH}: {e}") from e
+    a = _bind(l, SYMBOLS)
+    if l.emap_abi_version() != ABI_VERSION:
+        raise EmapLibraryError("libemap_hip.so ABI version mismatch")
+    _lib, _api = l, a
+    return l
+
+
+def _bind(l, symbols):
+    """Give every symbol of the table its restype / argtypes on the loaded library `l`; -> the checked view of the rc-returning ones."""
     a = types.SimpleNamespace()
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in symbols.items():
         try:
             fn = getattr(l, name)
         except AttributeError as e:
@@ -226,10 +246,25 @@ def lib():
             ck = l[name]            # indexing makes a function object of its own; the attribute above is the cached raw one
             ck.restype, ck.argtypes, ck.errcheck = C.c_int, [_Ptr if t is _P else t for t in args], _errcheck
             setattr(a, name[5:], ck)
-    if l.emap_abi_version() != ABI_VERSION:
-        raise EmapLibraryError("libemap_hip.so ABI version mismatch")
-    _lib, _api = l, a
+    return a
+
+
+def eval_lib():
+    """lib() with the symbols of include/emap_eval_hip.h bound as well (EVAL_SYMBOLS): the raw view of the second header."""
+    global _eval_lib, _eval_api
+    l = lib()
+    if _eval_lib is not l:          # first use, or lib() was reloaded
+        a = _bind(l, EVAL_SYMBOLS)
+        if l.emap_eval_abi_version() != EVAL_ABI_VERSION:
+            raise EmapLibraryError("libemap_hip.so evaluation ABI version mismatch (include/emap_eval_hip.h)")
+        _eval_lib, _eval_api = l, a
     return l
+
+
+def eval_api():
+    """The checked view of eval_lib(): one entry per rc-returning symbol of EVAL_SYMBOLS, named without ``emap_``; as api()."""
+    eval_lib()
+    return _eval_api
 
 
 def api():
