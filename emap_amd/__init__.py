@@ -18,6 +18,8 @@ from .parametric_edges import (sample_edges, bezier_curve_length, get_pred_point
                                compute_visibility, finish_parametric_edges, evaluate_parametric_edges)
 from . import dtu_eval  # noqa: F401
 from .dtu_eval import point_visibility_counts, compute_point_visibility, gt_edge_points, evaluate_dtu, DTU_SCANS  # noqa: F401
+from . import edge_fitting as fitting  # noqa: F401  (emap_amd.edge_fitting is the reference's FUNCTION, imported below; the module is emap_amd.fitting)
+from .edge_fitting import connect_points, edge_fitting, edge_fit, merge, get_parametric_edge  # noqa: F401
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
            "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
@@ -25,4 +27,5 @@ __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwo
            "downsample_point_cloud_average", "sample_segments", "evaluate_edges", "metrics_from_stats", "f_score",
            "parametric_edges", "sample_edges", "bezier_curve_length", "get_pred_points_and_directions", "process_geometry_data",
            "compute_visibility", "finish_parametric_edges", "evaluate_parametric_edges",
-           "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS"]
+           "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS",
+           "connect_points", "edge_fitting", "edge_fit", "merge", "get_parametric_edge"]

@@ -1,4 +1,4 @@
-"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h through its own table).
+"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h and include/emap_fit_hip.h through their own tables).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -188,7 +188,22 @@ EVAL_SYMBOLS = {
                                     _P, _P, _P]),
 }
 
-_lib = _api = _eval_lib = _eval_api = None
+# every symbol include/emap_fit_hip.h declares: the third header, with its own version and its own pair of views fit_lib() / fit_api()
+FIT_ABI_VERSION = 1
+FIT_MAX_POLYLINE_POINTS = 1024     # EMAP_FIT_MAX_POLYLINE_POINTS
+FIT_MAX_LINES = 16                 # EMAP_FIT_MAX_LINES
+FIT_LINK_LDS_POINTS = 1 << 20      # EMAP_FIT_LINK_LDS_POINTS
+FIT_SYMBOLS = {
+    "emap_fit_abi_version": (C.c_int, []),
+    "emap_fit_link": (_RC, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _P, _P, _P,
+                            _P, _P]),
+    "emap_fit_lines": (_RC, [_P, _P, C.c_int, C.c_double, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "emap_fit_beziers": (_RC, [_P, _P, C.c_int, _P, _P, _P]),
+    "emap_fit_merge_lines": (_RC, [_P, C.c_int, _P, _P, C.c_double, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "emap_fit_merge_endpoints": (_RC, [_P, C.c_int, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+}
+
+_lib = _api = _eval_lib = _eval_api = _fit_lib = _fit_api = None
 
 
 class EmapLibraryError(RuntimeError):
@@ -265,6 +280,24 @@ def eval_api():
     """The checked view of eval_lib(): one entry per rc-returning symbol of EVAL_SYMBOLS, named without ``emap_``; as api()."""
     eval_lib()
     return _eval_api
+
+
+def fit_lib():
+    """lib() with the symbols of include/emap_fit_hip.h bound as well (FIT_SYMBOLS): the raw view of the third header."""
+    global _fit_lib, _fit_api
+    l = lib()
+    if _fit_lib is not l:           # first use, or lib() was reloaded
+        a = _bind(l, FIT_SYMBOLS)
+        if l.emap_fit_abi_version() != FIT_ABI_VERSION:
+            raise EmapLibraryError("libemap_hip.so fitting ABI version mismatch (include/emap_fit_hip.h)")
+        _fit_lib, _fit_api = l, a
+    return l
+
+
+def fit_api():
+    """The checked view of fit_lib(): one entry per rc-returning symbol of FIT_SYMBOLS, named without ``emap_``; as api()."""
+    fit_lib()
+    return _fit_api
 
 
 def api():

@@ -263,6 +263,35 @@ def install(force: bool = True, patch_dataset: bool = True):
     return sorted(_ALIASES)
 
 
+def patch_edge_fitting():
+    """Point ``src.edge_extraction.extract_parametric_edge.get_parametric_edge`` - and the name the runner imported from it
+    (runner_udf.py:17), once that module is imported - at ``edge_fitting.get_parametric_edge``: fitting and merging on the device, with the
+    reference's two-argument signature.  With ``visible_checking`` the edge maps and cameras are read through the reference's own
+    ``get_edge_maps`` (from ``dataset_dir`` / ``scene_name`` / ``detector`` of the edge dict), as the reference does.  A separate step:
+    ``install()`` does not call it.  -> True when the reference module could be imported and was patched (it imports cv2)."""
+    try:
+        pe = importlib.import_module("src.edge_extraction.extract_parametric_edge")
+    except Exception:
+        return False
+    import os
+    fitting = importlib.import_module(__package__ + ".edge_fitting")      # the package attribute of that name is the function
+    get_edge_maps = pe.get_edge_maps
+
+    def get_parametric_edge(edge_dict, visible_checking=False):
+        if not visible_checking:
+            return fitting.get_parametric_edge(edge_dict, False)
+        edges, intrinsics_list, camtoworld_list, h, w = get_edge_maps(os.path.join(edge_dict["dataset_dir"], edge_dict["scene_name"]),
+                                                                      edge_dict["detector"])
+        return fitting.get_parametric_edge(edge_dict, True, edges, intrinsics_list, camtoworld_list, h, w)
+
+    get_parametric_edge.__wrapped__ = pe.get_parametric_edge
+    pe.get_parametric_edge = get_parametric_edge
+    rm = sys.modules.get("src.runner.runner_udf")
+    if rm is not None and hasattr(rm, "get_parametric_edge"):
+        rm.get_parametric_edge = get_parametric_edge
+    return True
+
+
 def patch_runner(train: bool = False):
     """Call after ``from src.runner.runner_udf import Runner_UDF``: wraps ``Runner_UDF.validate`` (see validate_wrapper) and, with
     ``train=True``, ``Runner_UDF.train_udf`` (see train_wrapper)."""

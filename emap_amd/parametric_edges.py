@@ -233,8 +233,8 @@ def compute_visibility(all_curve_points, all_line_points, edges, intrinsics_list
 
 def finish_parametric_edges(merged_edge_dict, visible_checking=False, edges=None, intrinsics_list=None, camtoworld_list=None, h=None, w=None,
                             device="cuda"):
-    """The tail of ``get_parametric_edge`` (extract_parametric_edge.py:257-300) behind the fitting and merging, which stay the reference's:
-    with ``visible_checking`` the edges whose control / end points are seen (threshold 0.5) in more than ``ceil(0.1 F)`` of the F edge maps
+    """The tail of ``get_parametric_edge`` (extract_parametric_edge.py:257-300) behind the fitting and merging (``edge_fitting.edge_fit`` and
+    ``edge_fitting.merge``; ``edge_fitting.get_parametric_edge`` runs all three): with ``visible_checking`` the edges whose control / end points are seen (threshold 0.5) in more than ``ceil(0.1 F)`` of the F edge maps
     are kept, then the kept edges are sampled with ``worldtogt`` = identity.  The maps and cameras the reference reads with
     ``get_edge_maps`` are arguments here.  -> ``(pred_points float32 numpy, return_edge_dict)``."""
     valid_curve = valid_line = None

@@ -23,7 +23,12 @@ udf_threshold 0.04 (a converged 4000-step run leaves a mean UDF of ~0.024 ON the
 (the reference's grid-stage normal is normalised per component, i.e. (+-1, +-1, +-1): with that floor on the wire a shift by df along it throws every
 point off the wire and the shift stage's filter keeps none - measured: 0 points), evaluated by `edge_metrics.evaluate_edges` against the
 wire frame sampled every 5 mm (`sample_segments(wireframe_segments())`): chamfer / acc / comp and precision / recall / F-score / IoU at
-5, 10 and 20 mm, added to the JSON line as "edge_metrics" (with the number of extracted points).  Without `--eval` the output is unchanged."""
+5, 10 and 20 mm, added to the JSON line as "edge_metrics" (with the number of extracted points).  Without `--eval` the output is unchanged.
+
+`--fit` goes on to the parametric edges, the form the paper's numbers are computed on: the same extraction with line directions
+(`is_linedirection=True`), `emap_amd.get_parametric_edge` (voxel down-sample, linking, line and Bezier fitting, merging, all on the device)
+and `parametric_edges.evaluate_parametric_edges` of the fitted edges against the same sampled wire frame, added to the JSON line as
+"parametric_edges" (numbers of lines and curves, the metrics).  Without `--fit` the output is unchanged."""
 import argparse
 import json
 import math
@@ -36,7 +41,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import emap_amd  # noqa: E402
-from emap_amd import edge_metrics, extraction, synthetic  # noqa: E402
+from emap_amd import edge_metrics, extraction, parametric_edges, synthetic  # noqa: E402
 from emap_amd.parallel import Trainer  # noqa: E402
 from emap_amd.validation import render_image  # noqa: E402
 
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--best", metavar="PATH", help="with --monitor: the checkpoint of the best window average of the edge loss")
     ap.add_argument("--window", type=int, default=500, help="with --monitor: iterations per loss average (the reference's 500)")
     ap.add_argument("--eval", action="store_true", help="extract the edge point cloud after training and add edge_metrics.evaluate_edges to the JSON line")
+    ap.add_argument("--fit", action="store_true", help="fit parametric edges to the extracted point cloud (get_parametric_edge) and add their metrics to the JSON line")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -164,6 +170,19 @@ def main():
         points, _ = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=128, udf_threshold=0.04, is_pointshift=False, device=dev)
         gt = edge_metrics.sample_segments(synthetic.wireframe_segments())
         edge_eval = {"edge_metrics": {"n_extracted": int(points.shape[0]), **(edge_metrics.evaluate_edges(points, gt, device=dev) if len(points) else {})}}
+    if a.fit:                      # train -> extract -> fit -> evaluate: the metrics of the fitted edges
+        n_mc = 128
+        points, line_directions = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=n_mc, udf_threshold=0.04, is_pointshift=False,
+                                                                     is_linedirection=True, device=dev)
+        fit_eval = {"n_extracted": int(points.shape[0])}
+        if len(points):
+            edge_dict = {"resolution": n_mc, "points": points, "ld_colors": (line_directions + 1) / 2.0}      # as runner_udf.py:541-561
+            _, fitted = emap_amd.get_parametric_edge(edge_dict, device=dev)
+            gt = edge_metrics.sample_segments(synthetic.wireframe_segments())
+            fit_eval.update(n_lines=len(fitted["lines_end_pts"]), n_curves=len(fitted["curves_ctl_pts"]))
+            if fit_eval["n_lines"] + fit_eval["n_curves"]:
+                fit_eval.update(parametric_edges.evaluate_parametric_edges(fitted, gt, device=dev))
+        edge_eval["parametric_edges"] = fit_eval
     print(json.dumps({
         "what": "training loop of runner_udf.py on a synthetic wire frame (13 segments, %d views %dx%d, view %d held out), HIP path only"
                 % (a.views, a.res, a.res, held_out),
