@@ -20,6 +20,8 @@ from . import dtu_eval  # noqa: F401
 from .dtu_eval import point_visibility_counts, compute_point_visibility, gt_edge_points, evaluate_dtu, DTU_SCANS  # noqa: F401
 from . import edge_fitting as fitting  # noqa: F401  (emap_amd.edge_fitting is the reference's FUNCTION, imported below; the module is emap_amd.fitting)
 from .edge_fitting import connect_points, edge_fitting, edge_fit, merge, get_parametric_edge  # noqa: F401
+from . import edge_raster  # noqa: F401
+from .edge_raster import rasterize_edges, rasterize_parametric_edges, to_dataset_edges, make_parametric_scene  # noqa: F401
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
            "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
@@ -28,4 +30,5 @@ __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwo
            "parametric_edges", "sample_edges", "bezier_curve_length", "get_pred_points_and_directions", "process_geometry_data",
            "compute_visibility", "finish_parametric_edges", "evaluate_parametric_edges",
            "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS",
-           "connect_points", "edge_fitting", "edge_fit", "merge", "get_parametric_edge"]
+           "connect_points", "edge_fitting", "edge_fit", "merge", "get_parametric_edge",
+           "edge_raster", "rasterize_edges", "rasterize_parametric_edges", "to_dataset_edges", "make_parametric_scene"]

@@ -1,4 +1,5 @@
-"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h and include/emap_fit_hip.h through their own tables).
+"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h, include/emap_fit_hip.h and include/emap_raster_hip.h through
+their own tables).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -203,7 +204,22 @@ FIT_SYMBOLS = {
     "emap_fit_merge_endpoints": (_RC, [_P, C.c_int, C.c_double, _P, _P, _P, C.c_size_t, _P]),
 }
 
-_lib = _api = _eval_lib = _eval_api = _fit_lib = _fit_api = None
+# every symbol include/emap_raster_hip.h declares: the fourth header, with its own version and its own pair of views raster_lib() / raster_api()
+RASTER_ABI_VERSION = 1
+RASTER_MAX_CURVE_SEGMENTS = 256    # EMAP_RASTER_MAX_CURVE_SEGMENTS
+RASTER_MAX_SEGMENTS = 1 << 20      # EMAP_RASTER_MAX_SEGMENTS
+RASTER_MAX_HALF_WIDTH = 64.0       # EMAP_RASTER_MAX_HALF_WIDTH
+RASTER_MAX_FRAMES = 65535          # EMAP_RASTER_MAX_FRAMES
+RASTER_MAX_DIM = 65536             # EMAP_RASTER_MAX_DIM
+RASTER_ROW_BYTES = 64              # EMAP_RASTER_ROW_BYTES
+RASTER_SYMBOLS = {
+    "emap_raster_abi_version": (C.c_int, []),
+    "emap_raster_workspace_bytes": (_RC, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "emap_raster_edges": (_RC, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _P, _P, _P,
+                                C.c_size_t, _P]),
+}
+
+_lib = _api = _eval_lib = _eval_api = _fit_lib = _fit_api = _raster_lib = _raster_api = None
 
 
 class EmapLibraryError(RuntimeError):
@@ -298,6 +314,24 @@ def fit_api():
     """The checked view of fit_lib(): one entry per rc-returning symbol of FIT_SYMBOLS, named without ``emap_``; as api()."""
     fit_lib()
     return _fit_api
+
+
+def raster_lib():
+    """lib() with the symbols of include/emap_raster_hip.h bound as well (RASTER_SYMBOLS): the raw view of the fourth header."""
+    global _raster_lib, _raster_api
+    l = lib()
+    if _raster_lib is not l:        # first use, or lib() was reloaded
+        a = _bind(l, RASTER_SYMBOLS)
+        if l.emap_raster_abi_version() != RASTER_ABI_VERSION:
+            raise EmapLibraryError("libemap_hip.so rasteriser ABI version mismatch (include/emap_raster_hip.h)")
+        _raster_lib, _raster_api = l, a
+    return l
+
+
+def raster_api():
+    """The checked view of raster_lib(): one entry per rc-returning symbol of RASTER_SYMBOLS, named without ``emap_``; as api()."""
+    raster_lib()
+    return _raster_api
 
 
 def api():

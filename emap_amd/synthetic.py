@@ -196,6 +196,44 @@ def make_wireframe_scene(n_images: int = 16, H: int = 200, W: int = 200, radius:
     return meta, edges
 
 
+def ring_cameras(n_images: int = 16, H: int = 200, W: int = 200, radius: float = 3.0, fov_deg: float = 30.0):
+    """The ``meta`` of make_wireframe_scene without its edge maps: the same ring of cameras, intrinsics and scene box, in the same
+    arithmetic - the two dicts are equal.  For scenes whose maps are drawn on the device (emap_amd.edge_raster.make_parametric_scene)."""
+    f = 0.5 * W / np.tan(np.deg2rad(fov_deg) / 2)
+    K = np.array([[f, 0, (W - 1) / 2, 0], [0, f, (H - 1) / 2, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float64)
+    frames = []
+    for i in range(n_images):
+        th, ph = 2 * np.pi * i / n_images + 0.2, 0.45 * np.sin(2.3 * i + 0.5)
+        c = radius * np.array([np.cos(th) * np.cos(ph), np.sin(ph), np.sin(th) * np.cos(ph)])
+        zax = -c / np.linalg.norm(c)
+        xax = np.cross([0.0, 1.0, 0.0], zax); xax /= np.linalg.norm(xax)
+        yax = np.cross(zax, xax)
+        c2w = np.eye(4); c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = xax, yax, zax, c
+        frames.append({"intrinsics": K.tolist(), "camtoworld": c2w.tolist(), "rgb_path": f"{i:04d}.png"})
+    return {"scene_box": {"near": 0.05, "far": 6.0, "radius": 1.0, "aabb": [[-1, -1, -1], [1, 1, 1]]}, "height": H, "width": W,
+            "frames": frames}
+
+
+def curved_wireframe(half: float = 0.45):
+    """A wire frame with curves, as parametric edges: ``(lines (12, 6), curves (6, 12))`` fp64 - end points and cubic Bezier control
+    points, flattened as ``parametric_edges.json`` holds them.  The 12 edges of the cube of wireframe_segments; a closed circle of radius
+    ``2 half / 3`` in the plane y = 0, four quarter arcs with the usual handle length 4 / 3 (sqrt 2 - 1) r; a quarter arc of radius
+    ``half`` that rounds one corner of the face x = -half; and one open S-shaped cubic on the face z = half.  Everything lies inside the
+    unit sphere for half <= 0.5."""
+    lines = wireframe_segments(half)[:12].reshape(12, 6)
+    k = 4.0 / 3.0 * (np.sqrt(2.0) - 1.0)
+    r = 2.0 * half / 3.0
+    quarter = lambda a, b, rad: [rad * a, rad * (a + k * b), rad * (k * a + b), rad * b]      # the arc from direction a to direction b
+    ex, ez = np.array([1.0, 0.0, 0.0]), np.array([0.0, 0.0, 1.0])
+    curves = [quarter(a, b, r) for a, b in ((ex, ez), (ez, -ex), (-ex, -ez), (-ez, ex))]
+    ey = np.array([0.0, 1.0, 0.0])
+    corner = np.array([-half, -half, -half])
+    curves.append([corner + p for p in quarter(ey, ez, half)])                                # on the face x = -half, centred on a corner
+    s = half * np.array([[-2 / 3, -2 / 3, 1.0], [4 / 3, -2 / 3, 1.0], [-4 / 3, 2 / 3, 1.0], [2 / 3, 2 / 3, 1.0]])
+    curves.append(list(s))
+    return lines, np.array(curves, dtype=np.float64).reshape(-1, 12)
+
+
 def scene_rays(meta, edges, img_idx: int, px, py, dtype=torch.float32):
     """Rays of given pixels of one view, as ``Dataset.gen_random_rays_patches_at`` builds them (reference src/dataset/dataset.py:244-287:
     p = K^-1 [x, y, 1], rays_v = R (p / |p|), rays_o = camera centre, depth_scale = the z component of p / |p|), in fp32 torch ops on

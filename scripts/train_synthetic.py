@@ -28,7 +28,13 @@ wire frame sampled every 5 mm (`sample_segments(wireframe_segments())`): chamfer
 `--fit` goes on to the parametric edges, the form the paper's numbers are computed on: the same extraction with line directions
 (`is_linedirection=True`), `emap_amd.get_parametric_edge` (voxel down-sample, linking, line and Bezier fitting, merging, all on the device)
 and `parametric_edges.evaluate_parametric_edges` of the fitted edges against the same sampled wire frame, added to the JSON line as
-"parametric_edges" (numbers of lines and curves, the metrics).  Without `--fit` the output is unchanged."""
+"parametric_edges" (numbers of lines and curves, the metrics).  Without `--fit` the output is unchanged.
+
+`--scene curved` trains on a wire frame WITH curves instead (`synthetic.curved_wireframe`: the cube's 12 edges, a circle of four cubic
+Beziers, a corner arc and an open S), its edge maps drawn on the device by `emap_amd.edge_raster.make_parametric_scene` in the same ring of
+cameras.  The ground truth of `--eval` and `--fit` is then `parametric_edges.sample_edges` of the scene's own lines and curves (every
+5 mm), the JSON line says "scene": "curved" with the numbers of ground-truth lines and curves, and "parametric_edges" carries how many
+curves the fit recovered.  Without `--scene` the run and its output are unchanged."""
 import argparse
 import json
 import math
@@ -41,7 +47,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import emap_amd  # noqa: E402
-from emap_amd import edge_metrics, extraction, parametric_edges, synthetic  # noqa: E402
+from emap_amd import edge_metrics, edge_raster, extraction, parametric_edges, synthetic  # noqa: E402
 from emap_amd.parallel import Trainer  # noqa: E402
 from emap_amd.validation import render_image  # noqa: E402
 
@@ -62,6 +68,8 @@ def main():
     ap.add_argument("--window", type=int, default=500, help="with --monitor: iterations per loss average (the reference's 500)")
     ap.add_argument("--eval", action="store_true", help="extract the edge point cloud after training and add edge_metrics.evaluate_edges to the JSON line")
     ap.add_argument("--fit", action="store_true", help="fit parametric edges to the extracted point cloud (get_parametric_edge) and add their metrics to the JSON line")
+    ap.add_argument("--scene", choices=("wireframe", "curved"), default="wireframe",
+                    help="curved: synthetic.curved_wireframe (lines and cubic Beziers), rasterised on the device")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -71,7 +79,13 @@ def main():
     bet = emap_amd.BetaNetwork(0.5, 0.3, 0.3, 5e-5, True, True, False).to(dev)
     r = emap_amd.UDFRendererBlending(None, net, devn, bet, n_samples=64, n_importance=64, n_outside=0, up_sample_steps=4,
                                      perturb=1.0, device=dev)
-    meta, edges = synthetic.make_wireframe_scene(n_images=a.views, H=a.res, W=a.res)
+    if a.scene == "curved":
+        gt_lines, gt_curves = synthetic.curved_wireframe()
+        meta, edges = edge_raster.make_parametric_scene(gt_lines, gt_curves, n_images=a.views, H=a.res, W=a.res, device=dev)
+        gt_points = lambda: parametric_edges.sample_edges(gt_curves.reshape(-1, 4, 3), gt_lines.reshape(-1, 2, 3), device=dev).points.float()
+    else:
+        meta, edges = synthetic.make_wireframe_scene(n_images=a.views, H=a.res, W=a.res)
+        gt_points = lambda: edge_metrics.sample_segments(synthetic.wireframe_segments())
     sampler = emap_amd.DeviceRaySampler.from_meta(meta, edges, device=dev, seed=5)
     held_out = 0
     sampler.set_train_images([i for i in range(a.views) if i != held_out])
@@ -100,9 +114,12 @@ def main():
         return 10.0 * math.log10(1.0 / max(mse, 1e-12)), mse
 
     def udf_on_off():
-        segs = torch.tensor(synthetic.wireframe_segments(), dtype=torch.float32, device=dev)
-        tt = torch.linspace(0.05, 0.95, 64, device=dev).view(1, -1, 1)
-        on = (segs[:, :1] * (1 - tt) + segs[:, 1:] * tt).reshape(-1, 3)
+        if a.scene == "curved":
+            on = gt_points()
+        else:
+            segs = torch.tensor(synthetic.wireframe_segments(), dtype=torch.float32, device=dev)
+            tt = torch.linspace(0.05, 0.95, 64, device=dev).view(1, -1, 1)
+            on = (segs[:, :1] * (1 - tt) + segs[:, 1:] * tt).reshape(-1, 3)
         g = torch.Generator(device="cpu").manual_seed(1)
         off = (torch.rand(4096, 3, generator=g) * 1.6 - 0.8).to(dev)
         d = torch.cdist(off, on).min(1).values
@@ -168,7 +185,7 @@ def main():
     edge_eval = {}
     if a.eval:                     # the product's own measure: extracted edge points against the sampled wire frame
         points, _ = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=128, udf_threshold=0.04, is_pointshift=False, device=dev)
-        gt = edge_metrics.sample_segments(synthetic.wireframe_segments())
+        gt = gt_points()
         edge_eval = {"edge_metrics": {"n_extracted": int(points.shape[0]), **(edge_metrics.evaluate_edges(points, gt, device=dev) if len(points) else {})}}
     if a.fit:                      # train -> extract -> fit -> evaluate: the metrics of the fitted edges
         n_mc = 128
@@ -178,14 +195,16 @@ def main():
         if len(points):
             edge_dict = {"resolution": n_mc, "points": points, "ld_colors": (line_directions + 1) / 2.0}      # as runner_udf.py:541-561
             _, fitted = emap_amd.get_parametric_edge(edge_dict, device=dev)
-            gt = edge_metrics.sample_segments(synthetic.wireframe_segments())
+            gt = gt_points()
             fit_eval.update(n_lines=len(fitted["lines_end_pts"]), n_curves=len(fitted["curves_ctl_pts"]))
             if fit_eval["n_lines"] + fit_eval["n_curves"]:
                 fit_eval.update(parametric_edges.evaluate_parametric_edges(fitted, gt, device=dev))
         edge_eval["parametric_edges"] = fit_eval
+    scene = {"scene": "curved", "gt_lines": len(gt_lines), "gt_curves": len(gt_curves)} if a.scene == "curved" else {}
     print(json.dumps({
-        "what": "training loop of runner_udf.py on a synthetic wire frame (13 segments, %d views %dx%d, view %d held out), HIP path only"
-                % (a.views, a.res, a.res, held_out),
+        "what": "training loop of runner_udf.py on a synthetic wire frame (%s, %d views %dx%d, view %d held out), HIP path only"
+                % ("12 segments and 6 cubic Beziers" if a.scene == "curved" else "13 segments", a.views, a.res, a.res, held_out),
+        **scene,
         "graph": bool(a.graph), "steps": a.steps, "rays_per_step": a.rays, "precision": a.precision, "wall_s": wall, "ms_per_step_incl_python": wall / max(a.steps - first, 1) * 1e3, "first_step": first,
         "held_out_view_psnr_db": {"before": psnr0[0], "after": psnr1[0]}, "train_view_psnr_db_after": psnr_train[0],
         "mean_udf_on_wireframe": {"before": u0[0], "after": u1[0]}, "mean_udf_away_from_it": {"before": u0[1], "after": u1[1]},
