@@ -1,5 +1,4 @@
-"""ctypes binding of libemap_hip.so (include/emap_hip.h, and include/emap_eval_hip.h, include/emap_fit_hip.h and include/emap_raster_hip.h through
-their own tables).
+"""ctypes binding of libemap_hip.so: the four headers under include/, each through its own table and pair of views (HEADERS).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -112,7 +111,7 @@ SYMBOLS = {
     "emap_compact_workspace_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
     "emap_compact_append": (_RC, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_int, _P, _P, _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "emap_jitter_points": (_RC, [_P, _P, C.c_int64, C.c_int, C.c_float, _P, _P]),
-    "emap_shift_points": (_RC, [_P, _P, _P, C.c_int64, _P]),
+    "emap_shift_points": (_RC, [_P, _P, _P, C.c_int64, _P, _P]),
     "emap_nn_workspace_bytes": (_RC, [C.c_int64, C.POINTER(C.c_size_t)]),
     "emap_nearest_neighbors": (_RC, [_P, C.c_int64, _P, C.c_int64, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "emap_dist_stats": (_RC, [_P, C.c_int64, C.POINTER(C.c_float), C.c_int, _P, _P]),
@@ -178,8 +177,7 @@ SYMBOLS = {
     "emap_linspace_host": (None, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_float)]),
 }
 
-# every symbol include/emap_eval_hip.h declares, in the same form: the second header of the same library, with its own version and its own
-# pair of views eval_lib() / eval_api().  SYMBOLS, lib() and api() are include/emap_hip.h's alone
+# every symbol include/emap_eval_hip.h declares, in the same form: the second header of the same library (HEADERS, below)
 EVAL_ABI_VERSION = 1
 EVAL_POINTS_DTYPES = {torch.float64: 0, torch.float32: 1}                       # EMAP_EVAL_POINTS_*
 EVAL_MAPS_DTYPES = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}         # EMAP_EVAL_MAPS_*
@@ -189,7 +187,7 @@ EVAL_SYMBOLS = {
                                     _P, _P, _P]),
 }
 
-# every symbol include/emap_fit_hip.h declares: the third header, with its own version and its own pair of views fit_lib() / fit_api()
+# every symbol include/emap_fit_hip.h declares: the third header
 FIT_ABI_VERSION = 1
 FIT_MAX_POLYLINE_POINTS = 1024     # EMAP_FIT_MAX_POLYLINE_POINTS
 FIT_MAX_LINES = 16                 # EMAP_FIT_MAX_LINES
@@ -204,7 +202,7 @@ FIT_SYMBOLS = {
     "emap_fit_merge_endpoints": (_RC, [_P, C.c_int, C.c_double, _P, _P, _P, C.c_size_t, _P]),
 }
 
-# every symbol include/emap_raster_hip.h declares: the fourth header, with its own version and its own pair of views raster_lib() / raster_api()
+# every symbol include/emap_raster_hip.h declares: the fourth header
 RASTER_ABI_VERSION = 1
 RASTER_MAX_CURVE_SEGMENTS = 256    # EMAP_RASTER_MAX_CURVE_SEGMENTS
 RASTER_MAX_SEGMENTS = 1 << 20      # EMAP_RASTER_MAX_SEGMENTS
@@ -219,7 +217,30 @@ RASTER_SYMBOLS = {
                                 C.c_size_t, _P]),
 }
 
-_lib = _api = _eval_lib = _eval_api = _fit_lib = _fit_api = _raster_lib = _raster_api = None
+# the four headers of the one library, each with its own table, version and pair of views: all that _view() and tests/test_headers_cpu.py
+# know of them.  `constants`: the #defines this module mirrors, name -> Python value
+HEADERS = {
+    "main": dict(header="emap_hip.h", symbols=SYMBOLS, version_fn="emap_abi_version", version=ABI_VERSION, mismatch="libemap_hip.so ABI version mismatch",
+                 constants={**{"EMAP_PREC_" + k.upper(): v for k, v in PRECISIONS.items()}, **{"EMAP_UDF_" + k.upper(): v for k, v in UDF_TYPES.items()},
+                            "EMAP_MAX_LIN": MAX_LIN, "EMAP_MAX_TRAIN_IMAGES": MAX_TRAIN_IMAGES, "EMAP_MAX_SAMPLES_PER_RAY": MAX_SAMPLES_PER_RAY,
+                            "EMAP_RENDER_UNBIASED": RENDER_UNBIASED, "EMAP_RENDER_UNBIASED_NORMCOS": RENDER_UNBIASED_NORMCOS, "EMAP_RENDER_PLAIN": RENDER_PLAIN,
+                            "EMAP_F_NAN_SAMPLES": F_NAN_SAMPLES, "EMAP_F_NAN_GRADERR": F_NAN_GRADERR, "EMAP_F_MLP_NONFINITE": F_MLP_NONFINITE}),
+    "eval": dict(header="emap_eval_hip.h", symbols=EVAL_SYMBOLS, version_fn="emap_eval_abi_version", version=EVAL_ABI_VERSION,
+                 mismatch="libemap_hip.so evaluation ABI version mismatch (include/emap_eval_hip.h)",
+                 constants={"EMAP_EVAL_POINTS_F64": EVAL_POINTS_DTYPES[torch.float64], "EMAP_EVAL_POINTS_F32": EVAL_POINTS_DTYPES[torch.float32],
+                            **{"EMAP_EVAL_MAPS_" + k: EVAL_MAPS_DTYPES[t] for k, t in (("U8", torch.uint8), ("F32", torch.float32), ("F64", torch.float64))}}),
+    "fit": dict(header="emap_fit_hip.h", symbols=FIT_SYMBOLS, version_fn="emap_fit_abi_version", version=FIT_ABI_VERSION,
+                mismatch="libemap_hip.so fitting ABI version mismatch (include/emap_fit_hip.h)",
+                constants={"EMAP_FIT_MAX_POLYLINE_POINTS": FIT_MAX_POLYLINE_POINTS, "EMAP_FIT_MAX_LINES": FIT_MAX_LINES, "EMAP_FIT_LINK_LDS_POINTS": FIT_LINK_LDS_POINTS}),
+    "raster": dict(header="emap_raster_hip.h", symbols=RASTER_SYMBOLS, version_fn="emap_raster_abi_version", version=RASTER_ABI_VERSION,
+                   mismatch="libemap_hip.so rasteriser ABI version mismatch (include/emap_raster_hip.h)",
+                   constants={"EMAP_RASTER_MAX_CURVE_SEGMENTS": RASTER_MAX_CURVE_SEGMENTS, "EMAP_RASTER_MAX_SEGMENTS": RASTER_MAX_SEGMENTS,
+                              "EMAP_RASTER_MAX_HALF_WIDTH": RASTER_MAX_HALF_WIDTH, "EMAP_RASTER_MAX_FRAMES": RASTER_MAX_FRAMES,
+                              "EMAP_RASTER_MAX_DIM": RASTER_MAX_DIM, "EMAP_RASTER_ROW_BYTES": RASTER_ROW_BYTES}),
+}
+
+_lib = None         # the loaded library; setting it to None makes the next call load it again (__graft_entry__.verify_library)
+_views = {}         # header key -> (the library its symbols were bound on, its checked view)
 
 
 class EmapLibraryError(RuntimeError):
@@ -242,25 +263,14 @@ def _errcheck(rc, fn, args):
     return rc
 
 
-def lib():
-    """Load (once) and return the bound library: raw ctypes functions that return the rc.  Raises EmapLibraryError if it is not built."""
-    global _lib, _api
-    if _lib is not None:
-        return _lib
+def _load():
     if not os.path.exists(LIB_PATH):
-        raise EmapLibraryError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (or emap_amd/csrc/build.sh). "
-            "emap_amd has no CPU fallback.")
+        raise EmapLibraryError(f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+                               "(or emap_amd/csrc/build.sh). emap_amd has no CPU fallback.")
     try:
-        l = C.CDLL(LIB_PATH)
+        return C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise EmapLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    a = _bind(l, SYMBOLS)
-    if l.emap_abi_version() != ABI_VERSION:
-        raise EmapLibraryError("libemap_hip.so ABI version mismatch")
-    _lib, _api = l, a
-    return l
 
 
 def _bind(l, symbols):
@@ -280,65 +290,54 @@ def _bind(l, symbols):
     return a
 
 
-def eval_lib():
-    """lib() with the symbols of include/emap_eval_hip.h bound as well (EVAL_SYMBOLS): the raw view of the second header."""
-    global _eval_lib, _eval_api
-    l = lib()
-    if _eval_lib is not l:          # first use, or lib() was reloaded
-        a = _bind(l, EVAL_SYMBOLS)
-        if l.emap_eval_abi_version() != EVAL_ABI_VERSION:
-            raise EmapLibraryError("libemap_hip.so evaluation ABI version mismatch (include/emap_eval_hip.h)")
-        _eval_lib, _eval_api = l, a
-    return l
+def _view(key):
+    """(raw, checked) views of the header HEADERS[key]: the library with the header's symbols bound, and one entry per rc-returning symbol.
+    The main header's first use loads the library; a header is bound and its version checked on first use, and again after a reload."""
+    global _lib
+    l = _view("main")[0] if key != "main" else _lib if _lib is not None else _load()
+    if key not in _views or _views[key][0] is not l:
+        h = HEADERS[key]
+        a = _bind(l, h["symbols"])
+        if getattr(l, h["version_fn"])() != h["version"]:
+            raise EmapLibraryError(h["mismatch"])
+        _lib, _views[key] = l, (l, a)
+    return _views[key]
 
 
-def eval_api():
-    """The checked view of eval_lib(): one entry per rc-returning symbol of EVAL_SYMBOLS, named without ``emap_``; as api()."""
-    eval_lib()
-    return _eval_api
-
-
-def fit_lib():
-    """lib() with the symbols of include/emap_fit_hip.h bound as well (FIT_SYMBOLS): the raw view of the third header."""
-    global _fit_lib, _fit_api
-    l = lib()
-    if _fit_lib is not l:           # first use, or lib() was reloaded
-        a = _bind(l, FIT_SYMBOLS)
-        if l.emap_fit_abi_version() != FIT_ABI_VERSION:
-            raise EmapLibraryError("libemap_hip.so fitting ABI version mismatch (include/emap_fit_hip.h)")
-        _fit_lib, _fit_api = l, a
-    return l
-
-
-def fit_api():
-    """The checked view of fit_lib(): one entry per rc-returning symbol of FIT_SYMBOLS, named without ``emap_``; as api()."""
-    fit_lib()
-    return _fit_api
-
-
-def raster_lib():
-    """lib() with the symbols of include/emap_raster_hip.h bound as well (RASTER_SYMBOLS): the raw view of the fourth header."""
-    global _raster_lib, _raster_api
-    l = lib()
-    if _raster_lib is not l:        # first use, or lib() was reloaded
-        a = _bind(l, RASTER_SYMBOLS)
-        if l.emap_raster_abi_version() != RASTER_ABI_VERSION:
-            raise EmapLibraryError("libemap_hip.so rasteriser ABI version mismatch (include/emap_raster_hip.h)")
-        _raster_lib, _raster_api = l, a
-    return l
-
-
-def raster_api():
-    """The checked view of raster_lib(): one entry per rc-returning symbol of RASTER_SYMBOLS, named without ``emap_``; as api()."""
-    raster_lib()
-    return _raster_api
+def lib():
+    """Load (once) and return the bound library: raw ctypes functions that return the rc.  Raises EmapLibraryError if it is not built."""
+    return _view("main")[0]
 
 
 def api():
     """The checked view of lib(): one entry per rc-returning symbol, named without ``emap_`` (``api().render_fwd``).  A call raises
     what check() raises when the rc is not 0; void* parameters take tensors (_Ptr) and struct parameters take the struct itself.
     Package code calls the library through this view; lib() is for code that looks at return codes."""
-    return _api if _api is not None else lib() and _api
+    return _view("main")[1]
+
+
+def eval_lib():         # lib() with the symbols of include/emap_eval_hip.h bound as well (EVAL_SYMBOLS): the raw view of the second header
+    return _view("eval")[0]
+
+
+def eval_api():         # the checked view of eval_lib(): one entry per rc-returning symbol of EVAL_SYMBOLS, named without emap_; as api()
+    return _view("eval")[1]
+
+
+def fit_lib():         # lib() with the symbols of include/emap_fit_hip.h bound as well (FIT_SYMBOLS): the raw view of the third header
+    return _view("fit")[0]
+
+
+def fit_api():         # the checked view of fit_lib(): one entry per rc-returning symbol of FIT_SYMBOLS, named without emap_; as api()
+    return _view("fit")[1]
+
+
+def raster_lib():         # lib() with the symbols of include/emap_raster_hip.h bound as well (RASTER_SYMBOLS): the raw view of the fourth header
+    return _view("raster")[0]
+
+
+def raster_api():         # the checked view of raster_lib(): one entry per rc-returning symbol of RASTER_SYMBOLS, named without emap_; as api()
+    return _view("raster")[1]
 
 
 def size_of(query: str, *args) -> int:

@@ -8,7 +8,7 @@ The rest is composition of what the package has: ``edge_metrics.downsample_point
 ``parametric_edges.sample_edges``.
 
 Projection conventions are those of ``parametric_edges.compute_visibility`` (a different routine: the mean over a handful of control points
-per fitted edge): fp64, ``K @ (R @ X + T)`` with the world-to-camera matrix formed by ``np.linalg.inv(camtoworld)`` on the host, divided by
+per fitted edge): fp64, ``K @ (R @ X + T)`` with K, R and T formed on the host (``_inputs.world_to_camera``), divided by
 its third row, no depth test, pixels rounded half to even, a point valid when ``0 <= u < w`` and ``0 <= v < h`` on the rounded doubles.
 The kernel takes every 3-term sum left to right without FMA contraction, so the pixel is a pure function of the inputs.
 
@@ -19,17 +19,17 @@ widened to double, which can differ from a float64 map within float32 rounding o
 
 numpy inputs go to ``device``; tensors are used where they are.  There is no CPU fallback: without a GPU the calls raise ``RuntimeError``.
 """
-import json
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, edge_metrics, parametric_edges
+from . import _inputs, _lib, edge_metrics, parametric_edges
 
 VIS_THREADS = 256          # csrc/visibility.hip: VIS_THREADS
 VIS_CHUNK = 64             # frames whose cameras sit in LDS at a time        (csrc/visibility.hip: VIS_CHUNK)
 VIS_MAX_BLOCKS = 2048      # workgroups of a launch; more than VIS_MAX_BLOCKS * VIS_THREADS points take the grid stride
+POINT_DTYPES = (torch.float32, torch.float64)       # _lib.EVAL_POINTS_DTYPES: points of these stay as they are, any other becomes float64
 
 # scan -> (edge_visibility_threshold, edge_visibility_frames_ratio): the table of scripts/get_gt_points_DTU.py:229-236
 DTU_SCANS = {
@@ -47,55 +47,24 @@ def visibility_frames(edge_visibility_frames_ratio, num_frames):
     return max(1, round(edge_visibility_frames_ratio * num_frames))
 
 
-def _host(a, dtype=np.float64):
-    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
-
-
-def _points(points, device):
-    """(n, 3) contiguous fp64 or fp32 tensor: numpy (or a list) goes to ``device``, a tensor stays; any dtype but float32 becomes float64."""
-    if isinstance(points, torch.Tensor):
-        t = points.detach()
-    else:
-        a = np.asarray(points)
-        t = torch.as_tensor(a if a.dtype == np.float32 else a.astype(np.float64, copy=False)).to(device)
-    if t.dtype not in _lib.EVAL_POINTS_DTYPES:
-        t = t.to(torch.float64)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"dtu_eval: points must be (n, 3), got {tuple(t.shape)}")
-    return t.contiguous()
-
-
 def _maps(edge_maps, h, w, device):
     """(F, h, w) contiguous tensor of uint8 / float32 / float64: the reference's (F, h, w, 1) numpy array goes to ``device`` in its own
     dtype (any other dtype as float64), a tensor stays where it is."""
-    if isinstance(edge_maps, torch.Tensor):
-        t = edge_maps.detach()
-    else:
-        a = np.asarray(edge_maps)
-        t = torch.as_tensor(a if a.dtype in (np.uint8, np.float32, np.float64) else a.astype(np.float64)).to(device)
-    if t.dtype not in _lib.EVAL_MAPS_DTYPES:
-        t = t.to(torch.float64)
-    if t.dim() == 4 and t.shape[3] == 1:
-        t = t[..., 0]
-    if t.dim() != 3 or tuple(t.shape[1:]) != (int(h), int(w)) or t.shape[0] == 0:
-        raise ValueError(f"dtu_eval: edge_maps must be (F, {h}, {w}) or (F, {h}, {w}, 1) with F > 0, got {tuple(edge_maps.shape)}")
-    return t.contiguous()
+    t = _inputs.to_device(edge_maps, device, torch.float64, keep=tuple(_lib.EVAL_MAPS_DTYPES))
+    return _inputs.edge_maps(t, h, w, "dtu_eval: edge_maps", nonempty=True)
 
 
 def _cameras(intrinsics_list, camtoworld_list, F, device):
-    """K (F, 3, 3), R (F, 3, 3), T (F, 3) fp64 on ``device``: K = intrinsic[:3, :3], [R | T] = np.linalg.inv(camtoworld)[:3] on the host,
-    as the reference forms them per frame (:110-111, :133-134); F small matrices."""
+    """K (F, 3, 3), R (F, 3, 3), T (F, 3) fp64 on ``device`` (``_inputs.world_to_camera``, as the reference forms them per frame: :110-111,
+    :133-134): three small copies."""
     if len(intrinsics_list) != F or len(camtoworld_list) != F:
         raise ValueError(f"dtu_eval: {F} edge maps, {len(intrinsics_list)} intrinsics, {len(camtoworld_list)} poses")
-    K = np.stack([_host(k)[:3, :3] for k in intrinsics_list])
-    w2c = np.stack([np.linalg.inv(_host(c)) for c in camtoworld_list])
-    put = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(device)
-    return put(K), put(w2c[:, :3, :3]), put(w2c[:, :3, 3])
+    return tuple(torch.as_tensor(a).to(device) for a in _inputs.world_to_camera(intrinsics_list, camtoworld_list))
 
 
 def _visibility(points, edge_maps, intrinsics_list, camtoworld_list, h, w, threshold, invert, min_frames, want_mask, device):
     """The launch: -> (count (n) int32, mask (n) uint8 or None) on the device of the points."""
-    pts = _points(points, device)
+    pts = _inputs.points(points, device, "dtu_eval", POINT_DTYPES)
     maps = _maps(edge_maps, h, w, device)
     _lib.require_cuda(pts, "points")
     _lib.require_cuda(maps, "edge_maps")
@@ -149,9 +118,9 @@ def gt_edge_points(gt_points, worldtogt, edge_maps, intrinsics_list, camtoworld_
     ``edge_metrics.downsample_point_cloud_average`` over the survivors' own extent, and the transform back.  No point data goes through
     the host.  The selection synchronises once, for the number of survivors; the down-sampling's own dynamic shapes (points inside the
     bounds, occupied voxels) are further synchronisations of torch's."""
-    worldtogt = _host(worldtogt)
+    worldtogt = _inputs.host64(worldtogt)
     gttoworld = np.linalg.inv(worldtogt)
-    pts = _points(gt_points, device).to(torch.float64)
+    pts = _inputs.points(gt_points, device, "dtu_eval", POINT_DTYPES).to(torch.float64)
     _lib.require_cuda(pts, "gt_points")
     pts = _affine(pts, gttoworld)
     frames = visibility_frames(edge_visibility_frames_ratio, len(edge_maps))
@@ -171,14 +140,13 @@ def evaluate_dtu(pred, gt_edge_points, worldtogt, threshold=5.0, num_voxels_per_
     -> ``{"precision", "recall", "n_pred", "n_gt", "hits_pred", "hits_gt"}``: precision = hits_pred / n_pred over the down-sampled
     prediction, recall = hits_gt / n_gt over the ground truth."""
     if isinstance(pred, (str, os.PathLike)):
-        with open(pred, "r") as f:
-            d = json.load(f)
+        d = _inputs.load_edge_dict(pred)
         pts = parametric_edges.sample_edges(d["curves_ctl_pts"], d["lines_end_pts"], device=device).points
     else:
-        pts = _points(pred, device).to(torch.float64)
+        pts = _inputs.points(pred, device, "dtu_eval", POINT_DTYPES).to(torch.float64)
     _lib.require_cuda(pts, "pred")
-    gt = edge_metrics._points(gt_edge_points, pts.device)
-    pts = _affine(pts, _host(worldtogt))
+    gt = _inputs.points(gt_edge_points, pts.device, "edge_metrics")
+    pts = _affine(pts, _inputs.host64(worldtogt))
     down = edge_metrics.downsample_point_cloud_average(pts, num_voxels_per_axis=num_voxels_per_axis)
     if down.shape[0] == 0 or gt.shape[0] == 0:
         raise ValueError(f"evaluate_dtu: empty point set (pred {int(down.shape[0])} points after down-sampling, gt {int(gt.shape[0])})")

@@ -26,7 +26,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, parametric_edges
+from . import _inputs, _lib, parametric_edges
 
 MAX_POLYLINE_POINTS = _lib.FIT_MAX_POLYLINE_POINTS     # csrc/fitting.hip: FIT_MAX_PTS - 8 scene units of edge at res 256
 MAX_LINES = _lib.FIT_MAX_LINES
@@ -40,18 +40,12 @@ def _finite(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(float(v))
 
 
-def _to_device(a, device, dtype=torch.float64):
-    """A tensor stays on its device; anything else goes to ``device`` (as in ``parametric_edges``)."""
-    t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64)).to(device)
-    return t.to(dtype).contiguous()
-
-
 # ---------------------------------------------------------------------------------------------------------------- voxel down-sample
 def voxel_down_sample(points, colors, voxel_size):
     """One point per occupied voxel: the mean of the voxel's points AND colours, as ``pcd.voxel_down_sample(voxel_size)`` in ``edge_fit``.
     The voxel index is ``floor((p - (min_bound - voxel_size / 2)) / voxel_size)`` with ``min_bound`` the points' own minimum - open3d's
     documented rule; the output is ordered by index, first axis slowest.  Tensors (n, 3) in, tensors on the same device out (fp64); torch
-    only (a stable sort, ``unique_consecutive``, differences of an fp64 cumulative sum, as ``edge_metrics._downsample``), so it runs on CPU
+    only (a stable sort, ``unique_consecutive``, differences of an fp64 cumulative sum, as ``edge_metrics.downsample_point_cloud_average``), so it runs on CPU
     and GPU tensors, deterministically.
 
     open3d's OUTPUT ORDER is unspecified (a hash map's), and open3d is not available to this project, so its result could not be compared;
@@ -133,7 +127,7 @@ def link(points, distance_threshold, angle_threshold, nms_factor, keep_short_lin
     is ``chain[offsets[k]:offsets[k + 1]]``.  ``vis_global`` and ``cell_scale`` change where the visited bits live and how coarse the grid
     is, never the result.  ``return_stats`` adds a dict with the numbers of steps and seeds of the walk."""
     _check_link_args(distance_threshold, angle_threshold, nms_factor)
-    pts = _to_device(points, device).reshape(-1, 6)
+    pts = _inputs.to_device(points, device).reshape(-1, 6)
     _lib.require_cuda(pts, "points")
     n, dev = int(pts.shape[0]), pts.device
     cell_xyz, cell_start, order, dims = link_grid(pts[:, :3], distance_threshold, cell_scale)
@@ -320,7 +314,7 @@ def edge_fit(edge_data=None, angle_threshold=0.03, nms_factor=0.9, fit_distance_
     if not (math.isfinite(res) and res > 0):
         raise ValueError(f"edge_fit: resolution must be finite and > 0 (got {res!r})")
     _check_link_args(fit_distance_threshold / res, angle_threshold, nms_factor)
-    pts, col = _to_device(edge_data["points"], device).reshape(-1, 3), _to_device(edge_data["ld_colors"], device).reshape(-1, 3)
+    pts, col = _inputs.to_device(edge_data["points"], device).reshape(-1, 3), _inputs.to_device(edge_data["ld_colors"], device).reshape(-1, 3)
     if pts.shape[0] != col.shape[0]:
         raise ValueError(f"edge_fit: {pts.shape[0]} points, {col.shape[0]} ld_colors")
     _lib.require_cuda(pts, "points")

@@ -17,20 +17,11 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _inputs, _lib
 
 NN_Q_TILE = 1024        # queries per workgroup of the search kernel (csrc/metrics.hip: NN_Q_TILE)
 NN_R_TILE = 1024        # references per LDS tile                     (csrc/metrics.hip: NN_R_TILE)
 MAX_THRESHOLDS = 8      # thresholds per emap_dist_stats launch
-
-
-def _points(a, device):
-    """(n, 3) fp32 contiguous tensor: a numpy array (or list) goes to ``device``, a tensor stays where it is."""
-    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), device=device)
-    t = _lib.f32c(t)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"edge_metrics: points must be (n, 3), got {tuple(t.shape)}")
-    return t
 
 
 def nearest_neighbors(a, b, split=0, device="cuda"):
@@ -38,7 +29,7 @@ def nearest_neighbors(a, b, split=0, device="cuda"):
     plain distance as ``pcu.k_nearest_neighbors(a, b, k=1, squared_distances=False)``.  Bit-exact and deterministic (module docstring);
     ``split`` forces the number of splits of ``b`` over workgroups (0: automatic) and never changes the result.  A row of ``a`` with a
     NaN gets idx -1 and dist NaN."""
-    a, b = _points(a, device), _points(b, device)
+    a, b = _inputs.points(a, device, "edge_metrics"), _inputs.points(b, device, "edge_metrics")
     _lib.require_cuda(a, "a")
     _lib.require_cuda(b, "b")
     if b.device != a.device:
@@ -75,7 +66,7 @@ def dist_stats(dist, thresholds=()):
 def _both_ways(pred, gt, thresholds, device):
     """The two searches and their statistics: (stats (2, 1 + n_thr) on the HOST - row 0 pred -> gt, row 1 gt -> pred -, idx pred -> gt,
     idx gt -> pred).  One search per direction whatever the number of thresholds; one device-to-host copy."""
-    pred, gt = _points(pred, device), _points(gt, device)
+    pred, gt = _inputs.points(pred, device, "edge_metrics"), _inputs.points(gt, device, "edge_metrics")
     thresholds = list(thresholds)
     d_pg, i_pg = nearest_neighbors(pred, gt)
     d_gp, i_gp = nearest_neighbors(gt, pred)
@@ -234,7 +225,7 @@ def evaluate_edges(pred, gt, thresholds=(0.005, 0.01, 0.02), downsample=256, dev
     thresholds = tuple(thresholds)
     if len(thresholds) > MAX_THRESHOLDS:
         raise ValueError(f"evaluate_edges: at most {MAX_THRESHOLDS} thresholds (got {len(thresholds)})")
-    pred, gt = _points(pred, device), _points(gt, device)
+    pred, gt = _inputs.points(pred, device, "edge_metrics"), _inputs.points(gt, device, "edge_metrics")
     if downsample is not None:
         pred = _downsample(pred, downsample, [-1, -1, -1], [1, 1, 1])
     if pred.shape[0] == 0 or gt.shape[0] == 0:

@@ -9,33 +9,23 @@ one workgroup per frame and tile of pixels, and stores every byte once.  The pix
 
 EDGE e < L is line e, edge L + j is curve j: the order of the two list arguments, and the order ``weights`` and the ids follow.  Cameras are
 what ``parametric_edges.compute_visibility`` and ``dtu_eval`` take: ``intrinsics_list`` (F, 4, 4) or (F, 3, 3), ``camtoworld_list``
-(F, 4, 4), the world-to-camera matrix formed by ``np.linalg.inv`` on the host.  There is no occlusion: the scene has no surfaces.
+(F, 4, 4), K, R and T formed on the host by ``_inputs.world_to_camera``.  There is no occlusion: the scene has no surfaces.
 
 numpy inputs go to ``device``; tensors are used where they are.  There is no CPU fallback: without a GPU the calls raise ``RuntimeError``.
 """
-import json
-import os
-
 import numpy as np
 import torch
 
-from . import _lib, synthetic
+from . import _inputs, _lib, synthetic
 
 RASTER_TILE_W = 64         # csrc/raster.hip: RASTER_TILE_W
 RASTER_TILE_H = 16         # csrc/raster.hip: RASTER_TILE_H
 RASTER_LIST_CHUNK = 256    # segments of a tile that sit in LDS at a time     (csrc/raster.hip: RASTER_LIST_CHUNK)
 
 
-def _host(a):
-    return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
-
-
 def _edges(a, per_edge, name, device):
     """(n, per_edge) contiguous fp64 tensor from (n, per_edge // 3, 3), (n, per_edge) or an empty list; finite."""
-    if isinstance(a, torch.Tensor):
-        t = a.detach().to(torch.float64)
-    else:
-        t = torch.as_tensor(np.asarray(a, dtype=np.float64))
+    t = _inputs.to_device(a, "cpu")                # numpy and lists are checked on the host and go to ``device`` last
     if t.numel() == 0:
         t = t.reshape(0, per_edge)
     if t.dim() == 3 and tuple(t.shape[1:]) == (per_edge // 3, 3):
@@ -47,32 +37,31 @@ def _edges(a, per_edge, name, device):
     return (t if isinstance(a, torch.Tensor) else t.to(device)).contiguous()
 
 
-def _cameras(intrinsics_list, camtoworld_list):
-    """intr (F, 4) = fx, fy, cx, cy; R (F, 3, 3), T (F, 3) with [R | T] = np.linalg.inv(camtoworld)[:3]: fp64 numpy, as dtu_eval._cameras."""
+def cameras(intrinsics_list, camtoworld_list):
+    """intr (F, 4) = fx, fy, cx, cy; R (F, 3, 3), T (F, 3): fp64 numpy, each view checked and then taken through ``_inputs.world_to_camera``."""
     F = len(intrinsics_list)
     if F == 0 or len(camtoworld_list) != F:
         raise ValueError(f"edge_raster: {F} intrinsics, {len(camtoworld_list)} poses (one of each per view, at least one view)")
     if F > _lib.RASTER_MAX_FRAMES:
         raise ValueError(f"edge_raster: {F} views, at most {_lib.RASTER_MAX_FRAMES} per call")
-    intr = np.empty((F, 4), dtype=np.float64)
-    w2c = np.empty((F, 4, 4), dtype=np.float64)
+    intr, R, T = np.empty((F, 4), dtype=np.float64), np.empty((F, 3, 3), dtype=np.float64), np.empty((F, 3), dtype=np.float64)
     for i, (k, c) in enumerate(zip(intrinsics_list, camtoworld_list)):
-        k, c = _host(k), _host(c)
+        k, c = _inputs.host64(k), _inputs.host64(c)
         if k.shape not in ((3, 3), (4, 4)) or c.shape != (4, 4):
             raise ValueError(f"edge_raster: view {i}: intrinsics must be (3, 3) or (4, 4) and camtoworld (4, 4), got {k.shape} and {c.shape}")
         if not (np.isfinite(k).all() and np.isfinite(c).all()):
             raise ValueError(f"edge_raster: view {i}: non-finite camera")
-        k = k[:3, :3]
-        if k[0, 1] != 0 or k[1, 0] != 0 or tuple(k[2]) != (0.0, 0.0, 1.0):
+        K = k[:3, :3]                                   # what world_to_camera returns as K
+        if K[0, 1] != 0 or K[1, 0] != 0 or tuple(K[2]) != (0.0, 0.0, 1.0):
             raise ValueError(f"edge_raster: view {i}: intrinsics must have no skew and the last row (0, 0, 1)")
-        intr[i] = k[0, 0], k[1, 1], k[0, 2], k[1, 2]
-        try:
-            w2c[i] = np.linalg.inv(c)
+        intr[i] = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        try:                                            # one view at a time, so that the error names the view
+            _, R[i:i + 1], T[i:i + 1] = _inputs.world_to_camera([k], [c])
         except np.linalg.LinAlgError as e:
             raise ValueError(f"edge_raster: view {i}: camtoworld has no inverse") from e
-    if not np.isfinite(w2c).all():
+    if not (np.isfinite(R).all() and np.isfinite(T).all()):
         raise ValueError("edge_raster: a camtoworld matrix has no finite inverse")
-    return intr, np.ascontiguousarray(w2c[:, :3, :3]), np.ascontiguousarray(w2c[:, :3, 3])
+    return intr, R, T
 
 
 def workspace_bytes(n_lines, n_curves, curve_segments, F):
@@ -105,10 +94,10 @@ def rasterize_edges(lines_end_pts, curves_ctl_pts, intrinsics_list, camtoworld_l
     L, Cn = int(lines.shape[0]), int(curves.shape[0])
     if L + Cn * curve_segments > _lib.RASTER_MAX_SEGMENTS:
         raise ValueError(f"edge_raster: {L} lines and {Cn} curves of {curve_segments} segments are more than {_lib.RASTER_MAX_SEGMENTS} segments")
-    intr, R, T = _cameras(intrinsics_list, camtoworld_list)
+    intr, R, T = cameras(intrinsics_list, camtoworld_list)
     F = len(intr)
     if weights is not None:
-        wt = weights.detach().to(torch.float64) if isinstance(weights, torch.Tensor) else torch.as_tensor(np.asarray(weights, dtype=np.float64))
+        wt = _inputs.to_device(weights, "cpu")          # as _edges: checked where it is
         if wt.dim() != 1 or wt.shape[0] != L + Cn:
             raise ValueError(f"edge_raster: weights must be ({L + Cn},) - one per line, then one per curve -, got {tuple(wt.shape)}")
         if not bool(((wt >= 0) & (wt <= 1)).all()):
@@ -133,14 +122,14 @@ def rasterize_edges(lines_end_pts, curves_ctl_pts, intrinsics_list, camtoworld_l
     return (out, ids) if return_ids else out
 
 
-def _meta_cameras(meta_or_sampler):
+def meta_cameras(meta_or_sampler):
     """(intrinsics (F, 4, 4), camtoworld (F, 4, 4), h, w) of a parsed ``meta_data.json`` or of a ``DeviceRaySampler``."""
     if isinstance(meta_or_sampler, dict):
         frames = meta_or_sampler["frames"]
         return ([np.asarray(f["intrinsics"], dtype=np.float64) for f in frames], [np.asarray(f["camtoworld"], dtype=np.float64)[:4, :4] for f in frames],
                 int(meta_or_sampler["height"]), int(meta_or_sampler["width"]))
     s = meta_or_sampler
-    return list(_host(s.intrinsics_all)), list(_host(s.pose_all)), int(s.H), int(s.W)
+    return list(_inputs.host64(s.intrinsics_all)), list(_inputs.host64(s.pose_all)), int(s.H), int(s.W)
 
 
 def rasterize_parametric_edges(json_path_or_dict, meta_or_sampler, half_width=1.5, weights=None, curve_segments=32, z_near=1e-3,
@@ -148,11 +137,8 @@ def rasterize_parametric_edges(json_path_or_dict, meta_or_sampler, half_width=1.
     """What ``get_parametric_edge`` writes (a ``parametric_edges.json`` path or its dict: ``lines_end_pts`` (L, 6), ``curves_ctl_pts``
     (C, 12)) drawn into the views it was reconstructed from: the cameras of a parsed ``meta_data.json`` dict, or of the
     ``DeviceRaySampler`` built from one.  -> what ``rasterize_edges`` returns, at the dataset's height and width."""
-    d = json_path_or_dict
-    if isinstance(d, (str, os.PathLike)):
-        with open(d, "r") as f:
-            d = json.load(f)
-    intrinsics, poses, h, w = _meta_cameras(meta_or_sampler)
+    d = _inputs.load_edge_dict(json_path_or_dict)
+    intrinsics, poses, h, w = meta_cameras(meta_or_sampler)
     return rasterize_edges(d["lines_end_pts"], d["curves_ctl_pts"], intrinsics, poses, h, w, half_width=half_width, weights=weights,
                            curve_segments=curve_segments, z_near=z_near, return_ids=return_ids, device=device)
 
@@ -181,6 +167,6 @@ def make_parametric_scene(lines, curves, n_images=16, H=200, W=200, radius=3.0, 
     [0, 1] -, the maps rasterised on the device.  For ``synthetic.wireframe_segments()`` and no curves both are make_wireframe_scene's,
     bit for bit."""
     meta = synthetic.ring_cameras(n_images, H, W, radius, fov_deg)
-    intrinsics, poses, h, w = _meta_cameras(meta)
+    intrinsics, poses, h, w = meta_cameras(meta)
     maps = rasterize_edges(lines, curves, intrinsics, poses, h, w, half_width=half_width, curve_segments=curve_segments, device=device)
     return meta, to_dataset_edges(maps).cpu().numpy()

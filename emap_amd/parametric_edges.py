@@ -18,14 +18,13 @@ A and B already carry the derivative's factors 3 and 2 - it normalises ``9 t^2 a
 ``3 t^2 a3 + 2 t a2 + a1``.  The two agree at t = 0 only; on the recorded fixture they are up to more than 90 degrees apart.  They are
 reproduced because this module mirrors the reference's outputs; ``sample_edges(..., tangents=True)`` also returns the true unit tangents.
 """
-import json
 import math
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
-from . import _lib, edge_metrics
+from . import _inputs, _lib, edge_metrics
 
 MAX_NUM_SAMPLES = 1024     # sub-intervals of the Simpson rule (csrc/parametric.hip: PE_MAX_SAMPLES)
 
@@ -41,13 +40,6 @@ class EdgeSamples(NamedTuple):
     tangents: Optional[torch.Tensor] = None     # (n, 3) fp64, device: unit tangents (NaN where the derivative is zero); with tangents=True
 
 
-def _device_fp64(a, shape, device):
-    """fp64 contiguous tensor of ``shape``: a tensor stays on its device - ``device`` is not consulted, as in ``edge_metrics`` -, anything
-    else (the json's nested lists, numpy) goes to ``device``."""
-    t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64)).to(device)
-    return t.to(torch.float64).reshape(shape).contiguous()
-
-
 def sample_edges(curves_ctl_pts, lines_end_pts, sample_resolution=0.005, num_samples=100, device="cuda", tangents=False):
     """Sample C cubic Beziers (C, 4, 3) and L segments (L, 2, 3): per edge ``int(length // sample_resolution)`` points at
     ``t = linspace(0, 1, num)`` with the reference's direction vectors (not tangents on curves: module docstring), curves first; with
@@ -56,7 +48,7 @@ def sample_edges(curves_ctl_pts, lines_end_pts, sample_resolution=0.005, num_sam
     resolution of ``bezier_curve_length`` (100 everywhere it is called).  One launch for lengths and counts, ``torch.cumsum``, ONE host
     synchronisation (the totals), one launch that fills the points.  Raises ``ValueError`` when a length is not finite - the reference's
     ``int(nan)`` raises there too - or when ``length / sample_resolution`` is 9e18 or more.  Bit-identical from run to run."""
-    curves, lines = _device_fp64(curves_ctl_pts, (-1, 4, 3), device), _device_fp64(lines_end_pts, (-1, 2, 3), device)
+    curves, lines = _inputs.to_device(curves_ctl_pts, device).reshape(-1, 4, 3), _inputs.to_device(lines_end_pts, device).reshape(-1, 2, 3)
     if not (math.isfinite(sample_resolution) and sample_resolution > 0):
         raise ValueError(f"sample_edges: sample_resolution must be finite and > 0 (got {sample_resolution!r})")
     if not 1 <= int(num_samples) <= MAX_NUM_SAMPLES:
@@ -112,13 +104,6 @@ def bezier_curve_length(control_points, num_samples):
     return float(lengths[0])
 
 
-def _load_edge_dict(json_path_or_dict):
-    if isinstance(json_path_or_dict, dict):
-        return json_path_or_dict
-    with open(json_path_or_dict, "r") as f:
-        return json.load(f)
-
-
 def get_pred_points_and_directions(json_path_or_dict, sample_resolution=0.005):
     """Mirror of ``get_pred_points_and_directions`` (eval_util.py:300-415): ``(all_curve_points (nc, 3), all_line_points (nl, 3),
     all_curve_directions (nc, 3), all_line_directions (nl, 3))`` as fp64 numpy arrays.  Differences: a dict is accepted in place of the
@@ -126,7 +111,7 @@ def get_pred_points_and_directions(json_path_or_dict, sample_resolution=0.005):
     (here the reference forms ``(1 - t) p0 + t p1``: one rounding apart).  The curve directions are the reference's, which are NOT the
     curves' tangents (module docstring): on a curve whose last two control points coincide the "direction" at t = 1 is ``6 (P0 - P3)``
     normalised, against the direction of travel, where the tangent is undefined.  ``sample_edges(..., tangents=True)`` has the tangents."""
-    d = _load_edge_dict(json_path_or_dict)
+    d = _inputs.load_edge_dict(json_path_or_dict)
     s = sample_edges(d["curves_ctl_pts"], d["lines_end_pts"], sample_resolution)
     k = s.n_curve_points
     p, v = s.points.cpu().numpy(), s.directions.cpu().numpy()
@@ -173,15 +158,11 @@ def edge_frame_visibility(all_curve_points, all_line_points, edges, intrinsics_l
     """The (edge, frame) table behind ``compute_visibility``: ``(visible (E, F) bool, means (E, F) fp64, n_valid (E, F) int64)`` on the
     device of ``edges``.  ``means`` is the mean of the edge map over the edge's points whose rounded pixel lies in the image (NaN when
     there is none)."""
-    if isinstance(edges, torch.Tensor):
-        maps = edges
-    else:
-        maps = torch.as_tensor(np.asarray(edges))
+    maps = edges if isinstance(edges, torch.Tensor) else torch.as_tensor(np.asarray(edges))       # where and as they are: no copy, no cast
     if maps.dim() == 4:
-        maps = maps[..., 0]
+        maps = maps[..., :1]                                              # the reference reads channel 0 of (F, H, W, c)
+    maps = _inputs.edge_maps(maps, h, w, "compute_visibility: edges")
     F = int(maps.shape[0])
-    if maps.dim() != 3 or tuple(maps.shape[1:]) != (int(h), int(w)):
-        raise ValueError(f"compute_visibility: edges must be (F, {h}, {w}) or (F, {h}, {w}, 1), got {tuple(maps.shape)}")
     if len(intrinsics_list) != F or len(camtoworld_list) != F:
         raise ValueError(f"compute_visibility: {F} edge maps, {len(intrinsics_list)} intrinsics, {len(camtoworld_list)} poses")
     dev = maps.device
@@ -189,12 +170,9 @@ def edge_frame_visibility(all_curve_points, all_line_points, edges, intrinsics_l
     if E == 0 or F == 0:
         return (torch.zeros(E, F, dtype=torch.bool, device=dev), torch.full((E, F), float("nan"), dtype=torch.float64, device=dev),
                 torch.zeros(E, F, dtype=torch.int64, device=dev))
-    # K, R, T per frame on the host as the reference forms them (:156-159); F small matrices
-    Ks = np.stack([np.asarray(k, dtype=np.float64)[:3, :3] for k in intrinsics_list])
-    w2c = np.stack([np.linalg.inv(np.asarray(c, dtype=np.float64)) for c in camtoworld_list])
-    K = torch.as_tensor(Ks).to(dev)
-    R = torch.as_tensor(np.ascontiguousarray(w2c[:, :3, :3])).to(dev)
-    T = torch.as_tensor(np.ascontiguousarray(w2c[:, :3, 3:])).to(dev)
+    # K, R, T per frame on the host as the reference forms them (:156-159); F small matrices, T as (F, 3, 1) for the sum below
+    K, R, T = (torch.as_tensor(a).to(dev) for a in _inputs.world_to_camera(intrinsics_list, camtoworld_list))
+    T = T.unsqueeze(-1)
     X = torch.as_tensor(pts).to(dev)
     eid_t = torch.as_tensor(eid).to(dev)
     x = torch.matmul(K, torch.matmul(R, X.T.unsqueeze(0)) + T)            # (F, 3, N): K @ (R @ X + T), fp64
@@ -256,6 +234,6 @@ def evaluate_parametric_edges(json_path_or_dict, gt_points, thresholds=(0.005, 0
     reference's loaders do, and run ``edge_metrics.evaluate_edges`` - the ``process_scan`` sequence of src/eval/eval_ABC.py:63-89 with its
     prediction taken from the fitted edges.  The sampled points never leave the device.  ``device`` is where the edge set and a numpy
     ``gt_points`` go; a ``gt_points`` tensor is used where it is and must be on that device.  -> the metrics dict."""
-    d = _load_edge_dict(json_path_or_dict)
+    d = _inputs.load_edge_dict(json_path_or_dict)
     s = sample_edges(d["curves_ctl_pts"], d["lines_end_pts"], sample_resolution, device=device)
     return edge_metrics.evaluate_edges(s.points.float(), gt_points, thresholds=thresholds, downsample=downsample, device=device)

@@ -86,9 +86,9 @@ def main():
     say(f"{'shape':27s} {'segments':>8s} {'ids':>3s} {'call ms (min .. max)':>30s} {'no segment ms':>13s} {'one tile ms':>11s} {'floor ms':>9s} {'x floor':>8s} "
         f"{'Gpixel/s':>9s} exact")
     for name, m, lines, curves in shapes:
-        intrinsics, poses, h, w = ER._meta_cameras(m)
+        intrinsics, poses, h, w = ER.meta_cameras(m)
         F = len(poses)
-        intr, Rm, T = (torch.as_tensor(x).to(dev) for x in ER._cameras(intrinsics, poses))
+        intr, Rm, T = (torch.as_tensor(x).to(dev) for x in ER.cameras(intrinsics, poses))
         l, c = torch.as_tensor(lines).to(dev), torch.as_tensor(curves).to(dev)
         L, Cn, n = len(lines), len(curves), 32
         S = L + Cn * n

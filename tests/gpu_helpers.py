@@ -38,6 +38,19 @@ def rel_p999(a, b, floor=1e-6):
     return float(torch.quantile(e, 0.999)) if e.numel() > 1 else float(e.max())
 
 
+# ---------------------------------------------------------------------------------------- guard-band coverage of a header
+def assert_covered_or_excluded(symbols, covered, excluded, namespace):
+    """Every entry point of the binding table `symbols` is in exactly one of a test module's two tables: `covered` - it returns an rc and
+    names guard-band cases that exist in `namespace` -, or `excluded` as "host-only" - no parameter of it is a device pointer."""
+    for name in symbols:
+        assert (name in covered) != (name in excluded), name
+    assert not (set(covered) | set(excluded)) - set(symbols)
+    for name, cases in covered.items():
+        assert symbols[name][0] is _lib._RC and cases and all(c in namespace for c in cases), name
+    for name, reason in excluded.items():
+        assert reason == "host-only" and _lib._P not in symbols[name][1], name
+
+
 # ---------------------------------------------------------------------------------------- networks and renderer of the goldens
 def mk(name, precision="f16x3", scale=1.0):
     kw, state = net_state(name)

@@ -1,5 +1,5 @@
 """CPU tests of the DTU evaluation (emap_amd.dtu_eval, csrc/visibility.hip, include/emap_eval_hip.h): the numpy mirror of the kernel's
-semantics against the golden counts recorded from the reference, the second header against its binding table and the library's exports,
+semantics against the golden counts recorded from the reference, the second header's dtype codes (the header itself: tests/test_headers_cpu.py),
 every host-side argument check - which runs before any HIP call -, and the parts of the module that need no GPU."""
 import ctypes as C
 import inspect
@@ -14,19 +14,15 @@ from conftest import ROOT
 import emap_amd
 from emap_amd import _lib, dtu_eval
 import dtu_eval_ref as R
+from host_checks import assert_host_check_fails
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g23_dtu_eval.npz")
-HEADER = os.path.join(ROOT, "include", "emap_eval_hip.h")
 VIEWS = ("a", "b")
 
 
 @pytest.fixture(scope="module")
 def g():
     return dict(np.load(GOLDEN))
-
-
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 # ------------------------------------------------------------------------------------------------ the mirror and the golden file
@@ -68,42 +64,12 @@ def test_mirror_on_the_hand_made_exact_cases(h, w):
     assert 51 / 255.0 == R.EXACT_THRESHOLD
 
 
-# ------------------------------------------------------------------------------------------------ header, table, library
-def test_header_table_and_exports_agree():
-    code = _header_code()
-    declared = sorted(set(re.findall(r"\b(emap_[a-z_0-9]+)\s*\(", code)))
-    assert declared == sorted(_lib.EVAL_SYMBOLS) == ["emap_eval_abi_version", "emap_point_visibility"]
-    assert not set(_lib.EVAL_SYMBOLS) & set(_lib.SYMBOLS)                       # the main table is the main header's alone
-    assert "struct" not in code                                                 # no layout to compare
-    raw = C.CDLL(_lib.LIB_PATH)
-    L = _lib.eval_lib()
-    assert L is _lib.lib()
-    for name, (res, args) in _lib.EVAL_SYMBOLS.items():
-        assert hasattr(raw, name), f"libemap_hip.so does not export {name}"
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", code).group(1).strip()
-        n_params = 0 if proto == "void" else len(proto.split(","))
-        assert n_params == len(args) == len(getattr(L, name).argtypes or []), name
-    # the parameter types of the one call, in order
-    proto = re.search(r"emap_point_visibility\s*\(([^)]*)\)", code).group(1)
-    kinds = [("ptr" if "*" in p else p.split()[-2]) for p in proto.split(",")]
-    ctypes_kind = {_lib._P: "ptr", C.c_int: "int", C.c_int64: "int64_t", C.c_double: "double"}
-    assert kinds == [ctypes_kind[t] for t in _lib.EVAL_SYMBOLS["emap_point_visibility"][1]]
-
-
-def test_versions_and_the_two_views():
-    code = _header_code()
-    assert "#define EMAP_EVAL_ABI_VERSION 1" in code and _lib.EVAL_ABI_VERSION == 1 and _lib.eval_lib().emap_eval_abi_version() == 1
-    assert _lib.lib().emap_abi_version() == _lib.ABI_VERSION == 12
-    A = _lib.eval_api()
-    assert A is _lib.eval_api() and sorted(vars(A)) == ["point_visibility"]
-    assert not hasattr(_lib.api(), "point_visibility") and "emap_point_visibility" not in _lib.SYMBOLS
-    raw = _lib.eval_lib().emap_point_visibility
-    assert raw.restype is C.c_int and raw.argtypes == _lib.EVAL_SYMBOLS["emap_point_visibility"][1] and A.point_visibility is not raw
-    for name, code_no in (("EMAP_EVAL_POINTS_F64", 0), ("EMAP_EVAL_POINTS_F32", 1), ("EMAP_EVAL_MAPS_U8", 0), ("EMAP_EVAL_MAPS_F32", 1),
-                          ("EMAP_EVAL_MAPS_F64", 2)):
-        assert re.search(rf"#define {name} {code_no}\b", code), name
-    assert _lib.EVAL_POINTS_DTYPES == {torch.float64: 0, torch.float32: 1}
-    assert _lib.EVAL_MAPS_DTYPES == {torch.uint8: 0, torch.float32: 1, torch.float64: 2}
+# ------------------------------------------------------------------------------------------------ the header's dtype codes
+def test_dtype_codes():
+    assert _lib.EVAL_POINTS_DTYPES == {torch.float64: 0, torch.float32: 1}      # EMAP_EVAL_POINTS_*, EMAP_EVAL_MAPS_*: the #defines equal these
+    assert _lib.EVAL_MAPS_DTYPES == {torch.uint8: 0, torch.float32: 1, torch.float64: 2}            # through _lib.HEADERS (test_headers_cpu)
+    assert set(_lib.HEADERS["eval"]["constants"]) == {"EMAP_EVAL_POINTS_F64", "EMAP_EVAL_POINTS_F32", "EMAP_EVAL_MAPS_U8", "EMAP_EVAL_MAPS_F32",
+                                                      "EMAP_EVAL_MAPS_F64"}
 
 
 P = C.c_void_p(256)          # a non-null pointer no host check dereferences
@@ -116,13 +82,7 @@ BAD = [("n", -1, "n"), ("F", 0, "F"), ("F", -2, "F"), ("h", 0, "h"), ("w", 0, "w
 
 @pytest.mark.parametrize("field,value,word", BAD)
 def test_every_host_check_returns_invalid_and_names_the_entry_point(field, value, word):
-    L = _lib.eval_lib()
-    args = dict(GOOD, **{field: value})
-    assert L.emap_point_visibility(*args.values()) == -1
-    msg = L.emap_last_error().decode()
-    assert msg.startswith("point_visibility:") and word in msg, msg
-    with pytest.raises(RuntimeError, match=r"point_visibility failed \(rc=-1\): point_visibility:"):
-        _lib.eval_api().point_visibility(*args.values())
+    assert_host_check_fails(_lib.eval_lib(), _lib.eval_api(), "emap_point_visibility", dict(GOOD, **{field: value}).values(), word)
 
 
 def test_no_points_return_ok_and_launch_nothing():

@@ -1,6 +1,6 @@
 """CPU tests of the edge fitting (emap_amd.edge_fitting, csrc/fitting.hip, include/emap_fit_hip.h): the numpy mirror of every stage
 (tests/edge_fitting_ref.py) against the golden file recorded from the reference, stage by stage, each stage fed the reference's previous
-output; the third header against its binding table and the library's exports; the reference's signatures; the host logic that needs no GPU
+output; the limits and kernel constants the module mirrors (the third header itself: tests/test_headers_cpu.py); the reference's signatures; the host logic that needs no GPU
 (sublist splitting, the voxel down-sample on CPU tensors); and every host-side argument check, which runs before any HIP call."""
 import ctypes as C
 import importlib
@@ -16,10 +16,10 @@ from conftest import ROOT
 import emap_amd
 from emap_amd import _lib
 import edge_fitting_ref as R
+from host_checks import assert_host_check_fails
 
 EF = importlib.import_module("emap_amd.edge_fitting")        # emap_amd.edge_fitting itself is the reference's function of that name
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g24_edge_fitting.npz")
-HEADER = os.path.join(ROOT, "include", "emap_fit_hip.h")
 TAGS = ("a", "b")
 ANGLE, NMS, FIT_DIST, MIN_INLIERS, MAX_LINES, MAX_CURVES = 0.03, 0.95, 10.0, 5, 4, 3
 
@@ -92,40 +92,9 @@ def test_mirror_merges_the_golden_fit(g, tag):
     assert not R.same_partition(mm["line_labels"], np.arange(len(mm["line_labels"])))
 
 
-# ------------------------------------------------------------------------------------------------ header, table, library
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-
-
-NEW = ["emap_fit_abi_version", "emap_fit_beziers", "emap_fit_lines", "emap_fit_link", "emap_fit_merge_endpoints", "emap_fit_merge_lines"]
-
-
-def test_header_table_and_exports_agree_and_the_other_two_abis_are_unchanged():
-    code = _header_code()
-    declared = sorted(set(re.findall(r"\b(emap_[a-z_0-9]+)\s*\(", code)))
-    assert declared == sorted(_lib.FIT_SYMBOLS) == NEW
-    assert not set(_lib.FIT_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.EVAL_SYMBOLS))
-    assert "struct" not in code
-    raw = C.CDLL(_lib.LIB_PATH)
-    L = _lib.fit_lib()
-    assert L is _lib.lib() and L is _lib.eval_lib()
-    kind = {_lib._P: "ptr", C.c_int: "int", C.c_double: "double", C.c_size_t: "size_t"}
-    for name, (res, args) in _lib.FIT_SYMBOLS.items():
-        assert hasattr(raw, name), f"libemap_hip.so does not export {name}"
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", code).group(1).strip()
-        kinds = [] if proto == "void" else [("ptr" if "*" in p else p.split()[-2]) for p in proto.split(",")]
-        assert kinds == [kind[t] for t in args], name
-        assert (res is _lib._RC) == (name != "emap_fit_abi_version")
-    assert "#define EMAP_FIT_ABI_VERSION 1" in code and _lib.FIT_ABI_VERSION == 1 and L.emap_fit_abi_version() == 1
-    A = _lib.fit_api()
-    assert A is _lib.fit_api() and sorted(vars(A)) == sorted(n[5:] for n in NEW if n != "emap_fit_abi_version")
-    assert not hasattr(_lib.api(), "fit_link") and not hasattr(_lib.eval_api(), "fit_link")
-    # the two existing headers, tables and versions
-    assert _lib.ABI_VERSION == 12 and L.emap_abi_version() == 12 and "#define EMAP_ABI_VERSION 12" in open(os.path.join(ROOT, "include", "emap_hip.h")).read()
-    assert _lib.EVAL_ABI_VERSION == 1 and L.emap_eval_abi_version() == 1 and sorted(_lib.EVAL_SYMBOLS) == ["emap_eval_abi_version", "emap_point_visibility"]
-    for name, value in (("EMAP_FIT_MAX_POLYLINE_POINTS", 1024), ("EMAP_FIT_MAX_LINES", 16), ("EMAP_FIT_LINK_LDS_POINTS", 1048576)):
-        assert re.search(rf"#define {name} {value}\b", code), name
-    assert (_lib.FIT_MAX_POLYLINE_POINTS, _lib.FIT_MAX_LINES, _lib.FIT_LINK_LDS_POINTS) == (1024, 16, 1048576)
+# ------------------------------------------------------------------------------------------------ limits, kernel constants, build
+def test_limits_kernel_constants_and_build_membership():
+    assert (_lib.FIT_MAX_POLYLINE_POINTS, _lib.FIT_MAX_LINES, _lib.FIT_LINK_LDS_POINTS) == (1024, 16, 1048576)      # the #defines: test_headers_cpu
     assert EF.MAX_POLYLINE_POINTS == 1024
     build = open(os.path.join(ROOT, "emap_amd", "csrc", "build.sh")).read()
     assert " fitting " in build and "$OUT/fitting.o" in build
@@ -159,13 +128,7 @@ BAD = ([("emap_fit_link", LINK, f, v) for f, v in (
 
 @pytest.mark.parametrize("name,good,field,value", BAD)
 def test_every_host_check_returns_invalid_and_names_the_entry_point(name, good, field, value):
-    L = _lib.fit_lib()
-    args = dict(good, **{field: value})
-    assert getattr(L, name)(*args.values()) == -1
-    msg = L.emap_last_error().decode()
-    assert msg.startswith(name[5:] + ":"), msg
-    with pytest.raises(RuntimeError, match=rf"{name[5:]} failed \(rc=-1\): {name[5:]}:"):
-        getattr(_lib.fit_api(), name[5:])(*args.values())
+    assert_host_check_fails(_lib.fit_lib(), _lib.fit_api(), name, dict(good, **{field: value}).values())
 
 
 def test_nothing_to_do_returns_ok_and_launches_nothing():

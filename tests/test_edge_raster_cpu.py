@@ -1,6 +1,6 @@
 """CPU tests of the edge rasteriser (emap_amd.edge_raster, csrc/raster.hip, include/emap_raster_hip.h): the numpy mirror of the header's
-semantics against the existing host generator (synthetic.make_wireframe_scene) byte for byte, the fourth header against its binding table
-and the library's exports, every host-side argument check - which runs before any HIP call -, and the parts that need no GPU."""
+semantics against the existing host generator (synthetic.make_wireframe_scene) byte for byte, the limits and kernel constants the module
+mirrors (the fourth header itself: tests/test_headers_cpu.py), every host-side argument check - which runs before any HIP call -, and the parts that need no GPU."""
 import ctypes as C
 import inspect
 import os
@@ -14,15 +14,11 @@ from conftest import ROOT
 import emap_amd
 from emap_amd import _lib, edge_raster as ER, synthetic
 import edge_raster_ref as R
+from host_checks import assert_host_check_fails
 
 HEADER = os.path.join(ROOT, "include", "emap_raster_hip.h")
-NEW = ["emap_raster_abi_version", "emap_raster_edges", "emap_raster_workspace_bytes"]
 # (n_images, H, W) -> lit bytes of make_wireframe_scene
 SCENES = {(16, 200, 200): 54724, (4, 64, 64): 3702, (5, 37, 53): 3494}
-
-
-def _header_code():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
 
 
 # ------------------------------------------------------------------------------------------------ the mirror and the generator
@@ -110,44 +106,10 @@ def test_mirror_of_the_shared_scene_hits_every_case():
     assert (box[:, 0] < R.TILE_W).all() and (box[:, 1] < R.TILE_H).all()        # every one of them meets the first tile
 
 
-# ------------------------------------------------------------------------------------------------ header, table, library
-def test_header_table_and_exports_agree():
-    code = _header_code()
-    declared = sorted(set(re.findall(r"\b(emap_[a-z_0-9]+)\s*\(", code)))
-    assert declared == sorted(_lib.RASTER_SYMBOLS) == NEW
-    assert not set(_lib.RASTER_SYMBOLS) & (set(_lib.SYMBOLS) | set(_lib.EVAL_SYMBOLS) | set(_lib.FIT_SYMBOLS))
-    assert "struct" not in code                                                 # no layout to compare
-    raw = C.CDLL(_lib.LIB_PATH)
-    L = _lib.raster_lib()
-    assert L is _lib.lib()
-    ctypes_kind = {_lib._P: "ptr", C.c_int: "int", C.c_double: "double", C.c_size_t: "size_t", C.POINTER(C.c_size_t): "ptr"}
-    for name, (res, args) in _lib.RASTER_SYMBOLS.items():
-        assert hasattr(raw, name), f"libemap_hip.so does not export {name}"
-        proto = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)", code).group(1).strip()
-        params = [] if proto == "void" else proto.split(",")
-        assert len(params) == len(args) == len(getattr(L, name).argtypes or []), name
-        kinds = [("ptr" if "*" in p else p.split()[-2]) for p in params]          # the parameter types, in order
-        assert kinds == [ctypes_kind[t] for t in args], name
-
-
-def test_the_four_versions_and_the_two_views():
-    code = _header_code()
-    assert "#define EMAP_RASTER_ABI_VERSION 1" in code and _lib.RASTER_ABI_VERSION == 1 and _lib.raster_lib().emap_raster_abi_version() == 1
-    assert _lib.lib().emap_abi_version() == _lib.ABI_VERSION == 12
-    assert _lib.eval_lib().emap_eval_abi_version() == _lib.EVAL_ABI_VERSION == 1
-    assert _lib.fit_lib().emap_fit_abi_version() == _lib.FIT_ABI_VERSION == 1
-    A = _lib.raster_api()
-    assert A is _lib.raster_api() and sorted(vars(A)) == ["raster_edges", "raster_workspace_bytes"]
-    assert not hasattr(_lib.api(), "raster_edges") and not hasattr(_lib.eval_api(), "raster_edges") and not hasattr(_lib.fit_api(), "raster_edges")
-    raw = _lib.raster_lib().emap_raster_edges
-    assert raw.restype is C.c_int and raw.argtypes == _lib.RASTER_SYMBOLS["emap_raster_edges"][1] and A.raster_edges is not raw
-    for name, value in (("EMAP_RASTER_MAX_CURVE_SEGMENTS", _lib.RASTER_MAX_CURVE_SEGMENTS), ("EMAP_RASTER_MAX_SEGMENTS", _lib.RASTER_MAX_SEGMENTS),
-                        ("EMAP_RASTER_MAX_FRAMES", _lib.RASTER_MAX_FRAMES), ("EMAP_RASTER_MAX_DIM", _lib.RASTER_MAX_DIM),
-                        ("EMAP_RASTER_ROW_BYTES", _lib.RASTER_ROW_BYTES)):
-        assert re.search(rf"#define {name} {value}\b", code), name
-    assert re.search(r"#define EMAP_RASTER_MAX_HALF_WIDTH 64\.0\b", code) and _lib.RASTER_MAX_HALF_WIDTH == 64.0
-    assert re.search(r"#define EMAP_RASTER_MAX_COORD 1099511627776\.0\b", code) and R.MAX_COORD == 2.0 ** 40
-    assert (_lib.RASTER_MAX_CURVE_SEGMENTS, _lib.RASTER_MAX_SEGMENTS) == (256, 1 << 20)
+# ------------------------------------------------------------------------------------------------ limits, kernel constants, build
+def test_limits_kernel_constants_and_build_membership():
+    assert (_lib.RASTER_MAX_CURVE_SEGMENTS, _lib.RASTER_MAX_SEGMENTS, _lib.RASTER_MAX_HALF_WIDTH) == (256, 1 << 20, 64.0)       # the #defines: test_headers_cpu
+    assert re.search(r"#define EMAP_RASTER_MAX_COORD 1099511627776\.0\b", open(HEADER).read()) and R.MAX_COORD == 2.0 ** 40   # the mirror's, not _lib's
     src = open(os.path.join(ROOT, "emap_amd", "csrc", "raster.hip")).read()
     for name in ("RASTER_TILE_W", "RASTER_TILE_H", "RASTER_LIST_CHUNK"):
         assert re.search(rf"constexpr int {name} = {getattr(ER, name)};", src), name
@@ -193,13 +155,7 @@ BAD = [("n_lines", -1, "negative"), ("n_curves", -2, "negative"), ("curve_segmen
 
 @pytest.mark.parametrize("field,value,word", BAD)
 def test_every_host_check_returns_invalid_and_names_the_entry_point(field, value, word):
-    L = _lib.raster_lib()
-    args = dict(GOOD, **{field: value})
-    assert L.emap_raster_edges(*args.values()) == -1
-    msg = L.emap_last_error().decode()
-    assert msg.startswith("raster_edges:") and word in msg, msg
-    with pytest.raises(RuntimeError, match=r"raster_edges failed \(rc=-1\): raster_edges:"):
-        _lib.raster_api().raster_edges(*args.values())
+    assert_host_check_fails(_lib.raster_lib(), _lib.raster_api(), "emap_raster_edges", dict(GOOD, **{field: value}).values(), word)
 
 
 # ------------------------------------------------------------------------------------------------ the module

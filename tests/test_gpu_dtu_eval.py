@@ -12,6 +12,7 @@ import torch
 from conftest import ROOT
 from emap_amd import _lib, dtu_eval as DE, parametric_edges
 from emap_amd.synthetic import wireframe_segments
+from gpu_helpers import assert_covered_or_excluded
 from guard_bands import Arena
 import dtu_eval_ref as R
 import parametric_edges_ref as PR
@@ -140,13 +141,8 @@ EXCLUDED = {"emap_eval_abi_version": "host-only"}
 
 
 def test_every_entry_point_of_the_second_header_is_covered_or_excluded():
-    for name in _lib.EVAL_SYMBOLS:
-        assert (name in COVERED) != (name in EXCLUDED), name
-    assert not (set(COVERED) | set(EXCLUDED)) - set(_lib.EVAL_SYMBOLS)
-    for name, cases in COVERED.items():
-        assert cases and all(c in globals() for c in cases), name
-    for name, reason in EXCLUDED.items():
-        assert reason == "host-only" and _lib.EVAL_SYMBOLS[name][0] is not _lib._RC and not _lib.EVAL_SYMBOLS[name][1], name
+    assert_covered_or_excluded(_lib.EVAL_SYMBOLS, COVERED, EXCLUDED, globals())
+    assert all(_lib.EVAL_SYMBOLS[name][0] is not _lib._RC and not _lib.EVAL_SYMBOLS[name][1] for name in EXCLUDED)      # no rc, no parameter
 
 
 @pytest.mark.parametrize("n,F,maps_dtype,points_dtype,with_mask", [

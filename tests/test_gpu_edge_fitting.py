@@ -13,6 +13,7 @@ import torch
 from conftest import ROOT
 from emap_amd import _lib, edge_metrics, parametric_edges
 from emap_amd.synthetic import wireframe_segments
+from gpu_helpers import assert_covered_or_excluded
 from guard_bands import Arena
 import edge_fitting_ref as R
 
@@ -330,13 +331,8 @@ EXCLUDED = {"emap_fit_abi_version": "host-only"}
 
 
 def test_every_entry_point_of_the_third_header_is_covered_or_excluded():
-    for name in _lib.FIT_SYMBOLS:
-        assert (name in COVERED) != (name in EXCLUDED), name
-    assert not (set(COVERED) | set(EXCLUDED)) - set(_lib.FIT_SYMBOLS)
-    for name, cases in COVERED.items():
-        assert _lib.FIT_SYMBOLS[name][0] is _lib._RC and cases and all(c in globals() for c in cases), name
-    for name, reason in EXCLUDED.items():
-        assert reason == "host-only" and _lib.FIT_SYMBOLS[name][0] is not _lib._RC and not _lib.FIT_SYMBOLS[name][1], name
+    assert_covered_or_excluded(_lib.FIT_SYMBOLS, COVERED, EXCLUDED, globals())
+    assert all(_lib.FIT_SYMBOLS[name][0] is not _lib._RC and not _lib.FIT_SYMBOLS[name][1] for name in EXCLUDED)        # no rc, no parameter
 
 
 def stream():

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from emap_amd import _lib, edge_raster as ER, synthetic
+from gpu_helpers import assert_covered_or_excluded
 from guard_bands import Arena
 import edge_raster_ref as R
 
@@ -144,13 +145,7 @@ EXCLUDED = {"emap_raster_abi_version": "host-only", "emap_raster_workspace_bytes
 
 
 def test_every_entry_point_of_the_fourth_header_is_covered_or_excluded():
-    for name in _lib.RASTER_SYMBOLS:
-        assert (name in COVERED) != (name in EXCLUDED), name
-    assert not (set(COVERED) | set(EXCLUDED)) - set(_lib.RASTER_SYMBOLS)
-    for name, cases in COVERED.items():
-        assert _lib.RASTER_SYMBOLS[name][0] is _lib._RC and cases and all(c in globals() for c in cases), name
-    for name, reason in EXCLUDED.items():                   # host-only: no parameter is a device pointer
-        assert reason == "host-only" and _lib._P not in _lib.RASTER_SYMBOLS[name][1], name
+    assert_covered_or_excluded(_lib.RASTER_SYMBOLS, COVERED, EXCLUDED, globals())
 
 
 @pytest.mark.parametrize("h,w,F,curve_segments,tiny,with_ids,with_weights", [
