@@ -22,6 +22,9 @@ from . import edge_fitting as fitting  # noqa: F401  (emap_amd.edge_fitting is t
 from .edge_fitting import connect_points, edge_fitting, edge_fit, merge, get_parametric_edge  # noqa: F401
 from . import edge_raster  # noqa: F401
 from .edge_raster import rasterize_edges, rasterize_parametric_edges, to_dataset_edges, make_parametric_scene  # noqa: F401
+from . import edge_score  # noqa: F401
+from .edge_score import (distance_maps, score_edge_maps, score_parametric_edges, score_rendered_views,  # noqa: F401
+                         filter_edges_by_support)
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
            "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
@@ -31,4 +34,5 @@ __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwo
            "compute_visibility", "finish_parametric_edges", "evaluate_parametric_edges",
            "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS",
            "connect_points", "edge_fitting", "edge_fit", "merge", "get_parametric_edge",
-           "edge_raster", "rasterize_edges", "rasterize_parametric_edges", "to_dataset_edges", "make_parametric_scene"]
+           "edge_raster", "rasterize_edges", "rasterize_parametric_edges", "to_dataset_edges", "make_parametric_scene",
+           "edge_score", "distance_maps", "score_edge_maps", "score_parametric_edges", "score_rendered_views", "filter_edges_by_support"]

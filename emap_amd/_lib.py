@@ -1,4 +1,5 @@
-"""ctypes binding of libemap_hip.so: the four headers under include/, each through its own table and pair of views (HEADERS).
+"""ctypes binding of libemap_hip.so: the four headers under include/, each through its own table and pair of views (HEADERS), and the
+fifth, include/emap_score_hip.h, through a record of the same form beside them (SCORE_HEADER).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -239,6 +240,30 @@ HEADERS = {
                               "EMAP_RASTER_MAX_DIM": RASTER_MAX_DIM, "EMAP_RASTER_ROW_BYTES": RASTER_ROW_BYTES}),
 }
 
+# every symbol include/emap_score_hip.h declares: the fifth header.  Its record has the fields of a HEADERS entry and sits beside that
+# registry, not in it: _view() finds it under SCORE_KEY
+SCORE_ABI_VERSION = 1
+SCORE_MAX_DIM = 32768              # EMAP_SCORE_MAX_DIM
+SCORE_MAX_FRAMES = 65535           # EMAP_SCORE_MAX_FRAMES
+SCORE_MAX_THRESHOLDS = 8           # EMAP_SCORE_MAX_THRESHOLDS
+SCORE_NONE = 2147483647            # EMAP_SCORE_NONE
+SCORE_MAPS_DTYPES = {torch.uint8: 0, torch.float32: 1}      # EMAP_SCORE_MAPS_*
+SCORE_WORKSPACE_PIXEL_BYTES = 2    # EMAP_SCORE_WORKSPACE_PIXEL_BYTES
+SCORE_SYMBOLS = {
+    "emap_score_abi_version": (C.c_int, []),
+    "emap_score_workspace_bytes": (_RC, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "emap_score_distance_maps": (_RC, [_P, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _P, _P, C.c_size_t, _P]),
+    "emap_score_stats": (_RC, [_P, C.c_int, C.c_double, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+}
+SCORE_KEY = "score"
+SCORE_HEADER = dict(header="emap_score_hip.h", symbols=SCORE_SYMBOLS, version_fn="emap_score_abi_version", version=SCORE_ABI_VERSION,
+                    mismatch="libemap_hip.so scoring ABI version mismatch (include/emap_score_hip.h)",
+                    constants={"EMAP_SCORE_MAX_DIM": SCORE_MAX_DIM, "EMAP_SCORE_MAX_FRAMES": SCORE_MAX_FRAMES,
+                               "EMAP_SCORE_MAX_THRESHOLDS": SCORE_MAX_THRESHOLDS, "EMAP_SCORE_NONE": SCORE_NONE,
+                               "EMAP_SCORE_MAPS_U8": SCORE_MAPS_DTYPES[torch.uint8], "EMAP_SCORE_MAPS_F32": SCORE_MAPS_DTYPES[torch.float32],
+                               "EMAP_SCORE_WORKSPACE_PIXEL_BYTES": SCORE_WORKSPACE_PIXEL_BYTES})
+_MORE_HEADERS = {SCORE_KEY: SCORE_HEADER}      # records _view() knows beside HEADERS
+
 _lib = None         # the loaded library; setting it to None makes the next call load it again (__graft_entry__.verify_library)
 _views = {}         # header key -> (the library its symbols were bound on, its checked view)
 
@@ -291,12 +316,12 @@ def _bind(l, symbols):
 
 
 def _view(key):
-    """(raw, checked) views of the header HEADERS[key]: the library with the header's symbols bound, and one entry per rc-returning symbol.
+    """(raw, checked) views of the header HEADERS[key] (or the record beside it): the library with the header's symbols bound, and one entry per rc-returning symbol.
     The main header's first use loads the library; a header is bound and its version checked on first use, and again after a reload."""
     global _lib
     l = _view("main")[0] if key != "main" else _lib if _lib is not None else _load()
     if key not in _views or _views[key][0] is not l:
-        h = HEADERS[key]
+        h = HEADERS[key] if key in HEADERS else _MORE_HEADERS[key]
         a = _bind(l, h["symbols"])
         if getattr(l, h["version_fn"])() != h["version"]:
             raise EmapLibraryError(h["mismatch"])
@@ -338,6 +363,14 @@ def raster_lib():         # lib() with the symbols of include/emap_raster_hip.h 
 
 def raster_api():         # the checked view of raster_lib(): one entry per rc-returning symbol of RASTER_SYMBOLS, named without emap_; as api()
     return _view("raster")[1]
+
+
+def score_lib():         # lib() with the symbols of include/emap_score_hip.h bound as well (SCORE_SYMBOLS): the raw view of the fifth header
+    return _view(SCORE_KEY)[0]
+
+
+def score_api():         # the checked view of score_lib(): one entry per rc-returning symbol of SCORE_SYMBOLS, named without emap_; as api()
+    return _view(SCORE_KEY)[1]
 
 
 def size_of(query: str, *args) -> int:

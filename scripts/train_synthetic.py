@@ -34,7 +34,12 @@ and `parametric_edges.evaluate_parametric_edges` of the fitted edges against the
 Beziers, a corner arc and an open S), its edge maps drawn on the device by `emap_amd.edge_raster.make_parametric_scene` in the same ring of
 cameras.  The ground truth of `--eval` and `--fit` is then `parametric_edges.sample_edges` of the scene's own lines and curves (every
 5 mm), the JSON line says "scene": "curved" with the numbers of ground-truth lines and curves, and "parametric_edges" carries how many
-curves the fit recovered.  Without `--scene` the run and its output are unchanged."""
+curves the fit recovered.  Without `--scene` the run and its output are unchanged.
+
+`--score2d` (with `--fit`) scores the fitted edges in image space, the score that needs no 3D ground truth:
+`emap_amd.score_parametric_edges` draws them into the scene's views and compares them with the scene's own edge maps - pixel precision /
+recall / F at 1, 2 and 4 pixels, chamfer in pixels, and per fitted edge the share of its pixels the maps support -, added to
+"parametric_edges" as "score2d".  Without `--score2d` the output is unchanged."""
 import argparse
 import json
 import math
@@ -70,6 +75,7 @@ def main():
     ap.add_argument("--fit", action="store_true", help="fit parametric edges to the extracted point cloud (get_parametric_edge) and add their metrics to the JSON line")
     ap.add_argument("--scene", choices=("wireframe", "curved"), default="wireframe",
                     help="curved: synthetic.curved_wireframe (lines and cubic Beziers), rasterised on the device")
+    ap.add_argument("--score2d", action="store_true", help="with --fit: score the fitted edges against the scene's edge maps (score_parametric_edges)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -199,6 +205,10 @@ def main():
             fit_eval.update(n_lines=len(fitted["lines_end_pts"]), n_curves=len(fitted["curves_ctl_pts"]))
             if fit_eval["n_lines"] + fit_eval["n_curves"]:
                 fit_eval.update(parametric_edges.evaluate_parametric_edges(fitted, gt, device=dev))
+                if a.score2d:          # the same edges against the views they came from: the sampler holds the maps on the device
+                    s2 = emap_amd.score_parametric_edges(fitted, sampler)
+                    fit_eval["score2d"] = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in s2.items() if k != "per_frame"}
+                    print("score2d: " + ", ".join(f"{k} {v:.4f}" for k, v in s2.items() if isinstance(v, float)), file=sys.stderr)
         edge_eval["parametric_edges"] = fit_eval
     scene = {"scene": "curved", "gt_lines": len(gt_lines), "gt_curves": len(gt_curves)} if a.scene == "curved" else {}
     print(json.dumps({
