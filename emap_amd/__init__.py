@@ -25,6 +25,9 @@ from .edge_raster import rasterize_edges, rasterize_parametric_edges, to_dataset
 from . import edge_score  # noqa: F401
 from .edge_score import (distance_maps, score_edge_maps, score_parametric_edges, score_rendered_views,  # noqa: F401
                          filter_edges_by_support)
+from . import edge_field  # noqa: F401
+from .edge_field import (edge_segments, polyline_segments, point_edge_distances, edge_udf, evaluate_udf,  # noqa: F401
+                         evaluate_points_on_edges)
 
 __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwork", "UDFRendererBlending",
            "sample_pdf", "get_embedder", "Embedder", "EdgeLoss", "DeviceRaySampler", "TrainSchedule", "TrainMonitor",
@@ -35,4 +38,5 @@ __all__ = ["UDFNetwork", "SingleVarianceNetwork", "BetaNetwork", "RenderingNetwo
            "dtu_eval", "point_visibility_counts", "compute_point_visibility", "gt_edge_points", "evaluate_dtu", "DTU_SCANS",
            "connect_points", "edge_fitting", "edge_fit", "merge", "get_parametric_edge",
            "edge_raster", "rasterize_edges", "rasterize_parametric_edges", "to_dataset_edges", "make_parametric_scene",
-           "edge_score", "distance_maps", "score_edge_maps", "score_parametric_edges", "score_rendered_views", "filter_edges_by_support"]
+           "edge_score", "distance_maps", "score_edge_maps", "score_parametric_edges", "score_rendered_views", "filter_edges_by_support",
+           "edge_field", "edge_segments", "polyline_segments", "point_edge_distances", "edge_udf", "evaluate_udf", "evaluate_points_on_edges"]

@@ -1,5 +1,6 @@
 """ctypes binding of libemap_hip.so: the four headers under include/, each through its own table and pair of views (HEADERS), and the
-fifth, include/emap_score_hip.h, through a record of the same form beside them (SCORE_HEADER).
+fifth and the sixth, include/emap_score_hip.h and include/emap_field_hip.h, through records of the same form beside them (SCORE_HEADER,
+FIELD_HEADER).
 
 The library is built in-tree by ``__graft_entry__.build()`` (``emap_amd/csrc/build.sh``).
 There is no CPU fallback: if the library is missing, or a call is made without a GPU, the error is
@@ -262,7 +263,27 @@ SCORE_HEADER = dict(header="emap_score_hip.h", symbols=SCORE_SYMBOLS, version_fn
                                "EMAP_SCORE_MAX_THRESHOLDS": SCORE_MAX_THRESHOLDS, "EMAP_SCORE_NONE": SCORE_NONE,
                                "EMAP_SCORE_MAPS_U8": SCORE_MAPS_DTYPES[torch.uint8], "EMAP_SCORE_MAPS_F32": SCORE_MAPS_DTYPES[torch.float32],
                                "EMAP_SCORE_WORKSPACE_PIXEL_BYTES": SCORE_WORKSPACE_PIXEL_BYTES})
-_MORE_HEADERS = {SCORE_KEY: SCORE_HEADER}      # records _view() knows beside HEADERS
+# every symbol include/emap_field_hip.h declares: the sixth header, a record of the same form
+FIELD_ABI_VERSION = 1
+FIELD_MAX_CURVE_SEGMENTS = 256     # EMAP_FIELD_MAX_CURVE_SEGMENTS
+FIELD_MAX_SEGMENTS = 1 << 20       # EMAP_FIELD_MAX_SEGMENTS
+FIELD_MAX_POINTS = 2147483647      # EMAP_FIELD_MAX_POINTS
+FIELD_MAX_THRESHOLDS = 8           # EMAP_FIELD_MAX_THRESHOLDS
+FIELD_POINTS_DTYPES = {torch.float64: 0, torch.float32: 1}      # EMAP_FIELD_POINTS_*
+FIELD_SYMBOLS = {
+    "emap_field_abi_version": (C.c_int, []),
+    "emap_field_expand_edges": (_RC, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "emap_field_workspace_bytes": (_RC, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "emap_field_point_distances": (_RC, [_P, C.c_int, C.c_int64, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
+    "emap_field_stats": (_RC, [_P, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int64, _P, _P, _P, _P]),
+}
+FIELD_KEY = "field"
+FIELD_HEADER = dict(header="emap_field_hip.h", symbols=FIELD_SYMBOLS, version_fn="emap_field_abi_version", version=FIELD_ABI_VERSION,
+                    mismatch="libemap_hip.so distance-field ABI version mismatch (include/emap_field_hip.h)",
+                    constants={"EMAP_FIELD_MAX_CURVE_SEGMENTS": FIELD_MAX_CURVE_SEGMENTS, "EMAP_FIELD_MAX_SEGMENTS": FIELD_MAX_SEGMENTS,
+                               "EMAP_FIELD_MAX_POINTS": FIELD_MAX_POINTS, "EMAP_FIELD_MAX_THRESHOLDS": FIELD_MAX_THRESHOLDS,
+                               "EMAP_FIELD_POINTS_F64": FIELD_POINTS_DTYPES[torch.float64], "EMAP_FIELD_POINTS_F32": FIELD_POINTS_DTYPES[torch.float32]})
+_MORE_HEADERS = {SCORE_KEY: SCORE_HEADER, FIELD_KEY: FIELD_HEADER}      # records _view() knows beside HEADERS
 
 _lib = None         # the loaded library; setting it to None makes the next call load it again (__graft_entry__.verify_library)
 _views = {}         # header key -> (the library its symbols were bound on, its checked view)
@@ -371,6 +392,14 @@ def score_lib():         # lib() with the symbols of include/emap_score_hip.h bo
 
 def score_api():         # the checked view of score_lib(): one entry per rc-returning symbol of SCORE_SYMBOLS, named without emap_; as api()
     return _view(SCORE_KEY)[1]
+
+
+def field_lib():         # lib() with the symbols of include/emap_field_hip.h bound as well (FIELD_SYMBOLS): the raw view of the sixth header
+    return _view(FIELD_KEY)[0]
+
+
+def field_api():         # the checked view of field_lib(): one entry per rc-returning symbol of FIELD_SYMBOLS, named without emap_; as api()
+    return _view(FIELD_KEY)[1]
 
 
 def size_of(query: str, *args) -> int:

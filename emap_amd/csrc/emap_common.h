@@ -374,6 +374,8 @@ int launch_sample_rays_train(const EmapRayDataset* ds, const int32_t* train_imag
 int gen_rays_count(const EmapRayDataset* ds, int resolution_level, int64_t* n, int* h, int* w);
 int launch_gen_rays_at(const EmapRayDataset* ds, int img_idx, int resolution_level, int64_t first, int64_t count, float* rays_o, float* rays_d,
                        float* depth_scale, hipStream_t st);
+// metrics.hip: compute units of the current device (what the brute-force searches size their splits by)
+int nn_device_cus();
 // train.hip: the scalar tail of a training step
 int launch_train_stats(const float* edge, const float* true_edge, const float* scalars, int N, float d_scale, float* d_edge, float* stats,
                        hipStream_t st);

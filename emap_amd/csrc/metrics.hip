@@ -184,7 +184,7 @@ __global__ __launch_bounds__(ST_THREADS) void dist_stats_kernel(const float* __r
 
 static size_t nn_workspace_bytes(int64_t n_q) { return ((size_t)n_q * sizeof(unsigned long long) + 255) & ~(size_t)255; }
 
-static int nn_device_cus() {     // of the current device; asked once per device
+int nn_device_cus() {     // of the current device; asked once per device  (field.hip sizes its split with it too)
     static int cus[64] = {0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return 256;

@@ -23,17 +23,18 @@ RASTER_TILE_H = 16         # csrc/raster.hip: RASTER_TILE_H
 RASTER_LIST_CHUNK = 256    # segments of a tile that sit in LDS at a time     (csrc/raster.hip: RASTER_LIST_CHUNK)
 
 
-def _edges(a, per_edge, name, device):
-    """(n, per_edge) contiguous fp64 tensor from (n, per_edge // 3, 3), (n, per_edge) or an empty list; finite."""
+def _edges(a, per_edge, name, device, tag="edge_raster"):
+    """(n, per_edge) contiguous fp64 tensor from (n, per_edge // 3, 3), (n, per_edge) or an empty list; finite.  ``tag`` names the calling
+    module in the error (edge_field takes its edges through here too)."""
     t = _inputs.to_device(a, "cpu")                # numpy and lists are checked on the host and go to ``device`` last
     if t.numel() == 0:
         t = t.reshape(0, per_edge)
     if t.dim() == 3 and tuple(t.shape[1:]) == (per_edge // 3, 3):
         t = t.reshape(-1, per_edge)
     if t.dim() != 2 or t.shape[1] != per_edge:
-        raise ValueError(f"edge_raster: {name} must be (n, {per_edge // 3}, 3) or (n, {per_edge}), got {tuple(a.shape) if hasattr(a, 'shape') else np.shape(a)}")
+        raise ValueError(f"{tag}: {name} must be (n, {per_edge // 3}, 3) or (n, {per_edge}), got {tuple(a.shape) if hasattr(a, 'shape') else np.shape(a)}")
     if not bool(torch.isfinite(t).all()):
-        raise ValueError(f"edge_raster: {name} holds a non-finite value")
+        raise ValueError(f"{tag}: {name} holds a non-finite value")
     return (t if isinstance(a, torch.Tensor) else t.to(device)).contiguous()
 
 

@@ -39,7 +39,14 @@ curves the fit recovered.  Without `--scene` the run and its output are unchange
 `--score2d` (with `--fit`) scores the fitted edges in image space, the score that needs no 3D ground truth:
 `emap_amd.score_parametric_edges` draws them into the scene's views and compares them with the scene's own edge maps - pixel precision /
 recall / F at 1, 2 and 4 pixels, chamfer in pixels, and per fitted edge the share of its pixels the maps support -, added to
-"parametric_edges" as "score2d".  Without `--score2d` the output is unchanged."""
+"parametric_edges" as "score2d".  Without `--score2d` the output is unchanged.
+
+`--eval-field` measures the trained FIELD itself against the exact distance field of the scene's ground-truth edges
+(`emap_amd.evaluate_udf`, 128^3 lattice, curves as 256 chords): the mean, root-mean-square and largest |udf - d| and the bias over the
+lattice points within 5 cm of the wire frame, and what the extraction threshold 0.04 keeps against what the exact field would keep (IoU),
+added to the JSON line as "field_error" and printed.  With `--eval` the extracted points are also scored against the edges themselves
+(`emap_amd.evaluate_points_on_edges`): the per-edge table - points assigned, precision, samples, recall at 5 mm - is printed and added
+as "points_on_edges".  Without `--eval-field` the output is unchanged."""
 import argparse
 import json
 import math
@@ -76,6 +83,8 @@ def main():
     ap.add_argument("--scene", choices=("wireframe", "curved"), default="wireframe",
                     help="curved: synthetic.curved_wireframe (lines and cubic Beziers), rasterised on the device")
     ap.add_argument("--score2d", action="store_true", help="with --fit: score the fitted edges against the scene's edge maps (score_parametric_edges)")
+    ap.add_argument("--eval-field", action="store_true", help="compare the trained UDF with the exact distance field of the ground-truth edges (evaluate_udf); "
+                                                              "with --eval also score the extracted points per edge (evaluate_points_on_edges)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -193,6 +202,19 @@ def main():
         points, _ = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=128, udf_threshold=0.04, is_pointshift=False, device=dev)
         gt = gt_points()
         edge_eval = {"edge_metrics": {"n_extracted": int(points.shape[0]), **(edge_metrics.evaluate_edges(points, gt, device=dev) if len(points) else {})}}
+    if a.eval_field:               # the field itself against the exact distance field of the ground-truth edges
+        f_lines, f_curves = (gt_lines, gt_curves) if a.scene == "curved" else (synthetic.wireframe_segments().reshape(-1, 6), np.zeros((0, 12)))
+        fe = emap_amd.evaluate_udf(net, f_lines, f_curves, N=128, band=0.05, udf_threshold=0.04, device=dev)
+        edge_eval["field_error"] = fe
+        print("field error: " + ", ".join(f"{k} {v:.5f}" if isinstance(v, float) else f"{k} {v}" for k, v in fe.items()), file=sys.stderr)
+        if a.eval and len(points):
+            pe = emap_amd.evaluate_points_on_edges(points, f_lines, f_curves, device=dev)
+            edge_eval["points_on_edges"] = {k: ({kk: vv.tolist() for kk, vv in v.items()} if k == "per_edge" else v) for k, v in pe.items()}
+            print("edge  type   points  precision_0.005  samples  recall_0.005", file=sys.stderr)
+            for e in range(len(f_lines) + len(f_curves)):
+                row = pe["per_edge"]
+                print(f"{e:4d}  {'line ' if e < len(f_lines) else 'curve'} {row['n_pred'][e]:7d}  {row['precision_0.005'][e]:15.4f}  {row['n_gt'][e]:7d}  "
+                      f"{row['recall_0.005'][e]:12.4f}", file=sys.stderr)
     if a.fit:                      # train -> extract -> fit -> evaluate: the metrics of the fitted edges
         n_mc = 128
         points, line_directions = extraction.get_pointcloud_from_udf(net.udf, net.gradient, N_MC=n_mc, udf_threshold=0.04, is_pointshift=False,
