@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, const float* g, flo
     const float bc1 = s_bc[0], bc2s = s_bc[1];
     // the geometry range in float4 words when the four buffers are 16-byte aligned (the flat buffers are): a quarter of the threads and memory
     // instructions of the element-wise form (11 -> 7 us at 463 k parameters); the rest - the last < 4 geometry elements and the scalar tail with
-    // its mask and per-element step counts - element by element.  Same arithmetic per element either way.
+    // its mask and per-element step counts - element by element.  Same arithmetic per element either way (held bit for bit on unaligned
+    // buffers by tests/test_gpu_train_tail.py).
     typedef float f4 __attribute__((ext_vector_type(4)));
     const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15) == 0;
     const long long n4 = al ? (n_geo >> 2) : 0;
@@ -267,10 +268,11 @@ int launch_adam(float* p, const float* g, float* m, float* v, float* step, int64
         set_error("adam_step: bad arguments");
         return EMAP_E_INVALID;
     }
-    if (n == 0) return EMAP_OK;
     const int64_t work = n_geo / 4 + (n - (n_geo & ~(int64_t)3));      // float4 words of the geometry range + the remaining elements
     const int grid = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    if (lr_dev) hipLaunchKernelGGL(adam_kernel<LrOnDevice>, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, LrOnDevice{lr_dev}, b1, b2, eps, tail_mask, tail_step);
+    // n == 0: nothing to update, but the call still counts as a step (emap_hip.h: step_dev is incremented by the call)
+    if (n == 0) {}
+    else if (lr_dev) hipLaunchKernelGGL(adam_kernel<LrOnDevice>, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, LrOnDevice{lr_dev}, b1, b2, eps, tail_mask, tail_step);
     else hipLaunchKernelGGL(adam_kernel<LrByValue>, dim3(grid), dim3(256), 0, st, p, g, m, v, step, (long long)n, (long long)n_geo, LrByValue{lr_geo, lr}, b1, b2, eps, tail_mask, tail_step);
     hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, step);
     return check_launch("adam_step");
